@@ -10,9 +10,14 @@ half-sweep; the total work is fixed (scaling "strong"). `--gpus N` without
 torchrun starts the N rank processes itself (torch.distributed.run, before
 any GPU call). With 8 or more ranks the line also carries `als_c3`
 (BASELINE configs[2]: 10M x 1M at 1 %, rank 64, user-sharded with chunked
-RCCL all-gathers); `--config c3` makes c3 the headline (8 ranks required).
+RCCL all-gathers) under `--full`; `--config c3` makes c3 the headline (8
+ranks required).
 
-Also measured in the same run (not the headline value):
+A plain run generates the inputs, runs `--warmup` untimed and `--steps` timed
+epochs and prints the line (`ms_per_step` = one timed epoch); `--dump-outputs
+DIR` also writes the factors the last timed epoch produced (dump_outputs).
+
+With `--full` also measured in the same run (not the headline value):
   * scoring: B users x all items, JVM-exact ALS dot + stable top-5 on the
     device (pairs scored and consumed by top-k per second);
   * roofline of the dominant kernel (als_half_sweep_f64_kernel), timed with
@@ -636,12 +641,34 @@ def max_over_ranks(x, world):
     return float(t.item())
 
 
-def run_als(cfg, world, rank, group, chunks, steps, warmup, accum_mode, stream):
+DUMP_BYTES_PER_ARRAY = 30_000_000  # two arrays: under 64 MB in all
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: what the timed epochs leave their caller, the item and
+    user factor matrices ([rows, rank] float32, global row order) as
+    item_factors.npy / user_factors.npy. A matrix above DUMP_BYTES_PER_ARRAY
+    is written as a fixed sample of its rows (ascending row ids drawn by
+    numpy's default_rng, seeds 1 / 2), the same rows in every run."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for seed, (name, fac) in enumerate((("item_factors", eng.item_factors), ("user_factors", eng.user_factors)), 1):
+        n, k = fac.shape
+        keep = DUMP_BYTES_PER_ARRAY // (4 * k)
+        if n > keep:
+            rows = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+            fac = fac[torch.as_tensor(rows, device=fac.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), fac.to(torch.float32).cpu().numpy())
+
+
+def run_als(cfg, world, rank, group, chunks, steps, warmup, accum_mode, stream, compute_only=True, dump_dir=None):
     """One configuration's ALS fit timed: this rank's CSR / CSC shard
     generated on the device, `warmup` untimed + `steps` timed epochs (barrier
-    + synchronize on both sides, max over ranks), then one compute-only epoch
-    (the same kernels without the all-gathers) for the collective time that
-    is not hidden. Returns (engine, csr, csc, facts)."""
+    + synchronize on both sides, max over ranks), the factors written to
+    dump_dir (rank 0, dump_outputs) when given, then with compute_only one
+    compute-only epoch (the same kernels without the all-gathers) for the
+    collective time that is not hidden. Returns (engine, csr, csc, facts)."""
     k = cfg["rank"]
     n_users, n_items = cfg["users"], cfg["items"]
     # ALS shards: chunk-interleaved when W > 1 so each chunk's all-gather
@@ -704,14 +731,18 @@ def run_als(cfg, world, rank, group, chunks, steps, warmup, accum_mode, stream):
     elapsed = max_over_ranks(time.perf_counter() - t0, world)
     item_ms = sum(e[0].elapsed_time(e[1]) for e in ev) / len(ev)
     user_ms = sum(e[1].elapsed_time(e[2]) for e in ev) / len(ev)
+    if dump_dir and rank == 0:
+        dump_outputs(eng, dump_dir)
 
     # the same epoch's kernels without the collectives (after the timed region)
-    c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    c0.record(stream)
-    eng.compute_only_epoch()
-    c1.record(stream)
-    torch.cuda.synchronize()
-    compute_ms = max_over_ranks(c0.elapsed_time(c1), world)
+    compute_ms = None
+    if compute_only:
+        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        c0.record(stream)
+        eng.compute_only_epoch()
+        c1.record(stream)
+        torch.cuda.synchronize()
+        compute_ms = max_over_ranks(c0.elapsed_time(c1), world)
     ms_per_step = elapsed / steps * 1e3
     facts = dict(k=k, n_users=n_users, n_items=n_items, elapsed=elapsed, ms_per_step=ms_per_step,
                  item_ms=item_ms, user_ms=user_ms, nnz_user=nnz_user, nnz_item=nnz_item, per_rank_nnz=per_rank_nnz,
@@ -720,7 +751,8 @@ def run_als(cfg, world, rank, group, chunks, steps, warmup, accum_mode, stream):
                  u_real=sum(c for _, c in u_lay.part_rows(rank)), i_real=sum(c for _, c in i_lay.part_rows(rank)),
                  collectives={"world_size": world, "epoch_ms": ms_per_step,
                               "compute_only_epoch_ms_max_over_ranks": compute_ms,
-                              "collective_ms_not_hidden_per_epoch": max(0.0, ms_per_step - compute_ms),
+                              "collective_ms_not_hidden_per_epoch": (max(0.0, ms_per_step - compute_ms)
+                                                                     if compute_only else None),
                               "allgather_bytes_per_epoch_replicated": (eng.U.numel() + eng.V.numel()) * 4
                               if world > 1 else 0,
                               "note": ("epoch wall time (max over ranks) minus the same epoch's half-sweep "
@@ -776,6 +808,13 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every secondary line (scoring, hybrid, ingest, c4, c5, rank 256, two-tower "
+                         "training, the API call, c3 with 8 ranks), the compute-only epoch, the CPU baselines, the "
+                         "checks and the profile counters; the options below select among them and need --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the factors the last timed epoch produced to DIR/item_factors.npy and "
+                         "DIR/user_factors.npy (float32; a fixed row sample of a matrix above 30 MB)")
     ap.add_argument("--score-users", type=int, default=1024)
     ap.add_argument("--hybrid-users", type=int, default=256,
                     help="users per batch of the end-to-end hybrid top-5 measurement (0 = skip)")
@@ -831,6 +870,11 @@ def main():
         args.rank256_epochs = 0 if big else 1
     if args.c3_epochs is None:
         args.c3_epochs = 2
+    if not args.full:
+        # a plain run: set up, warm up, time the epochs, print the headline
+        args.score_users = args.hybrid_users = args.c4_items = args.c5_users = 0
+        args.rank256_epochs = args.c3_epochs = args.api_reps = args.tt_steps = 0
+        args.ingest, args.no_cpu_baseline = False, True
     # HREC_BENCH_BACKEND=gloo + HREC_BENCH_DEVICE=0: rehearsal of the W > 1
     # flow with every rank on one GPU (RCCL refuses two ranks per device);
     # the driver's multi-GPU runs use the defaults (RCCL, one GPU per rank).
@@ -847,7 +891,8 @@ def main():
 
     stream = torch.cuda.current_stream()
     chunks = args.chunks if world > 1 else 1
-    eng, csr, csc, als = run_als(cfg, world, rank, group, chunks, args.steps, args.warmup, args.accum_mode, stream)
+    eng, csr, csc, als = run_als(cfg, world, rank, group, chunks, args.steps, args.warmup, args.accum_mode, stream,
+                                 compute_only=args.full, dump_dir=args.dump_outputs)
     k, n_users, n_items = als["k"], als["n_users"], als["n_items"]
     u0, u_per = als["u0"], als["u_per"]
     u_real, i_real = als["u_real"], als["i_real"]
@@ -1286,7 +1331,7 @@ def main():
     # scripts/summarize_profile.py); otherwise null + the reason.
     traffic, traffic_src, tsw, pj, fresh = None, None, None, {}, {}
     traffic_sides = None
-    prof = args.traffic_json or latest_profile()
+    prof = (args.traffic_json or latest_profile()) if args.full else None
     if prof and os.path.exists(prof) and args.accum_mode == 0:
         with open(prof) as f:
             pj = json.load(f)
@@ -1388,7 +1433,8 @@ def main():
             "als_rank256": als256,
             "als_c3": als_c3,
         }
-        attach_counters(line, pj if world == 1 else {}, prof)
+        if args.full:
+            attach_counters(line, pj if world == 1 else {}, prof)
         print(json.dumps(line))
     if world > 1:
         dist.destroy_process_group()

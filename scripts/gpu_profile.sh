@@ -9,8 +9,8 @@ set -e
 python -c "import __graft_entry__ as g; g.build()"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-A="--no-cpu-baseline --steps 3 --warmup 1"
-ONE="--steps 1 --warmup 0 --no-cpu-baseline"
+A="--full --no-cpu-baseline --steps 3 --warmup 1"
+ONE="--full --steps 1 --warmup 0 --no-cpu-baseline"
 MFMA="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"
 passes() {  # passes <tag> <args...>: FETCH, WRITE and MFMA passes of one bench subset
   tag=$1; shift

@@ -6,7 +6,7 @@ K=$1; shift
 python -c "import __graft_entry__ as g; g.build()"
 mkdir -p gpurun_out/pmck
 export TMPDIR=/tmp
-A="--no-cpu-baseline --no-ingest --steps 1 --warmup 0 $*"
+A="--full --no-cpu-baseline --no-ingest --steps 1 --warmup 0 $*"
 i=0
 for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" \
            "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" \

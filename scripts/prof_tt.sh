@@ -2,7 +2,7 @@
 set -e
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-A="--steps 1 --warmup 0 --no-cpu-baseline --no-ingest --score-users 0 --hybrid-users 0 --c4-items 0 --c5-users 0"
+A="--full --steps 1 --warmup 0 --no-cpu-baseline --no-ingest --score-users 0 --hybrid-users 0 --c4-items 0 --c5-users 0"
 timeout -k 10 300 python bench.py $A > gpurun_out/tt.json
 python -c "import json; print(json.load(open('gpurun_out/tt.json'))['tt_train'])"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/ptt -o ptt -- python bench.py $A > /dev/null 2> gpurun_out/ptt.err

@@ -1,7 +1,7 @@
 """GPU: the ALS cold-start fallback precomputed once per model
 (csrc/cold_start.hip, hrec_cold_fallback) —
 ALSModel.predict_for_user's value for an item the transform left NaN
-(/root/reference/src/als_model.py:78-86: the mean rating of the <= 3 most
+(the reference's src/als_model.py:78-86: the mean rating of the <= 3 most
 similar other items with cosine > 0.5, :93-104, else the global mean).
 
 Tolerance: BIT-EXACT. The vector must equal, item by item, what the per-item

@@ -1,6 +1,6 @@
 """GPU parity of the exact hybrid top-k without score matrices
 (csrc/hybrid_exact.hip, hrec_hybrid_exact_*) — get_hybrid_recommendations
-(/root/reference/src/hybrid_system.py:57-75, :95-116) for a batch of users at
+(the reference's src/hybrid_system.py:57-75, :95-116) for a batch of users at
 the reference's numerics: the JVM-exact ALS dot (Spark ALSModel.transform,
 src/als_model.py:75) and the f32 Keras Dot (src/two_tower_model.py:80).
 
