@@ -71,7 +71,7 @@
 namespace hrec {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
-typedef float f4 __attribute__((ext_vector_type(4)));
+typedef hrec_f4 f4;
 
 template <int NT>
 struct Vec;
@@ -99,17 +99,11 @@ struct Vec<1> {
 
 __device__ __forceinline__ int tri(int i) { return (i * (i + 1)) >> 1; }
 
-// Structured buffer loads (buffer_load_dword* ... idxen offen): address =
+// Structured buffer loads (sbuf_load_f4 / _f2 / _f1 of common.h): address =
 // base + vindex * stride + voffset, with the hardware range check
 // (vindex >= num_records reads as zero).
-typedef int i4v __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-__device__ f4 sbuf_load_f4(i4v rsrc, int vindex, int voffset, int soffset, int aux) __asm(
-    "llvm.amdgcn.struct.buffer.load.v4f32");
-__device__ f2 sbuf_load_f2(i4v rsrc, int vindex, int voffset, int soffset, int aux) __asm(
-    "llvm.amdgcn.struct.buffer.load.v2f32");
-__device__ float sbuf_load_f1(i4v rsrc, int vindex, int voffset, int soffset, int aux) __asm(
-    "llvm.amdgcn.struct.buffer.load.f32");
+typedef hrec_rsrc_t i4v;
+typedef hrec_f2 f2;
 
 // Four f64 source-factor columns (32 B) of one gathered row: two 16-B
 // structured loads (S64 gathers: source factors kept in f64, no conversion).

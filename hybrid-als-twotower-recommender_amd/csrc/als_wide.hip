@@ -80,9 +80,6 @@ __device__ unsigned long long g_wide_stamps[8];
 
 typedef double wd4 __attribute__((ext_vector_type(4)));
 
-__device__ float wide_sbuf_load_f1(hrec_rsrc_t rsrc, int vindex, int voffset, int soffset, int aux) __asm(
-    "llvm.amdgcn.struct.buffer.load.f32");
-
 // Waves per row: 8 for kp <= 128; 16 for kp >= 192, so that each wave's
 // share of the register-resident Gramian tiles (<= 9 x 8 VGPRs) fits the
 // 128 VGPRs of a 1024-thread block.
@@ -247,7 +244,7 @@ __global__ __launch_bounds__(WideShape<NT>::THREADS) void als_half_sweep_wide_ke
         const int e = tid + q * kWideThreads;
         p = win * WR + (e < S::F4 ? e / (KP / 4) : 0);
       }
-      ix[q] = __float_as_int(wide_sbuf_load_f1(irs, p < n32 ? p : n32 - 1, 0, 0, 0));
+      ix[q] = __float_as_int(sbuf_load_f1(irs, p < n32 ? p : n32 - 1, 0, 0, 0));
     }
   };
   auto load_rows = [&](int win, const int (&ix)[S::F4_PER_T]) {
@@ -271,7 +268,7 @@ __global__ __launch_bounds__(WideShape<NT>::THREADS) void als_half_sweep_wide_ke
     // the ratings: consumed at the window's conversion, so one window ahead
     const int l = kUniRow ? __lane_id() : tid;  // the rating slots are lanes 0..WR-1 of wave 0
     const int pr = win * WR + (l < WR ? l : 0);
-    lr = wide_sbuf_load_f1(vrs, pr < n32 ? pr : n32 - 1, 0, 0, 0);
+    lr = sbuf_load_f1(vrs, pr < n32 ? pr : n32 - 1, 0, 0, 0);
     okr = tid < WR && win * WR + l < n32;
   };
   auto load_window = [&](int win) {  // window `win` now (prologue)

@@ -12,8 +12,9 @@
 // reference's protocol is cold, so every candidate takes the fallback).
 //
 //   1. cold_norm_kernel: x_j = f_j / |f_j| (a zero norm -> 1), the
-//      arithmetic of cosine_kernel (csrc/score.hip) and of sklearn's
-//      normalize: the same bits for every similarity;
+//      arithmetic of cosine_kernel (below; both take the norm from
+//      cos_row_norm) and of sklearn's normalize: the same bits for every
+//      similarity;
 //   2. cold_pairs_kernel: a thread per query item q, a block per (256
 //      queries, item slice); the slice's rows staged in LDS (every thread reads
 //      the same row: a broadcast), sim(q, j) = sum_c x_qc x_jc as the
@@ -36,16 +37,48 @@ constexpr int kColdTile = 256;  // items staged per LDS round
 constexpr int kColdMaxDim = 16;
 constexpr int kColdK = 3;       // _find_similar_items' k
 
+// |f| of a feature row as sklearn's normalize takes it (sequential non-FMA
+// f64 chain; callers keep contraction off), a zero norm replaced by 1.
+__device__ __forceinline__ double cos_row_norm(const double* __restrict__ f, int dim) {
+#pragma clang fp contract(off)
+  double nr = 0.0;
+  for (int c = 0; c < dim; ++c) nr = nr + f[c] * f[c];
+  nr = sqrt(nr);
+  if (nr == 0.0) nr = 1.0;
+  return nr;
+}
+
+// ALSModel._find_similar_items (src/als_model.py:93-104): sklearn
+// cosine_similarity([target], [other]) = dot(a/|a|, b/|b|) with a zero norm
+// replaced by 1. One thread per (query, item); the query's own row -> -inf so
+// it never ranks (the reference skips it).
+__global__ __launch_bounds__(256) void cosine_kernel(const double* __restrict__ feats, int64_t n_items, int dim,
+                                                     const int64_t* __restrict__ qrows, double* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int64_t q = blockIdx.y;
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n_items) return;
+  const int64_t qr = qrows[q];
+  double* o = out + q * n_items;
+  if (j == qr) {
+    o[j] = -__builtin_inf();
+    return;
+  }
+  const double* a = feats + qr * dim;
+  const double* b = feats + j * dim;
+  const double na = cos_row_norm(a, dim), nb = cos_row_norm(b, dim);
+  double dot = 0.0;
+  for (int c = 0; c < dim; ++c) dot = dot + (a[c] / na) * (b[c] / nb);
+  o[j] = dot;
+}
+
 __global__ __launch_bounds__(256) void cold_norm_kernel(const double* __restrict__ feats, int64_t n, int dim,
                                                         double* __restrict__ x) {
 #pragma clang fp contract(off)
   const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= n) return;
   const double* f = feats + j * dim;
-  double nr = 0.0;
-  for (int c = 0; c < dim; ++c) nr = nr + f[c] * f[c];
-  nr = sqrt(nr);
-  if (nr == 0.0) nr = 1.0;
+  const double nr = cos_row_norm(f, dim);
   for (int c = 0; c < dim; ++c) x[j * dim + c] = f[c] / nr;
 }
 
@@ -146,17 +179,43 @@ static int cold_slices(int64_t n) {
   return (int)s;
 }
 
-static size_t cold_al(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace hrec
 
 using namespace hrec;
 
+extern "C" int hrec_cosine_sim(const double* feats, int64_t n_items, int dim, const int64_t* query_rows,
+                               int64_t n_query, double* out, void* stream) {
+  HREC_REQUIRE(n_items >= 0 && n_query >= 0 && dim >= 1, "cosine_sim: bad shape");
+  if (n_items == 0 || n_query == 0) return HREC_OK;
+  HREC_REQUIRE(n_query < 65536, "cosine_sim: at most 65535 queries per call");
+  HREC_REQUIRE(feats && query_rows && out, "cosine_sim: null pointer");
+  const dim3 grid((unsigned)((n_items + 255) / 256), (unsigned)n_query);
+  hipLaunchKernelGGL(cosine_kernel, grid, dim3(256), 0, as_stream(stream), feats, n_items, dim, query_rows, out);
+  return check_launch("cosine_kernel");
+}
+
+// Workspace of hrec_cold_fallback, in carve order.
+struct ColdWs {
+  double* x;   // [n][dim] normalised rows
+  double* pv;  // [n][S][kColdK] the slices' lists
+  int* pj;
+  int* pn;     // [n][S]
+  size_t total;
+};
+static ColdWs cold_layout(void* base, int64_t n, int dim, int S) {
+  ColdWs w{};
+  Carver c(base);
+  w.x = (double*)c.take((size_t)n * dim * 8);
+  w.pv = (double*)c.take((size_t)n * S * kColdK * 8);
+  w.pj = (int*)c.take((size_t)n * S * kColdK * 4);
+  w.pn = (int*)c.take((size_t)n * S * 4);
+  w.total = c.total();
+  return w;
+}
+
 extern "C" size_t hrec_cold_fallback_workspace_bytes(int64_t n_items, int dim) {
   const int64_t n = n_items > 0 ? n_items : 0;
-  const size_t S = (size_t)cold_slices(n);
-  return cold_al((size_t)n * (dim > 0 ? dim : 1) * 8) + cold_al((size_t)n * S * kColdK * 8) +
-         cold_al((size_t)n * S * kColdK * 4) + cold_al((size_t)n * S * 4) + 256;
+  return cold_layout(nullptr, n, dim > 0 ? dim : 1, cold_slices(n)).total;
 }
 
 extern "C" int hrec_cold_fallback(const double* feats, const double* ratings, int64_t n_items, int dim,
@@ -170,14 +229,11 @@ extern "C" int hrec_cold_fallback(const double* feats, const double* ratings, in
   HREC_REQUIRE(workspace_bytes >= need, "cold_fallback: workspace %zu < %zu", workspace_bytes, need);
   hipStream_t s = as_stream(stream);
   const int S = cold_slices(n_items);
-  char* p = (char*)workspace;
-  double* x = (double*)p;
-  p += cold_al((size_t)n_items * dim * 8);
-  double* pv = (double*)p;
-  p += cold_al((size_t)n_items * S * kColdK * 8);
-  int* pj = (int*)p;
-  p += cold_al((size_t)n_items * S * kColdK * 4);
-  int* pn = (int*)p;
+  const ColdWs w = cold_layout(workspace, n_items, dim, S);
+  double* x = w.x;
+  double* pv = w.pv;
+  int* pj = w.pj;
+  int* pn = w.pn;
   const unsigned nb = (unsigned)((n_items + 255) / 256);
   hipLaunchKernelGGL(cold_norm_kernel, dim3(nb), dim3(256), 0, s, feats, n_items, dim, x);
   int rc = check_launch("cold_norm_kernel");

@@ -28,7 +28,27 @@ inline bool hrec_factor_ld_ok(int kp) {
 // idx[i] += off for every id >= 0 (item-shard offsets; csrc/dot_topk.hip).
 int offset_ids(int64_t* idx, int64_t n, int64_t off, hipStream_t s);
 
-// Stable descending top-k of n_rows rows (score.hip): larger first, equal
+// Workspace carving: 256-byte aligned slices of one allocation, in take()
+// order. A null base only sizes, so one layout function serves both a
+// *_workspace_bytes query and the run.
+inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+struct Carver {
+  char* base;
+  size_t off = 0;
+  explicit Carver(void* b) : base(static_cast<char*>(b)) {}
+  char* take(size_t bytes) {
+    char* r = base ? base + off : nullptr;
+    off += al256(bytes);
+    return r;
+  }
+  size_t total() const { return off; }
+};
+
+// Largest top_k of the selection kernels (csrc/topk.hip); above it the sort
+// path (csrc/sort_topk.hip).
+constexpr int kTopkSelectMax = 1024;
+
+// Stable descending top-k of n_rows rows (csrc/topk.hip): larger first, equal
 // values -> smaller original index first (src_idx maps positions to original
 // indices; entries with index -1 are skipped; row_n, if given, bounds row r
 // to its first min(n, row_n[r]) entries). Workspace: topk_ws_bytes.
@@ -66,6 +86,19 @@ __device__ __forceinline__ hrec_rsrc_t rows_rsrc(const void* base, int64_t row0,
   r.w = 0x00020000;
   return r;
 }
+// buffer_load_dword[x2|x4] ... idxen offen (structured: vindex * stride +
+// voffset; vindex >= num_records reads as zero) and buffer_load_dwordx2 ...
+// offen (raw: base + voffset, range-checked).
+typedef float hrec_f4 __attribute__((ext_vector_type(4)));
+typedef float hrec_f2 __attribute__((ext_vector_type(2)));
+__device__ hrec_f4 sbuf_load_f4(hrec_rsrc_t rsrc, int vindex, int voffset, int soffset, int aux) __asm(
+    "llvm.amdgcn.struct.buffer.load.v4f32");
+__device__ hrec_f2 sbuf_load_f2(hrec_rsrc_t rsrc, int vindex, int voffset, int soffset, int aux) __asm(
+    "llvm.amdgcn.struct.buffer.load.v2f32");
+__device__ float sbuf_load_f1(hrec_rsrc_t rsrc, int vindex, int voffset, int soffset, int aux) __asm(
+    "llvm.amdgcn.struct.buffer.load.f32");
+__device__ hrec_f2 rbuf_load_f2(hrec_rsrc_t rsrc, int voffset, int soffset, int aux) __asm(
+    "llvm.amdgcn.raw.buffer.load.v2f32");
 
 // Allow a kernel the CU's whole LDS (160 KiB) as dynamic shared memory, once
 // per kernel (hipFuncSetAttribute costs a runtime call per launch otherwise).
@@ -163,7 +196,7 @@ int minmax_i64_run(const int64_t* x, int64_t n, int64_t* out, hipStream_t s);
 size_t radix_pairs_ws_bytes(int64_t n);
 int radix_pairs_sort(const uint32_t* keys, const uint32_t* p0, const uint32_t* p1, int64_t n, int bits, void* ws,
                      uint32_t* p0_out, uint32_t* p1_out, const uint32_t** keys_sorted, hipStream_t s);
-// csrc/score.hip: hrec_fuse_rows_topk's exact segment path, gated on *gate.
+// csrc/fuse.hip: hrec_fuse_rows_topk's exact segment path, gated on *gate.
 size_t fuse_rows_exact_ws_bytes(int64_t n_rows, int64_t n, int kk);
 int fuse_rows_exact(const float* als, const float* tt, int64_t n_rows, int64_t n, int64_t ld, const float* als_mm,
                     const float* tt_mm, double w0, double w1, int kk, int64_t* out_idx, double* out_val, void* ws,

@@ -38,7 +38,7 @@ namespace hrec {
 constexpr int kGemvThreads = 256;
 constexpr int kGemvMaxB = 4;
 
-typedef float gemv_f4 __attribute__((ext_vector_type(4)));
+typedef hrec_f4 gemv_f4;
 
 #ifndef HREC_GEMV_PIPE
 // 1 = the next round's loads issued before this round's MFMAs (with half the
@@ -60,9 +60,6 @@ struct GemvShape {
   static constexpr int NT = NT0 < 1 ? 1 : NT0;  // 16-item tiles per wave round
   static constexpr int kItems = 16 * NT;            // items per wave round
 };
-
-__device__ gemv_f4 gemv_sbuf_load(hrec_rsrc_t rsrc, int vindex, int voffset, int soffset, int aux) __asm(
-    "llvm.amdgcn.struct.buffer.load.v4f32");
 
 #ifndef HREC_GEMV_AUX
 // cache-policy bits of the item loads: 0 = cached. A wave load covers 64 B of
@@ -106,7 +103,7 @@ __global__ __launch_bounds__(kGemvThreads) void dot_gemv_kernel(
     for (int t = 0; t < NT; ++t)
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
-        it[t][ks] = gemv_sbuf_load(rs, (int)((16 * t + c) * item_step), 64 * ks + 16 * g, 0, HREC_GEMV_AUX);
+        it[t][ks] = sbuf_load_f4(rs, (int)((16 * t + c) * item_step), 64 * ks + 16 * g, 0, HREC_GEMV_AUX);
   };
   int64_t rd = (int64_t)blockIdx.x * (kGemvThreads / 64) + wave;
 #if HREC_GEMV_PIPE

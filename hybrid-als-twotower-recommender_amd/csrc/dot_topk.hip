@@ -27,11 +27,11 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "hybrid_common.h"
 
 namespace hrec {
 
-typedef float dot_f4 __attribute__((ext_vector_type(4)));
+typedef hrec_f4 dot_f4;
 typedef __bf16 dot_bf8 __attribute__((ext_vector_type(8)));
 
 constexpr int kDotThreads = 512;
@@ -44,11 +44,6 @@ struct DotShape {
   static constexpr int kChunks = DK * kElem / 16;   // 16-B chunks per row
   static constexpr int kRow = DK * kElem + 16;      // LDS bytes per user row
 };
-
-typedef int dot_rsrc __attribute__((ext_vector_type(4)));
-// buffer_load_dwordx4 ... idxen offen (structured: vindex * stride + voffset)
-__device__ dot_f4 dot_sbuf_load(dot_rsrc rsrc, int vindex, int voffset, int soffset, int aux) __asm(
-    "llvm.amdgcn.struct.buffer.load.v4f32");
 
 union DotFrag {
   int4 i;
@@ -159,12 +154,12 @@ __global__ __launch_bounds__(kDotThreads) void dot_tile_kernel(
   };
   int vcur[NI], vnext[NI];
   rows_of(ig, vcur);
-  dot_rsrc rs_cur = rsrc_of(ig), rs_next = rs_cur;
+  hrec_rsrc_t rs_cur = rsrc_of(ig), rs_next = rs_cur;
   DotFrag ring[P][NI];
 #pragma unroll
   for (int q = 0; q < P; ++q)
 #pragma unroll
-    for (int t = 0; t < NI; ++t) ring[q][t].f = dot_sbuf_load(rs_cur, vcur[t], voff + 64 * q, 0, 0);
+    for (int t = 0; t < NI; ++t) ring[q][t].f = sbuf_load_f4(rs_cur, vcur[t], voff + 64 * q, 0, 0);
   DotFrag ua[NU];
 #pragma unroll
   for (int u = 0; u < NU; ++u) ua[u] = user_frag(u, 0);
@@ -188,7 +183,7 @@ __global__ __launch_bounds__(kDotThreads) void dot_tile_kernel(
 #pragma unroll
         for (int t = 0; t < NI; ++t) {
           b[t] = ring[q][t];
-          ring[q][t].f = dot_sbuf_load(same ? rs_cur : rs_next, same ? vcur[t] : vnext[t], off, 0, 0);
+          ring[q][t].f = sbuf_load_f4(same ? rs_cur : rs_next, same ? vcur[t] : vnext[t], off, 0, 0);
         }
         const int kn = ks + 1 < S::kSteps ? ks + 1 : 0;
 #pragma unroll
@@ -269,15 +264,10 @@ __global__ void dot_offset_kernel(int64_t* __restrict__ idx, int64_t n, int64_t 
   if (i < n && idx[i] >= 0) idx[i] += off;
 }
 
-// f32 -> bf16 bit patterns, round to nearest even (NaN stays NaN).
+// f32 -> bf16 bit patterns (bf16_rne).
 __global__ void f32_to_bf16_kernel(const float* __restrict__ in, int64_t n, uint16_t* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint32_t x = __float_as_uint(in[i]);
-    uint16_t h;
-    if ((x & 0x7fffffffu) > 0x7f800000u) h = (uint16_t)((x >> 16) | 0x40);
-    else h = (uint16_t)((x + 0x7fffu + ((x >> 16) & 1u)) >> 16);
-    out[i] = h;
-  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = (uint16_t)bf16_rne(in[i]);
 }
 
 // Resident-users variant: the block keeps UB users (up to 128 KB of LDS) and
@@ -384,12 +374,12 @@ __global__ __launch_bounds__(kDotThreads) void dot_res_kernel(
   };
   int vnext[NI];
   rows_of(ig, vnext);
-  dot_rsrc rsrc = rsrc_of(ig);
+  hrec_rsrc_t rsrc = rsrc_of(ig);
   DotFrag it_f[KS][NI];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-    for (int t = 0; t < NI; ++t) it_f[ks][t].f = dot_sbuf_load(rsrc, vnext[t], voff + 64 * ks, 0, 0);
+    for (int t = 0; t < NI; ++t) it_f[ks][t].f = sbuf_load_f4(rsrc, vnext[t], voff + 64 * ks, 0, 0);
   const int n_ch = (UB + 16 * NU - 1) / (16 * NU);
   DotFrag ua[NU];  // user fragments of the next step (chunk 0, step 0 first)
 #pragma unroll
@@ -463,7 +453,7 @@ __global__ __launch_bounds__(kDotThreads) void dot_res_kernel(
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-              for (int t = 0; t < NI; ++t) it_f[ks][t].f = dot_sbuf_load(rsrc, vnext[t], voff + 64 * ks, 0, 0);
+              for (int t = 0; t < NI; ++t) it_f[ks][t].f = sbuf_load_f4(rsrc, vnext[t], voff + 64 * ks, 0, 0);
           }
           return;
         }
@@ -482,7 +472,7 @@ __global__ __launch_bounds__(kDotThreads) void dot_res_kernel(
           for (int t = 0; t < NI; ++t) dot_mma<BF16>(it_f[ks][t], a[u], acc[u][t]);
         if constexpr (last) {  // step ks of this tile is done: refill it with the next tile's
 #pragma unroll
-          for (int t = 0; t < NI; ++t) it_f[ks][t].f = dot_sbuf_load(rsrc, vnext[t], voff + 64 * ks, 0, 0);
+          for (int t = 0; t < NI; ++t) it_f[ks][t].f = sbuf_load_f4(rsrc, vnext[t], voff + 64 * ks, 0, 0);
         }
         // Order the step: each next-step user read sits between MFMA pairs, so
         // the LDS reads overlap the whole step instead of trailing it.
@@ -819,12 +809,6 @@ int offset_ids(int64_t* idx, int64_t n, int64_t off, hipStream_t s) {
   return check_launch("dot_offset_kernel");
 }
 
-static char* dot_carve(char*& p, size_t bytes) {
-  char* r = p;
-  p += (bytes + 255) & ~(size_t)255;
-  return r;
-}
-
 }  // namespace hrec
 
 using namespace hrec;
@@ -876,18 +860,38 @@ extern "C" int hrec_dot_filter(const void* user_vec, int n_users, const void* it
                         cand_idx, cand_n, as_stream(stream));
 }
 
+// Workspace of hrec_dot_topk, in carve order.
+struct DotWs {
+  float* samp;  // [B][S] sample scores
+  char* tws;    // sample top-k workspace
+  float* sv;    // [B][kk] sample top-k values / indices
+  int64_t* si;
+  float* cv;    // [B][cap] candidates
+  int64_t* ci;
+  int* cn;      // [B] counters
+  char* fws;    // final top-k workspace
+  size_t total;
+};
+static DotWs dot_layout(void* base, int B, int64_t n_items, int kk) {
+  DotWs w{};
+  Carver c(base);
+  const int64_t S = dot_sample(n_items, kk), cap = dot_cap(kk);
+  w.samp = (float*)c.take((size_t)B * S * 4);
+  w.tws = c.take(topk_ws_bytes(B, S, kk, 4));
+  w.sv = (float*)c.take((size_t)B * kk * 4);
+  w.si = (int64_t*)c.take((size_t)B * kk * 8);
+  w.cv = (float*)c.take((size_t)B * cap * 4);
+  w.ci = (int64_t*)c.take((size_t)B * cap * 8);
+  w.cn = (int*)c.take((size_t)B * 4);
+  w.fws = c.take(topk_ws_bytes(B, cap, kk, 4));
+  w.total = c.total();
+  return w;
+}
+
 extern "C" size_t hrec_dot_topk_workspace_bytes(int n_users, int64_t n_items, int top_k) {
-  const size_t B = (size_t)(n_users > 0 ? n_users : 0);
   const int kk = (int)(top_k < n_items ? top_k : n_items);
   if (kk <= 0) return 256;
-  const int64_t S = dot_sample(n_items, kk), cap = dot_cap(kk);
-  size_t b = B * (size_t)S * 4 + 256;                 // sample scores
-  b += topk_ws_bytes(B, S, kk, 4) + 256;               // sample top-k workspace
-  b += B * (size_t)kk * 12 + 512;                      // sample top-k values / indices
-  b += B * (size_t)cap * 12 + 512;                     // candidates
-  b += B * 4 + 256;                                    // counters
-  b += topk_ws_bytes(B, cap, kk, 4) + 256;             // final top-k workspace
-  return b;
+  return dot_layout(nullptr, n_users > 0 ? n_users : 0, n_items, kk).total;
 }
 
 extern "C" int hrec_dot_topk(const void* user_vec, int n_users, const void* item_vec, int64_t n_items, int dk,
@@ -904,45 +908,37 @@ extern "C" int hrec_dot_topk(const void* user_vec, int n_users, const void* item
   hipStream_t s = as_stream(stream);
   const int kk = (int)(top_k < n_items ? top_k : n_items);
   const int64_t S = dot_sample(n_items, kk), cap = dot_cap(kk);
-  char* p = (char*)workspace;
-  float* samp = (float*)dot_carve(p, (size_t)n_users * S * 4);
-  char* tws = dot_carve(p, topk_ws_bytes(n_users, S, kk, 4));
-  float* sv = (float*)dot_carve(p, (size_t)n_users * kk * 4);
-  int64_t* si = (int64_t*)dot_carve(p, (size_t)n_users * kk * 8);
-  float* cv = (float*)dot_carve(p, (size_t)n_users * cap * 4);
-  int64_t* ci = (int64_t*)dot_carve(p, (size_t)n_users * cap * 8);
-  int* cn = (int*)dot_carve(p, (size_t)n_users * 4);
-  char* fws = dot_carve(p, topk_ws_bytes(n_users, cap, kk, 4));
+  const DotWs w = dot_layout(workspace, n_users, n_items, kk);
   if (hipMemsetAsync(overflow, 0, sizeof(int), s) != hipSuccess) return check_launch("dot_topk: memset");
   if (S == n_items && thr_in == nullptr) {  // small: every score, exact top-k
-    rc = dot_launch<false>(user_vec, n_users, item_vec, n_items, n_items, 1, dk, dtype, samp, n_items, nullptr, 0, 0, nullptr,
+    rc = dot_launch<false>(user_vec, n_users, item_vec, n_items, n_items, 1, dk, dtype, w.samp, n_items, nullptr, 0, 0, nullptr,
                            nullptr, nullptr, 0, s);
     if (rc) return rc;
-    rc = topk_rows<float>(samp, n_users, n_items, n_items, kk, out_idx, out_val, tws, (size_t)1 << 62, s);
+    rc = topk_rows<float>(w.samp, n_users, n_items, n_items, kk, out_idx, out_val, w.tws, (size_t)1 << 62, s);
   } else {
     const float* thr = thr_in;
     int thr_stride = 1;
     if (thr == nullptr) {  // 1) thresholds: the kk-th best of S strided items
       const int64_t step = n_items / S;
-      rc = dot_launch<false>(user_vec, n_users, item_vec, n_items, S, step, dk, dtype, samp, S, nullptr, 0, 0, nullptr,
+      rc = dot_launch<false>(user_vec, n_users, item_vec, n_items, S, step, dk, dtype, w.samp, S, nullptr, 0, 0, nullptr,
                              nullptr, nullptr, 0, s);
       if (rc) return rc;
-      rc = topk_rows<float>(samp, n_users, S, S, kk, si, sv, tws, (size_t)1 << 62, s);
+      rc = topk_rows<float>(w.samp, n_users, S, S, kk, w.si, w.sv, w.tws, (size_t)1 << 62, s);
       if (rc) return rc;
-      thr = sv + (kk - 1);
+      thr = w.sv + (kk - 1);
       thr_stride = kk;
     }
     // 2) fused score + survivor filter over every item
-    if (hipMemsetAsync(cn, 0, (size_t)n_users * 4, s) != hipSuccess)
+    if (hipMemsetAsync(w.cn, 0, (size_t)n_users * 4, s) != hipSuccess)
       return check_launch("dot_topk: memset");
     rc = dot_launch<true>(user_vec, n_users, item_vec, n_items, n_items, 1, dk, dtype, nullptr, 0, thr, thr_stride, (int)cap,
-                          cv, ci, cn, 0, s);
+                          w.cv, w.ci, w.cn, 0, s);
     if (rc) return rc;
-    hipLaunchKernelGGL(dot_overflow_kernel, dim3(64), dim3(256), 0, s, cn, n_users, (int)cap, overflow);
+    hipLaunchKernelGGL(dot_overflow_kernel, dim3(64), dim3(256), 0, s, w.cn, n_users, (int)cap, overflow);
     rc = check_launch("dot_overflow_kernel");
     if (rc) return rc;
     // 3) exact stable top-k of the survivors (item index breaks ties)
-    rc = topk_rows<float>(cv, n_users, cap, cap, kk, out_idx, out_val, fws, (size_t)1 << 62, s, ci, cn);
+    rc = topk_rows<float>(w.cv, n_users, cap, cap, kk, out_idx, out_val, w.fws, (size_t)1 << 62, s, w.ci, w.cn);
   }
   if (rc) return rc;
   return offset_ids(out_idx, (int64_t)n_users * kk, idx_offset, s);

@@ -1,8 +1,8 @@
-// Device helpers shared by the pruned hybrid top-k kernels (csrc/hybrid_prune.hip,
-// bf16 c5 path; csrc/hybrid_exact.hip, exact c2 path): the fusion arithmetic of
-// fuse_rows_kernel (src/hybrid_system.py:57-75), the top-k order of
-// score.hip's better() (sorted(..., reverse=True) over the reference's
-// candidate order, src/hybrid_system.py:108) and 64-bit lane moves.
+// Device helpers shared by the scoring, top-k and fusion kernels: the bf16
+// rounding (hrec_f32_to_bf16), the top-k order (sorted(..., reverse=True) over
+// the reference's candidate order, src/hybrid_system.py:108), the fusion
+// arithmetic (src/hybrid_system.py:57-75) and 64-bit lane moves. Each rule
+// has its one definition here.
 #pragma once
 
 #include <float.h>
@@ -12,17 +12,23 @@
 
 namespace hrec {
 
-typedef float hp_f4 __attribute__((ext_vector_type(4)));
+typedef hrec_f4 hp_f4;
 
 // f32 -> bf16 bits, round to nearest even (NaN stays NaN): hrec_f32_to_bf16.
-__device__ __forceinline__ uint32_t hp_bf16(float v) {
+__device__ __forceinline__ uint32_t bf16_rne(float v) {
   const uint32_t x = __float_as_uint(v);
   if ((x & 0x7fffffffu) > 0x7f800000u) return (x >> 16) | 0x40u;
   return (x + 0x7fffu + ((x >> 16) & 1u)) >> 16;
 }
 
-// The scaler coefficients of fuse_rows_kernel (sklearn MinMaxScaler: ALS in
-// f64, two-tower in f32; range < 10 eps -> 1).
+// sklearn MinMaxScaler's range (container sklearn _data.py:518-522, 261-262):
+// a range below 10 eps of its dtype scales by 1.
+__device__ __forceinline__ double mm_range(double r) { return r < 10.0 * DBL_EPSILON ? 1.0 : r; }
+__device__ __forceinline__ float mm_range(float r) { return r < 10.0f * FLT_EPSILON ? 1.0f : r; }
+
+// The scaler coefficients of the batched fusion (MinMaxScaler.fit_transform:
+// scale = 1 / range, min_ = 0 - min * scale; ALS in f64 as the reference's
+// als scores are Python floats, two-tower in f32 as np.float32 scores).
 struct HpScale {
   double ascale, amin_;
   float tscale, tmin_;
@@ -30,18 +36,17 @@ struct HpScale {
 __device__ __forceinline__ HpScale hp_scale(float amin, float amax, float tmin, float tmax) {
 #pragma clang fp contract(off)
   HpScale s;
-  double arange = (double)amax - (double)amin;
-  if (arange < 10.0 * DBL_EPSILON) arange = 1.0;
-  s.ascale = 1.0 / arange;
+  s.ascale = 1.0 / mm_range((double)amax - (double)amin);
   s.amin_ = 0.0 - (double)amin * s.ascale;
-  float trange = tmax - tmin;
-  if (trange < 10.0f * FLT_EPSILON) trange = 1.0f;
-  s.tscale = 1.0f / trange;
+  s.tscale = 1.0f / mm_range(tmax - tmin);
   s.tmin_ = 0.0f - tmin * s.tscale;
   return s;
 }
-// Non-decreasing in a and in t (positive scales and weights, rounding is
-// monotone): the fused score of an upper bound of (a, t) bounds the item's.
+// fused = w0 * als_norm + w1 * (double)tt_norm (y = x * scale + min_, two
+// roundings each in the input dtype; numpy 1.21 scalar promotion widens the
+// f32 tt_norm before the multiply). Non-decreasing in a and in t (positive
+// scales and weights, rounding is monotone): the fused score of an upper
+// bound of (a, t) bounds the item's.
 __device__ __forceinline__ double hp_fuse(const HpScale& s, float a, float t, double w0, double w1) {
 #pragma clang fp contract(off)
   const double an = (double)a * s.ascale + s.amin_;
@@ -49,21 +54,51 @@ __device__ __forceinline__ double hp_fuse(const HpScale& s, float a, float t, do
   return w0 * an + w1 * (double)tn;
 }
 
-// Order of the fused top-k (score.hip's better()): larger first, equal ->
-// smaller item id, NaN last.
-__device__ __forceinline__ bool hp_better(double va, int64_t ia, double vb, int64_t ib) {
+// Order of every top-k: larger value first; equal values -> smaller index
+// first (a stable descending sort of the input order). NaN sorts last.
+template <typename T>
+__device__ __forceinline__ bool better(T va, int64_t ia, T vb, int64_t ib) {
   const bool na = va != va, nb = vb != vb;
   if (na || nb) return !na && nb ? true : (na && nb ? ia < ib : false);
   return va > vb || (va == vb && ia < ib);
 }
 
-// hp_better's order as one unsigned key (larger = better; ties -> the smaller
-// item): 0 = an empty slot (idx INT64_MAX), 1 = NaN, numbers above by their
-// ordered bits (-0 folded into +0, equal values share a key).
+template <typename T>
+struct KV {
+  T v;
+  int64_t i;
+};
+
+template <typename T>
+__device__ __forceinline__ KV<T> wave_best(KV<T> x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    KV<T> y;
+    y.v = __shfl_xor(x.v, off, kWave);
+    y.i = __shfl_xor(x.i, off, kWave);
+    // lanes without a candidate carry i = INT64_MAX and lose every comparison
+    const bool take = (x.i == INT64_MAX) ? (y.i != INT64_MAX)
+                                         : (y.i != INT64_MAX && better(y.v, y.i, x.v, x.i));
+    if (take) x = y;
+  }
+  return x;
+}
+
+// better()'s value order as one unsigned key (larger = better, equal values
+// share a key): 0 = NaN, numbers above by their ordered bits.
+__device__ __forceinline__ uint64_t order_key(double v) {
+  if (v != v) return 0;  // NaN ranks below every number
+  const uint64_t b = (uint64_t)__double_as_longlong(v + 0.0);  // -0 -> +0 (they compare equal)
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double key_value(uint64_t k) {
+  if (k == 0) return __builtin_nan("");
+  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+// The same with a key below NaN's for an empty slot (idx INT64_MAX): 0 =
+// empty, 1 = NaN, numbers by order_key (ties -> the smaller item).
 __device__ __forceinline__ uint64_t hp_order_key(double v, int64_t idx) {
-  const double z = v + 0.0;  // -0 + 0 = +0
-  const uint64_t u = (uint64_t)__double_as_longlong(z);
-  const uint64_t ord = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+  const uint64_t ord = order_key(v);
   return idx == INT64_MAX ? 0ull : (v != v ? 1ull : ord);
 }
 
@@ -164,7 +199,7 @@ struct HpList {
   __device__ __forceinline__ void insert(double xv, int64_t xi) {
 #pragma unroll
     for (int j = 0; j < KK; ++j) {  // compare-exchange chain (sorted list)
-      const bool sw = i[j] == INT64_MAX || hp_better(xv, xi, v[j], i[j]);
+      const bool sw = i[j] == INT64_MAX || better(xv, xi, v[j], i[j]);
       const double tv = v[j];
       const int64_t ti = i[j];
       v[j] = sw ? xv : tv;

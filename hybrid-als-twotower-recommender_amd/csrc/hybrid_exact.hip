@@ -53,8 +53,6 @@ namespace hrec {
 
 typedef float hx_f16 __attribute__((ext_vector_type(16)));
 typedef __bf16 hx_bf8 __attribute__((ext_vector_type(8)));
-__device__ hp_f4 hx_sbuf_load(hrec_rsrc_t rsrc, int vindex, int voffset, int soffset, int aux) __asm(
-    "llvm.amdgcn.struct.buffer.load.v4f32");
 
 union HxFrag {
   int4 i;
@@ -107,9 +105,9 @@ __device__ __forceinline__ float hx_u2f(uint32_t u) { return __uint_as_float(u);
 
 // Split bf16 of x: hi = bf16(x), lo = bf16(x - hi) (x - hi is exact in f32).
 __device__ __forceinline__ void hx_split(float x, uint16_t& hi, uint16_t& lo) {
-  const uint32_t h = hp_bf16(x);
+  const uint32_t h = bf16_rne(x);
   hi = (uint16_t)h;
-  lo = (uint16_t)hp_bf16(x - __uint_as_float(h << 16));
+  lo = (uint16_t)bf16_rne(x - __uint_as_float(h << 16));
 }
 
 // 0. Split bf16 user operands [2][B][2 DK] ([hi | lo] per row): the ALS rows
@@ -233,8 +231,8 @@ __global__ __launch_bounds__(HxShape<DK>::kThreads, DK == 64 ? HxShape<DK>::kBlo
     for (int p = 0; p < 2; ++p)
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        fa[p][ks].f = hx_sbuf_load(ra, vi, p * (DK * 2) + 32 * ks + 16 * h, 0, 0);
-        ft[p][ks].f = hx_sbuf_load(rt, vi, p * (DK * 2) + 32 * ks + 16 * h, 0, 0);
+        fa[p][ks].f = sbuf_load_f4(ra, vi, p * (DK * 2) + 32 * ks + 16 * h, 0, 0);
+        ft[p][ks].f = sbuf_load_f4(rt, vi, p * (DK * 2) + 32 * ks + 16 * h, 0, 0);
       }
   };
   int64_t jb = i0 + 32 * w;
@@ -748,7 +746,7 @@ __global__ __launch_bounds__(kHxThreads2) void hx_pre_kernel(HxArgs a) {
     for (int g = 64 * wv + lane; g < G; g += 64 * 8) {
       const float4 x = st_row[g];
       const double u = hp_fuse(sc0, hx_up((double)x.x + Ea), hx_up((double)x.z + Et), w0, w1);
-      if (bg == INT64_MAX || hp_better(u, g, bu, bg)) {
+      if (bg == INT64_MAX || better(u, g, bu, bg)) {
         bu = u;
         bg = g;
       }
@@ -779,7 +777,7 @@ __global__ __launch_bounds__(kHxThreads2) void hx_pre_kernel(HxArgs a) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int ge = s_sg[e];
-        r += ge >= 0 && ge != gl && hp_better(s_sv[e], ge, v, gl);
+        r += ge >= 0 && ge != gl && better(s_sv[e], ge, v, gl);
       }
       rank = gl >= 0 ? r : 99;
     }
@@ -1137,30 +1135,25 @@ struct HxWs {
 
 static HxWs hx_layout(char* base, int B, int64_t N, int dk) {
   HxWs w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* r = base ? base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return r;
-  };
+  Carver c(base);
   const int64_t G = (N + kHxGrp - 1) / kHxGrp;
-  w.uop = (uint16_t*)take((size_t)2 * B * dk * 4);
-  w.uf = (float*)take((size_t)2 * B * dk * 4);
-  w.uok = (int*)take((size_t)B * 4);
-  w.stats = (float*)take((size_t)B * G * 16);
-  w.counts = (int*)take((size_t)2 * B * 4);
-  w.flag = (int*)take(16);  // flag, pair_total
-  w.rec = (HxRec*)take((size_t)B * sizeof(HxRec));
+  w.uop = (uint16_t*)c.take((size_t)2 * B * dk * 4);
+  w.uf = (float*)c.take((size_t)2 * B * dk * 4);
+  w.uok = (int*)c.take((size_t)B * 4);
+  w.stats = (float*)c.take((size_t)B * G * 16);
+  w.counts = (int*)c.take((size_t)2 * B * 4);
+  w.flag = (int*)c.take(16);  // flag, pair_total
+  w.rec = (HxRec*)c.take((size_t)B * sizeof(HxRec));
   const size_t n_pairs = (size_t)B * hx_pair_cap((int)G);
-  w.pairs = (int4*)take(n_pairs * 16);
-  w.cv = (double*)take(n_pairs * kHxSlots * 8);
-  w.ci = (int64_t*)take(n_pairs * kHxSlots * 8);
-  w.pc = (int*)take(n_pairs * 4);
-  w.total = off + 256;
+  w.pairs = (int4*)c.take(n_pairs * 16);
+  w.cv = (double*)c.take(n_pairs * kHxSlots * 8);
+  w.ci = (int64_t*)c.take(n_pairs * kHxSlots * 8);
+  w.pc = (int*)c.take(n_pairs * 4);
+  w.total = c.total() + 256;
   return w;
 }
 
-static size_t hx_items_bytes(int64_t N, int dk) { return (((size_t)2 * N * dk * 4 + 255) & ~(size_t)255) + 256; }
+static size_t hx_items_bytes(int64_t N, int dk) { return al256((size_t)2 * N * dk * 4) + 256; }
 static const float* hx_norms(const void* prepared, int64_t N, int dk) {
   return reinterpret_cast<const float*>(static_cast<const char*>(prepared) + hx_items_bytes(N, dk) - 256);
 }

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256) void hp_user_ops_kernel(const float* __restric
   for (int c = threadIdx.x; c < dk; c += blockDim.x) {
     float v = 0.f;
     if (c < wd) v = bad ? __builtin_nanf("") : src[row * ld + c];
-    out[c] = (uint16_t)hp_bf16(v);
+    out[c] = (uint16_t)bf16_rne(v);
   }
 }
 
@@ -445,50 +445,13 @@ __global__ __launch_bounds__(512) void hp_cand_topk_kernel(const int* __restrict
   const bool flagged = uflag[b] || nb > cap || nb < kk;  // block-uniform
   const float amin = als_mm[b], amax = als_mm[B + b], tmin = tt_mm[b], tmax = tt_mm[B + b];
   const HpScale sc = hp_scale(amin, amax, tmin, tmax);
-  double lv[KK];
-  int64_t li[KK];
-  auto reset = [&]() {
-#pragma unroll
-    for (int j = 0; j < KK; ++j) {
-      lv[j] = 0.0;
-      li[j] = INT64_MAX;  // empty slot
-    }
-  };
-  auto insert = [&](double xv, int64_t xi) {
-#pragma unroll
-    for (int j = 0; j < KK; ++j) {  // compare-exchange chain (sorted list)
-      const bool sw = li[j] == INT64_MAX || hp_better(xv, xi, lv[j], li[j]);
-      const double tv = lv[j];
-      const int64_t ti = li[j];
-      lv[j] = sw ? xv : tv;
-      li[j] = sw ? xi : ti;
-      xv = sw ? tv : xv;
-      xi = sw ? ti : xi;
-    }
-  };
+  HpList<KK> L;  // the lane's sorted best KK
   auto fused = [&](float h, float l) { return hm ? hp_fuse(sc, l, h, w0, w1) : hp_fuse(sc, h, l, w0, w1); };
-  auto wave_best = [&](double& bv, int64_t& bi) { hp_wave_best(bv, bi); };  // csrc/hybrid_common.h
   // the lanes' lists -> each wave's best kk (LDS) -> wave 0's merge; writes
   // the outputs when `write`; returns (in s_full) whether a NaN or a missing
   // entry is among the kk. Called block-uniformly.
   auto merge = [&](bool write) {
-    for (int r = 0; r < kk; ++r) {
-      double bv = lv[0];
-      int64_t bi = li[0];
-      wave_best(bv, bi);
-      if (lane == 0) {
-        rv[wv * KK + r] = bv;
-        ri[wv * KK + r] = bi;
-      }
-      if (bi != INT64_MAX && li[0] == bi) {  // the (unique) owner pops its head
-#pragma unroll
-        for (int j = 0; j + 1 < KK; ++j) {
-          lv[j] = lv[j + 1];
-          li[j] = li[j + 1];
-        }
-        li[KK - 1] = INT64_MAX;
-      }
-    }
+    L.wave_top(kk, lane, rv + wv * KK, ri + wv * KK);
     __syncthreads();
     if (wv == 0) {
       // lane l holds candidates l (and l + 64 when 8 kk > 64), better one first
@@ -502,7 +465,7 @@ __global__ __launch_bounds__(512) void hp_cand_topk_kernel(const int* __restrict
         v1 = rv[lane + 64];
         i1 = ri[lane + 64];
       }
-      if (i1 != INT64_MAX && (i0 == INT64_MAX || hp_better(v1, i1, v0, i0))) {
+      if (i1 != INT64_MAX && (i0 == INT64_MAX || better(v1, i1, v0, i0))) {
         const double tv = v0;
         const int64_t ti = i0;
         v0 = v1;
@@ -514,7 +477,7 @@ __global__ __launch_bounds__(512) void hp_cand_topk_kernel(const int* __restrict
       for (int r = 0; r < kk; ++r) {
         double bv = v0;
         int64_t bi = i0;
-        wave_best(bv, bi);
+        hp_wave_best(bv, bi);
         if (bi == INT64_MAX || bv != bv) bad = true;
         if (write && lane == 0) {
           out_idx[(int64_t)b * kk + r] = bi == INT64_MAX ? -1 : bi + idx_offset;
@@ -531,14 +494,14 @@ __global__ __launch_bounds__(512) void hp_cand_topk_kernel(const int* __restrict
     __syncthreads();
   };
   HP_STAMP(1);
-  reset();
+  L.reset();
   if (!flagged) {
     // two survivor groups per wave in flight (q0, q0 + 8); the next pair's
     // ids and heavy scores load while this pair's rows are gathered
     auto take = [&](const hp_f4& acc, int q, int64_t item, float h) {
       const int p = 16 * q + hs;
       const int64_t pid = __shfl(item, hs, kWave);
-      if (c < 4 && p < nb) insert(fused(h, hp_pick(acc, c)), pid);
+      if (c < 4 && p < nb) L.insert(fused(h, hp_pick(acc, c)), pid);
     };
     for (; 16 * q0 < nb; q0 += 16) {
       const int q1 = q0 + 8;
@@ -591,7 +554,7 @@ __global__ __launch_bounds__(512) void hp_cand_topk_kernel(const int* __restrict
   HpFrag uh[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) uh[ks].i = *reinterpret_cast<const int4*>(uhr + 16 * g + 64 * ks);
-  reset();
+  L.reset();
   for (int64_t q = wv; 16 * q < N; q += 8) {
     const int64_t item = 16 * q + c < N ? 16 * q + c : -1;
     HpFrag rh[KS], rl[KS];
@@ -601,7 +564,7 @@ __global__ __launch_bounds__(512) void hp_cand_topk_kernel(const int* __restrict
     const hp_f4 ah = hp_dot<DK>(rh, uh);
     const hp_f4 al = hp_dot<DK>(rl, uf);
     const int64_t p = 16 * q + hs;
-    if (c < 4 && p < N) insert(fused(hp_pick(ah, c), hp_pick(al, c)), p);
+    if (c < 4 && p < N) L.insert(fused(hp_pick(ah, c), hp_pick(al, c)), p);
   }
   merge(true);
 }
@@ -621,25 +584,20 @@ struct HpWs {
 
 static HpWs hp_layout(char* base, int B, int64_t N, int dk, int kk) {
   HpWs w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* r = base ? base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return r;
-  };
+  Carver c(base);
   const int G = hs_groups(N);
   // phase 1 (independent of top_k)
-  w.part = (float*)take((size_t)2 * G * 2 * B * 4);
-  w.argpos = (int*)take((size_t)2 * G * B * 4);
-  w.uop = (uint16_t*)take((size_t)2 * B * dk * 2);
+  w.part = (float*)c.take((size_t)2 * G * 2 * B * 4);
+  w.argpos = (int*)c.take((size_t)2 * G * B * 4);
+  w.uop = (uint16_t*)c.take((size_t)2 * B * dk * 2);
   // phase 2
-  w.theta = (float*)take((size_t)B * G * 4);
-  w.uflag = (int*)take((size_t)B * 4);
-  w.cv = (float*)take((size_t)B * kHpCap * 4);
-  w.ci = (int64_t*)take((size_t)B * kHpCap * 8);
-  w.cn = (int*)take((size_t)B * 4);
-  w.flag = (int*)take(4);
-  w.total = off + 256;
+  w.theta = (float*)c.take((size_t)B * G * 4);
+  w.uflag = (int*)c.take((size_t)B * 4);
+  w.cv = (float*)c.take((size_t)B * kHpCap * 4);
+  w.ci = (int64_t*)c.take((size_t)B * kHpCap * 8);
+  w.cn = (int*)c.take((size_t)B * 4);
+  w.flag = (int*)c.take(4);
+  w.total = c.total() + 256;
   return w;
 }
 

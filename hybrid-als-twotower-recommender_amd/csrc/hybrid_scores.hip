@@ -28,15 +28,12 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "hybrid_common.h"
 
 namespace hrec {
 
-typedef float hs_f4 __attribute__((ext_vector_type(4)));
+typedef hrec_f4 hs_f4;
 typedef __bf16 hs_bf8 __attribute__((ext_vector_type(8)));
-typedef int hs_rsrc __attribute__((ext_vector_type(4)));
-__device__ hs_f4 hs_sbuf_load(hs_rsrc rsrc, int vindex, int voffset, int soffset, int aux) __asm(
-    "llvm.amdgcn.struct.buffer.load.v4f32");
 
 union HsFrag {
   int4 i;
@@ -99,13 +96,6 @@ constexpr size_t kHsMaxLds = 160 * 1024;
 // the slot -> user map), 16-B aligned
 __host__ __device__ inline size_t hs_filter_head(int UB, int row_b) {
   return ((size_t)UB * row_b + (size_t)UB * 16 + 8 + 15) & ~(size_t)15;
-}
-
-// f32 -> bf16 bits, round to nearest even (NaN stays NaN): hrec_f32_to_bf16.
-__device__ __forceinline__ uint32_t hs_bf16(float v) {
-  const uint32_t x = __float_as_uint(v);
-  if ((x & 0x7fffffffu) > 0x7f800000u) return (x >> 16) | 0x40u;
-  return (x + 0x7fffu + ((x >> 16) & 1u)) >> 16;
 }
 
 // The value of lane ^ 16 / lane ^ 32 by the gfx950 row / half swaps
@@ -227,7 +217,7 @@ __global__ __launch_bounds__(kHsThreads) void hyb_scores_kernel(HybScoresArgs a)
   const int xq = c ^ g;
   // resource based at the block's first item (rows relative to i0: a
   // resource spans at most 4 GiB, rows_rsrc)
-  const hs_rsrc rsrc = rows_rsrc(a.items[model], i0, DK * 2, a.N);
+  const hrec_rsrc_t rsrc = rows_rsrc(a.items[model], i0, DK * 2, a.N);
   const int voff = 16 * g;
   auto rows_of = [&](int64_t jb, int (&vi)[NI]) {
 #pragma unroll
@@ -246,7 +236,7 @@ __global__ __launch_bounds__(kHsThreads) void hyb_scores_kernel(HybScoresArgs a)
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-      for (int t = 0; t < NI; ++t) it_f[ks][t].f = hs_sbuf_load(rsrc, vnext[t], voff + 64 * ks, 0, 0);
+      for (int t = 0; t < NI; ++t) it_f[ks][t].f = sbuf_load_f4(rsrc, vnext[t], voff + 64 * ks, 0, 0);
   }
 
   // HS_FILTER: the tile's live users (bound finite, or NaN = admit all) get
@@ -352,7 +342,7 @@ __global__ __launch_bounds__(kHsThreads) void hyb_scores_kernel(HybScoresArgs a)
         const int r = o / S::kChunks, q = o % S::kChunks;
         uint32_t h[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) h[e] = hs_bf16(f[j][e]);  // bf16(0.f) = 0
+        for (int e = 0; e < 8; ++e) h[e] = bf16_rne(f[j][e]);  // bf16(0.f) = 0
         const int4 v = {(int)(h[0] | (h[1] << 16)), (int)(h[2] | (h[3] << 16)), (int)(h[4] | (h[5] << 16)),
                         (int)(h[6] | (h[7] << 16))};
         *reinterpret_cast<int4*>(us + r * kRowB + 16 * (S::kSwz ? q ^ (r & 15) : q)) = v;
@@ -426,7 +416,7 @@ __global__ __launch_bounds__(kHsThreads) void hyb_scores_kernel(HybScoresArgs a)
                                                                   0, 0);
           if (last) {  // step ks of this slice is done: refill it with the next slice's
 #pragma unroll
-            for (int t = 0; t < NI; ++t) it_f[ks][t].f = hs_sbuf_load(rsrc, vnext[t], voff + 64 * ks, 0, 0);
+            for (int t = 0; t < NI; ++t) it_f[ks][t].f = sbuf_load_f4(rsrc, vnext[t], voff + 64 * ks, 0, 0);
           }
 #pragma unroll
           for (int u = 0; u < NU; ++u) {

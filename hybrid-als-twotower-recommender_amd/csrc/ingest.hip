@@ -876,7 +876,6 @@ inline unsigned grid_for(int64_t n) {
   return (unsigned)(b < 65536 ? (b > 0 ? b : 1) : 65536);
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 int bits_for(int64_t n_rows) {  // radix bits covering codes 0 .. n_rows-1
   int b = 1;
@@ -905,12 +904,12 @@ struct CsrWs {
     n_cnt = ((int64_t)1 << maxd) * n_tiles;
     n_chunks = ((n_tiles + kScanTiles - 1) / kScanTiles) << maxd;  // column sums
     ka = 0;
-    kb = ka + align256(4 * (size_t)nnz);
-    pa = kb + align256(4 * (size_t)nnz);
-    pb = pa + align256(8 * (size_t)nnz);
-    cnt = pb + align256(8 * (size_t)nnz);
-    sums = cnt + align256(4 * (size_t)n_cnt);
-    total = sums + align256(4 * (size_t)n_chunks);
+    kb = ka + al256(4 * (size_t)nnz);
+    pa = kb + al256(4 * (size_t)nnz);
+    pb = pa + al256(8 * (size_t)nnz);
+    cnt = pb + al256(8 * (size_t)nnz);
+    sums = cnt + al256(4 * (size_t)n_cnt);
+    total = sums + al256(4 * (size_t)n_chunks);
   }
 };
 
@@ -934,17 +933,17 @@ struct EncodeWs {
   explicit EncodeWs(int64_t n) {
     // the in-tree sort's workspace (its sorted keys stay there), the sort's
     // value output, then the scan's workspace (must not overlap the keys)
-    size_t tmp = csr_ws_max(n) + align256(4 * (size_t)n) + align256(scan_ws_bytes(n));
-    const size_t wide = csr_ws_max(n) + 4 * align256(4 * (size_t)n);
+    size_t tmp = csr_ws_max(n) + al256(4 * (size_t)n) + al256(scan_ws_bytes(n));
+    const size_t wide = csr_ws_max(n) + 4 * al256(4 * (size_t)n);
     if (wide > tmp) tmp = wide;
     if (scan_ws_bytes(n) > tmp) tmp = scan_ws_bytes(n);
     keys = 0;
-    pos = keys + align256(8 * (size_t)n);
-    pos2 = pos + align256(4 * (size_t)n);
-    flag = pos2 + align256(4 * (size_t)n);
-    incl = flag + align256(4 * (size_t)n);
-    temp = incl + align256(4 * (size_t)n);
-    total = temp + align256(tmp);
+    pos = keys + al256(8 * (size_t)n);
+    pos2 = pos + al256(4 * (size_t)n);
+    flag = pos2 + al256(4 * (size_t)n);
+    incl = flag + al256(4 * (size_t)n);
+    temp = incl + al256(4 * (size_t)n);
+    total = temp + al256(tmp);
   }
 };
 
@@ -1113,7 +1112,7 @@ extern "C" int hrec_encode_ids_ex(const int64_t* ids, int64_t n, int64_t id_lo, 
     if (rc) return rc;
     hipLaunchKernelGGL(distinct_flags_kernel<int32_t>, dim3(g), dim3(256), 0, s, k32s, n, flag);
     // the sorted keys live at the start of temp: the scan works past them
-    void* scan_ws = static_cast<char*>(temp) + csr_ws_max(n) + align256(4 * (size_t)n);
+    void* scan_ws = static_cast<char*>(temp) + csr_ws_max(n) + al256(4 * (size_t)n);
     rc = scan_run<int32_t>(flag, incl, n, false, scan_ws, s);
     if (rc) return rc;
     hipLaunchKernelGGL(scatter_codes_kernel<int32_t>, dim3(g), dim3(256), 0, s, k32s, id_lo, pos2, flag, incl, n,
@@ -1124,7 +1123,7 @@ extern "C" int hrec_encode_ids_ex(const int64_t* ids, int64_t n, int64_t id_lo, 
     // sort by the low word carrying (high word, position), then by the high
     // word carrying (low word, position) — LSD over 64 bits
     char* t4 = static_cast<char*>(temp) + csr_ws_max(n);
-    const size_t c4 = align256(4 * (size_t)n);
+    const size_t c4 = al256(4 * (size_t)n);
     uint32_t* A = reinterpret_cast<uint32_t*>(t4);
     uint32_t* Bw = reinterpret_cast<uint32_t*>(t4 + c4);
     uint32_t* C = reinterpret_cast<uint32_t*>(t4 + 2 * c4);
@@ -1171,7 +1170,7 @@ extern "C" int hrec_minmax_i64(const int64_t* x, int64_t n, int64_t* out, void* 
 
 extern "C" size_t hrec_coo_to_csr_workspace_bytes(int64_t nnz, int64_t n_rows) {
   if (nnz <= 0 || nnz >= 0x7fffffffll || n_rows <= 0 || n_rows >= 0x7fffffffll) return 0;
-  return CsrWs(nnz, bits_for(n_rows)).total + align256(8 * (size_t)((n_rows + 1 + kMinTile - 1) / kMinTile));
+  return CsrWs(nnz, bits_for(n_rows)).total + al256(8 * (size_t)((n_rows + 1 + kMinTile - 1) / kMinTile));
 }
 
 extern "C" int hrec_coo_to_csr(const int32_t* rows, const int32_t* cols, const float* vals, int64_t nnz,

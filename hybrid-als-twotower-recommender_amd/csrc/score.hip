@@ -1,9 +1,7 @@
-// K2: ALS scoring (Spark ALSModel.transform, JVM-exact f32 chain),
-// generic stable top-k (the reference's sorted(..., reverse=True)[:k]),
-// K9: hybrid min-max fusion (src/hybrid_system.py:57-75) + top-k (:108).
-#include <float.h>
-
-#include "common.h"
+// K2: ALS scoring (Spark ALSModel.transform, JVM-exact f32 chain) and its
+// fused top-k; K2p: the pruned ALS top-k. The generic stable top-k is
+// csrc/topk.hip, the hybrid fusion (K9) csrc/fuse.hip.
+#include "hybrid_common.h"
 
 namespace hrec {
 
@@ -67,10 +65,8 @@ __global__ __launch_bounds__(256) void als_score_kernel(const float* __restrict_
 // every product and sum is rounded exactly like the JVM loop).
 // FILTER: instead of writing the scores, append (score, item) pairs with
 // score >= thr[b] to a per-user candidate list (wave-aggregated atomics).
-typedef float f2v __attribute__((ext_vector_type(2)));
-typedef int i4v __attribute__((ext_vector_type(4)));
-// buffer_load_dwordx2 ... offen (raw: base + voffset, range-checked)
-__device__ f2v rbuf_load_f2(i4v rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v2f32");
+typedef hrec_f2 f2v;
+typedef hrec_rsrc_t i4v;
 
 template <int UB, bool FILTER>
 __global__ __launch_bounds__(256) void als_score_fast_kernel(
@@ -220,186 +216,6 @@ __global__ __launch_bounds__(256) void als_score_fast_kernel(
     }
   }
 }
-
-// ----------------------------------------------------------------- top-k
-// Order: larger value first; equal values -> smaller index first (a stable
-// descending sort of the input order). NaN sorts last.
-template <typename T>
-__device__ __forceinline__ bool better(T va, int64_t ia, T vb, int64_t ib) {
-  const bool na = va != va, nb = vb != vb;
-  if (na || nb) return !na && nb ? true : (na && nb ? ia < ib : false);
-  return va > vb || (va == vb && ia < ib);
-}
-
-template <typename T>
-struct KV {
-  T v;
-  int64_t i;
-};
-
-template <typename T>
-__device__ __forceinline__ KV<T> wave_best(KV<T> x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    KV<T> y;
-    y.v = __shfl_xor(x.v, off, kWave);
-    y.i = __shfl_xor(x.i, off, kWave);
-    // lanes without a candidate carry i = INT64_MAX and lose every comparison
-    const bool take = (x.i == INT64_MAX) ? (y.i != INT64_MAX)
-                                         : (y.i != INT64_MAX && better(y.v, y.i, x.v, x.i));
-    if (take) x = y;
-  }
-  return x;
-}
-
-constexpr int kTopkBlock = 256;
-constexpr int kTopkPer = 16;  // elements per thread per segment
-constexpr int kTopkSeg = kTopkBlock * kTopkPer;
-constexpr int kTopkSelectMax = 1024;  // larger top_k: the sort path (csrc/sort_topk.hip)
-
-// Stage 1: rows x segments; each block selects the top `kk` of its segment
-// of one row by kk rounds of block arg-best over elements held in registers.
-// `src_idx` (optional) maps positions to original indices (stage 2 input).
-template <typename T>
-__global__ __launch_bounds__(kTopkBlock) void topk_segment_kernel(const T* __restrict__ vals,
-                                                                  const int64_t* __restrict__ src_idx,
-                                                                  const int* __restrict__ row_n,
-                                                                  int64_t n, int64_t row_stride, int kk,
-                                                                  T* __restrict__ out_v,
-                                                                  int64_t* __restrict__ out_i,
-                                                                  int64_t out_row_stride,
-                                                                  const int* __restrict__ gate) {
-  __shared__ KV<T> red[kTopkBlock / 64];
-  __shared__ int64_t win;
-  if (gate && *gate == 0) return;
-  const int64_t row = blockIdx.y;
-  const int64_t seg0 = (int64_t)blockIdx.x * kTopkSeg;
-  const T* __restrict__ rv = vals + row * row_stride;
-  const int64_t* __restrict__ ri = src_idx ? src_idx + row * row_stride : nullptr;
-  if (row_n) {
-    const int64_t rn = row_n[row];
-    n = rn < n ? rn : n;
-  }
-  T v[kTopkPer];
-  int64_t id[kTopkPer];
-#pragma unroll
-  for (int e = 0; e < kTopkPer; ++e) {
-    const int64_t p = seg0 + (int64_t)e * kTopkBlock + threadIdx.x;
-    if (p < n) {
-      v[e] = rv[p];
-      id[e] = ri ? ri[p] : p;
-    } else {
-      v[e] = 0;
-      id[e] = -1;
-    }
-  }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int r = 0; r < kk; ++r) {
-    KV<T> best{(T)0, -1};
-#pragma unroll
-    for (int e = 0; e < kTopkPer; ++e) {
-      if (id[e] >= 0 && (best.i < 0 || better(v[e], id[e], best.v, best.i))) best = KV<T>{v[e], id[e]};
-    }
-    if (best.i < 0) best.i = INT64_MAX;
-    KV<T> wb = wave_best(best);
-    if (lane == 0) red[w] = wb;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      KV<T> b = red[0];
-      for (int q = 1; q < kTopkBlock / 64; ++q) {
-        if (red[q].i == INT64_MAX) continue;
-        if (b.i == INT64_MAX || better(red[q].v, red[q].i, b.v, b.i)) b = red[q];
-      }
-      const int64_t o = row * out_row_stride + (int64_t)blockIdx.x * kk + r;
-      out_v[o] = b.v;
-      out_i[o] = b.i == INT64_MAX ? -1 : b.i;
-      win = b.i;
-    }
-    __syncthreads();
-    const int64_t wi = win;
-#pragma unroll
-    for (int e = 0; e < kTopkPer; ++e)
-      if (id[e] == wi) id[e] = -1;
-    __syncthreads();
-  }
-}
-
-// Small top-k (kk <= 16) of rows of at most kTopkWaveMax elements: one wave
-// per row. Each lane streams its elements (p = lane, lane + 64, ...) through a
-// sorted register list of its KK best (a compare-exchange chain, no
-// branches), then kk rounds of wave arg-best over the list heads, the winner
-// popping its head. Same order, same output as topk_segment_kernel, without
-// its block barriers.
-constexpr int kTopkWaveMax = 8192;
-
-template <typename T, int KK>
-__global__ __launch_bounds__(256) void topk_wave_kernel(const T* __restrict__ vals,
-                                                        const int64_t* __restrict__ src_idx,
-                                                        const int* __restrict__ row_n, int64_t n_rows, int64_t n,
-                                                        int64_t row_stride, int kk, T* __restrict__ out_v,
-                                                        int64_t* __restrict__ out_i, int64_t out_row_stride,
-                                                        const int* __restrict__ gate) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= n_rows || (gate && *gate == 0)) return;  // wave-uniform
-  if (row_n) {
-    const int64_t rn = row_n[row];
-    n = rn < n ? rn : n;
-  }
-  const T* __restrict__ rv = vals + row * row_stride;
-  const int64_t* __restrict__ ri = src_idx ? src_idx + row * row_stride : nullptr;
-  T lv[KK];
-  int64_t li[KK];
-#pragma unroll
-  for (int j = 0; j < KK; ++j) {
-    lv[j] = (T)0;
-    li[j] = INT64_MAX;  // empty slot: loses to every element
-  }
-  constexpr int B = 8;  // loads in flight per lane before the first insertion
-  for (int64_t p0 = lane; p0 < n; p0 += 64 * B) {
-    T bv[B];
-    int64_t bi[B];
-#pragma unroll
-    for (int e = 0; e < B; ++e) {
-      const int64_t p = p0 + 64 * e;
-      const bool in = p < n;
-      bv[e] = in ? rv[p] : (T)0;
-      bi[e] = in ? (ri ? ri[p] : p) : -1;
-    }
-#pragma unroll
-    for (int e = 0; e < B; ++e) {
-      T xv = bv[e];
-      int64_t xi = bi[e] < 0 ? INT64_MAX : bi[e];  // absent: an empty slot, inserts as a no-op
-#pragma unroll
-      for (int j = 0; j < KK; ++j) {
-        const bool sw = xi != INT64_MAX && (li[j] == INT64_MAX || better(xv, xi, lv[j], li[j]));
-        const T tv = lv[j];
-        const int64_t ti = li[j];
-        lv[j] = sw ? xv : tv;
-        li[j] = sw ? xi : ti;
-        xv = sw ? tv : xv;
-        xi = sw ? ti : xi;
-      }
-    }
-  }
-  for (int r = 0; r < kk; ++r) {
-    const KV<T> w = wave_best(KV<T>{lv[0], li[0]});
-    if (lane == 0) {
-      const int64_t o = row * out_row_stride + r;
-      out_v[o] = w.i == INT64_MAX ? (T)0 : w.v;
-      out_i[o] = w.i == INT64_MAX ? -1 : w.i;
-    }
-    if (w.i != INT64_MAX && li[0] == w.i) {  // the (unique) owner pops its head
-#pragma unroll
-      for (int j = 0; j + 1 < KK; ++j) {
-        lv[j] = lv[j + 1];
-        li[j] = li[j + 1];
-      }
-      li[KK - 1] = INT64_MAX;
-    }
-  }
-}
-
 // Survivor threshold from a sample row (one wave per row, kk <= 64): the
 // kk-th largest of the 64 lane maxima (lane l: elements l, l + 64, ...). Those
 // are kk distinct sample elements, so the value bounds the row's kk-th best
@@ -435,660 +251,9 @@ __global__ __launch_bounds__(256) void sample_threshold_kernel(const float* __re
   }
 }
 
-// ---------------------------------------------------------------- fusion
-// sklearn MinMaxScaler.fit_transform (container sklearn _data.py:518-522,
-// 261-262): scale = 1/range (range < 10*eps -> 1), min_ = 0 - min*scale,
-// y = x*scale + min_ ; two roundings each, in the input dtype.
-__global__ __launch_bounds__(256) void minmax_partial_kernel(const double* __restrict__ als,
-                                                             const void* __restrict__ tt, int tt_f32,
-                                                             int64_t n, double* __restrict__ part) {
-  __shared__ double sh[4][256];
-  double amin = DBL_MAX, amax = -DBL_MAX, tmin = DBL_MAX, tmax = -DBL_MAX;
-  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (int64_t)gridDim.x * 256) {
-    const double a = als[p];
-    const double t = tt_f32 ? (double)((const float*)tt)[p] : ((const double*)tt)[p];
-    amin = fmin(amin, a);
-    amax = fmax(amax, a);
-    tmin = fmin(tmin, t);
-    tmax = fmax(tmax, t);
-  }
-  sh[0][threadIdx.x] = amin;
-  sh[1][threadIdx.x] = amax;
-  sh[2][threadIdx.x] = tmin;
-  sh[3][threadIdx.x] = tmax;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) {
-      sh[0][threadIdx.x] = fmin(sh[0][threadIdx.x], sh[0][threadIdx.x + s]);
-      sh[1][threadIdx.x] = fmax(sh[1][threadIdx.x], sh[1][threadIdx.x + s]);
-      sh[2][threadIdx.x] = fmin(sh[2][threadIdx.x], sh[2][threadIdx.x + s]);
-      sh[3][threadIdx.x] = fmax(sh[3][threadIdx.x], sh[3][threadIdx.x + s]);
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x < 4) part[blockIdx.x * 4 + threadIdx.x] = sh[threadIdx.x][0];
-}
-
-// coef = {als_scale, als_min_, tt_scale, tt_min_} as doubles (the tt pair is
-// the exact f32 values widened when tt_f32).
-__global__ void minmax_final_kernel(const double* __restrict__ part, int nparts, int tt_f32,
-                                    double* __restrict__ coef, double* __restrict__ out_minmax) {
-  if (threadIdx.x != 0) return;
-  double amin = DBL_MAX, amax = -DBL_MAX, tmin = DBL_MAX, tmax = -DBL_MAX;
-  for (int q = 0; q < nparts; ++q) {
-    amin = fmin(amin, part[4 * q + 0]);
-    amax = fmax(amax, part[4 * q + 1]);
-    tmin = fmin(tmin, part[4 * q + 2]);
-    tmax = fmax(tmax, part[4 * q + 3]);
-  }
-  if (out_minmax) {  // the fitted MinMaxScalers' data_min_ / data_max_ (src/hybrid_system.py:66-67)
-    out_minmax[0] = amin;
-    out_minmax[1] = amax;
-    out_minmax[2] = tmin;
-    out_minmax[3] = tmax;
-  }
-  double arange = amax - amin;
-  if (arange < 10.0 * DBL_EPSILON) arange = 1.0;
-  const double ascale = 1.0 / arange;
-  coef[0] = ascale;
-  coef[1] = 0.0 - amin * ascale;
-  if (tt_f32) {
-    const float fmin_ = (float)tmin, fmax_ = (float)tmax;
-    float frange = fmax_ - fmin_;
-    if (frange < 10.0f * FLT_EPSILON) frange = 1.0f;
-    const float fscale = 1.0f / frange;
-    const float fmin2 = 0.0f - fmin_ * fscale;
-    coef[2] = (double)fscale;
-    coef[3] = (double)fmin2;
-  } else {
-    double trange = tmax - tmin;
-    if (trange < 10.0 * DBL_EPSILON) trange = 1.0;
-    const double tscale = 1.0 / trange;
-    coef[2] = tscale;
-    coef[3] = 0.0 - tmin * tscale;
-  }
-}
-
-// fused = w0*als_norm + w1*tt_norm, f64 (numpy 1.21 scalar promotion: the
-// f32 tt_norm element is widened before the multiply — SURVEY App. A.3).
-__global__ __launch_bounds__(256) void fuse_kernel(const double* __restrict__ als, const void* __restrict__ tt,
-                                                   int tt_f32, int64_t n, const double* __restrict__ coef,
-                                                   double w0, double w1, double* __restrict__ fused) {
-#pragma clang fp contract(off)
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= n) return;
-  const double an = als[p] * coef[0] + coef[1];
-  double tn;
-  if (tt_f32) {
-    const float x = ((const float*)tt)[p];
-    const float y = x * (float)coef[2] + (float)coef[3];
-    tn = (double)y;
-  } else {
-    tn = ((const double*)tt)[p] * coef[2] + coef[3];
-  }
-  fused[p] = w0 * an + w1 * tn;
-}
-
-
-// ------------------------------------------------------- cold-start cosine
-// ALSModel._find_similar_items (src/als_model.py:93-104): sklearn
-// cosine_similarity([target], [other]) = dot(a/|a|, b/|b|) with a zero norm
-// replaced by 1. One thread per (query, item); the query's own row -> -inf so
-// it never ranks (the reference skips it).
-__global__ __launch_bounds__(256) void cosine_kernel(const double* __restrict__ feats, int64_t n_items, int dim,
-                                                     const int64_t* __restrict__ qrows, double* __restrict__ out) {
-#pragma clang fp contract(off)
-  const int64_t q = blockIdx.y;
-  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= n_items) return;
-  const int64_t qr = qrows[q];
-  double* o = out + q * n_items;
-  if (j == qr) {
-    o[j] = -__builtin_inf();
-    return;
-  }
-  const double* a = feats + qr * dim;
-  const double* b = feats + j * dim;
-  double na = 0.0, nb = 0.0;
-  for (int c = 0; c < dim; ++c) {
-    na = na + a[c] * a[c];
-    nb = nb + b[c] * b[c];
-  }
-  na = sqrt(na);
-  nb = sqrt(nb);
-  if (na == 0.0) na = 1.0;
-  if (nb == 0.0) nb = 1.0;
-  double dot = 0.0;
-  for (int c = 0; c < dim; ++c) dot = dot + (a[c] / na) * (b[c] / nb);
-  o[j] = dot;
-}
-
-
-// --------------------------------------------- batched fusion (K9, rows)
-// Per-row min / max of an f32 score matrix (NaN ignored, like np.nanmin):
-// out[r] = min, out[n_rows + r] = max (two contiguous halves, so the
-// cross-shard reduction is one MIN and one MAX all-reduce). One block per row.
-// Per-row min / max (NaN ignored, like fminf). One 1024-thread block per
-// row streams it with 16-B loads (rows 16-B aligned) — HBM-bound.
-__global__ __launch_bounds__(1024) void rows_minmax_kernel(const float* __restrict__ x, int64_t n, int64_t ld,
-                                                           int vec4, float* __restrict__ out) {
-  __shared__ float smin[16], smax[16];
-  const float* r = x + (int64_t)blockIdx.x * ld;
-  float lo = __builtin_inff(), hi = -__builtin_inff();
-  int64_t j0 = 0;
-  if (vec4) {
-    const int64_t n4 = n >> 2;
-    const float4* r4 = reinterpret_cast<const float4*>(r);
-    for (int64_t j = threadIdx.x; j < n4; j += 1024) {
-      const float4 v = r4[j];
-      lo = fminf(fminf(lo, v.x), fminf(v.y, fminf(v.z, v.w)));
-      hi = fmaxf(fmaxf(hi, v.x), fmaxf(v.y, fmaxf(v.z, v.w)));
-    }
-    j0 = n4 << 2;
-  }
-  for (int64_t j = j0 + threadIdx.x; j < n; j += 1024) {
-    lo = fminf(lo, r[j]);
-    hi = fmaxf(hi, r[j]);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, off, kWave));
-    hi = fmaxf(hi, __shfl_xor(hi, off, kWave));
-  }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    smin[w] = lo;
-    smax[w] = hi;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int q = 1; q < 16; ++q) {
-      lo = fminf(lo, smin[q]);
-      hi = fmaxf(hi, smax[q]);
-    }
-    out[blockIdx.x] = lo;              // mins  [n_rows]
-    out[gridDim.x + blockIdx.x] = hi;  // maxes [n_rows]
-  }
-}
-
-// fused[r][j] = w0 * minmax64(als[r][j]) + w1 * (double)minmax32(tt[r][j]),
-// with each row's min/max given (global over every shard of the row): the
-// ALS side is min-max scaled in f64 (the reference's als scores are Python
-// floats), the two-tower side in f32 (np.float32 scores), then f64 fusion
-// with numpy 1.21's scalar promotion — hrec_fuse_topk per row.
-__global__ __launch_bounds__(256) void fuse_rows_kernel(const float* __restrict__ als, const float* __restrict__ tt,
-                                                        int64_t n, int64_t ld, const float* __restrict__ als_mm,
-                                                        const float* __restrict__ tt_mm, double w0, double w1,
-                                                        double* __restrict__ fused) {
-#pragma clang fp contract(off)
-  const int64_t r = blockIdx.y;
-  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
-  const int64_t R = gridDim.y;  // min/max layout: [2][n_rows]
-  const double amin = (double)als_mm[r], amax = (double)als_mm[R + r];
-  double arange = amax - amin;
-  if (arange < 10.0 * DBL_EPSILON) arange = 1.0;
-  const double ascale = 1.0 / arange;
-  const double amin_ = 0.0 - amin * ascale;
-  const float tmin = tt_mm[r], tmax = tt_mm[R + r];
-  float trange = tmax - tmin;
-  if (trange < 10.0f * FLT_EPSILON) trange = 1.0f;
-  const float tscale = 1.0f / trange;
-  const float tmin_ = 0.0f - tmin * tscale;
-  const double an = (double)als[r * ld + j] * ascale + amin_;
-  const float tn = tt[r * ld + j] * tscale + tmin_;
-  fused[r * n + j] = w0 * an + w1 * (double)tn;
-}
-
-// fuse_rows_kernel's arithmetic + a stable top-kk (kk <= kFuseK) of each
-// segment of kFuseSeg items, without materialising the fused row. One WAVE
-// per segment (no block barriers). Each fused f64 becomes an order-preserving
-// u64 key (NaN lowest, as `better` ranks it), so every comparison is one
-// integer compare; lane l holds items seg0 + 64 e + l (ascending e =
-// ascending index, so a strict '>' keeps the earlier item on ties).
-//   1. t = the kk-th best of the 64 lane maxima (kk rounds of a wave
-//      arg-best; the winning LANE drops out) — a lower bound of the
-//      segment's kk-th best, since those kk maxima are kk distinct items;
-//   2. items not worse than t are the candidates (ballot-compacted into LDS;
-//      typically ~kk of them; more than 64 — heavy ties — falls back to
-//      exact rescans);
-//   3. kk rounds of a wave arg-best over the candidates (key desc, index asc)
-//      -> [row][seg*kk] (value, index).
-constexpr int kFuseK = 8;
-#ifndef HREC_FUSE_PER
-#define HREC_FUSE_PER 16
-#endif
-constexpr int kFusePer = HREC_FUSE_PER;  // items per lane per segment
-constexpr int kFuseSeg = 64 * kFusePer;
-#ifndef HREC_FUSE_RANK
-#define HREC_FUSE_RANK 1  // selections by rank among <= 64 entries (LDS broadcast reads) instead of arg-best rounds
-#endif
-constexpr bool kFuseRank = HREC_FUSE_RANK;
-
-__device__ __forceinline__ uint64_t order_key(double v) {
-  if (v != v) return 0;  // NaN ranks below every number
-  const uint64_t b = (uint64_t)__double_as_longlong(v + 0.0);  // -0 -> +0 (they compare equal)
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_value(uint64_t k) {
-  if (k == 0) return __builtin_nan("");
-  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-
-struct KI {
-  uint64_t k;
-  int64_t i;  // INT64_MAX: no item
-};
-__device__ __forceinline__ bool ki_better(const KI& a, const KI& b) {  // a ranks before b
-  return a.i != INT64_MAX && (b.i == INT64_MAX || a.k > b.k || (a.k == b.k && a.i < b.i));
-}
-__device__ __forceinline__ KI wave_best_ki(KI x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    KI y;
-    y.k = ((uint64_t)(uint32_t)__shfl_xor((int)(x.k >> 32), off, kWave) << 32) |
-          (uint32_t)__shfl_xor((int)x.k, off, kWave);
-    y.i = __shfl_xor(x.i, off, kWave);
-    if (ki_better(y, x)) x = y;
-  }
-  return x;
-}
-
-// One segment (seg of row r, R rows) on one wave; ck / ce: the wave's 128
-// LDS slots ([64, 128): scratch of non-candidates).
-template <int KK>
-__device__ __forceinline__ void fuse_segment_one(
-    int64_t seg, int64_t r, int64_t R, const float* __restrict__ als, const float* __restrict__ tt, int64_t n,
-    int64_t ld, int64_t segs, const float* __restrict__ als_mm, const float* __restrict__ tt_mm, double w0, double w1,
-    double* __restrict__ cand_v, int64_t* __restrict__ cand_i, uint64_t* __restrict__ ck, int* __restrict__ ce) {
-#pragma clang fp contract(off)
-  const int lane = threadIdx.x & 63;
-  const double amin = (double)als_mm[r], amax = (double)als_mm[R + r];
-  double arange = amax - amin;
-  if (arange < 10.0 * DBL_EPSILON) arange = 1.0;
-  const double ascale = 1.0 / arange;
-  const double amin_ = 0.0 - amin * ascale;
-  const float tmin = tt_mm[r], tmax = tt_mm[R + r];
-  float trange = tmax - tmin;
-  if (trange < 10.0f * FLT_EPSILON) trange = 1.0f;
-  const float tscale = 1.0f / trange;
-  const float tmin_ = 0.0f - tmin * tscale;
-  const int64_t seg0 = seg * kFuseSeg;
-  const float* __restrict__ ar = als + r * ld + seg0 + lane;
-  const float* __restrict__ tr = tt + r * ld + seg0 + lane;
-  const int nvalid = (int)((n - seg0) < kFuseSeg ? (n - seg0) : kFuseSeg);  // items of this segment
-  uint64_t key[kFusePer];
-  float av[kFusePer], tv[kFusePer];
-  if (nvalid == kFuseSeg) {  // full segment: unconditional loads
-#pragma unroll
-    for (int e = 0; e < kFusePer; ++e) {
-      av[e] = ar[e * 64];
-      tv[e] = tr[e * 64];
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < kFusePer; ++e) {
-      const int off = e * 64 + lane < nvalid ? e * 64 : 0;  // the lane's first item is in range
-      av[e] = ar[off];
-      tv[e] = tr[off];
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < kFusePer; ++e) {
-    const double an = (double)av[e] * ascale + amin_;
-    const float tn = tv[e] * tscale + tmin_;
-    const uint64_t kv = order_key(w0 * an + w1 * (double)tn);
-    key[e] = e * 64 + lane < nvalid ? kv : 0;
-  }
-  const int nmine = nvalid > lane ? (nvalid - lane + 63) >> 6 : 0;  // live items of this lane
-  // 1. lane arg-best (strict '>' in ascending e keeps the earliest of equals)
-  uint64_t bk = key[0];
-  int be = 0;
-#pragma unroll
-  for (int e = 1; e < kFusePer; ++e) {
-    const bool gt = key[e] > bk;
-    bk = gt ? key[e] : bk;
-    be = gt ? e : be;
-  }
-  KI mine{bk, nmine > 0 ? seg0 + (int64_t)be * 64 + lane : INT64_MAX};
-  KI t{0, INT64_MAX};
-  if constexpr (kFuseRank) {
-    // t = the min(kk, live lanes)-th best lane maximum, by each lane's RANK
-    // among the 64 maxima (one pass of broadcast LDS reads, no dependent
-    // cross-lane rounds); in-segment positions order equal keys
-    const int mpos = nmine > 0 ? be * 64 + lane : -1;
-    ck[64 + lane] = bk;
-    ce[64 + lane] = mpos;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    int rank = 0;
-#pragma unroll 8
-    for (int q = 0; q < 64; ++q) {
-      const uint64_t ok = ck[64 + q];
-      const int op = ce[64 + q];
-      rank += (op >= 0 && (mpos < 0 || ok > bk || (ok == bk && op < mpos))) ? 1 : 0;
-    }
-    const int nvl = __popcll(__ballot(mpos >= 0));
-    const int target = (nvl < KK ? nvl : KK) - 1;
-    const uint64_t hit = __ballot(mpos >= 0 && rank == target);
-    if (hit) {
-      const int src = __builtin_ctzll(hit);
-      t.k = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(bk >> 32), src) << 32) |
-            (uint32_t)__builtin_amdgcn_readlane((int)bk, src);
-      t.i = seg0 + __builtin_amdgcn_readlane(mpos, src);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  } else {
-    for (int q = 0; q < KK; ++q) {
-      const KI w = wave_best_ki(mine);
-      if (w.i == INT64_MAX) break;
-      t = w;
-      if (w.i == mine.i) mine.i = INT64_MAX;
-    }
-  }
-  // 2. candidates: items not worse than t (no t: fewer than kk items, take all)
-  int nc = 0;
-  bool overflow = false;
-#pragma unroll
-  for (int e = 0; e < kFusePer; ++e) {
-    const int64_t j = seg0 + (int64_t)e * 64 + lane;
-    const bool live = e < nmine;
-    const bool c = live && (t.i == INT64_MAX || key[e] > t.k || (key[e] == t.k && j <= t.i));
-    const uint64_t m = __ballot(c);
-    const int cnt = __popcll(m);
-    if (nc + cnt > 64) {
-      overflow = true;
-      break;
-    }
-    const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    const int slot = c ? nc + below : 64 + lane;  // branch-free append
-    ck[slot] = key[e];
-    ce[slot] = e * 64 + lane;
-    nc += cnt;
-  }
-  const int64_t obase = r * segs * KK + seg * KK;
-  if (!overflow) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if constexpr (kFuseRank) {
-      // each candidate's rank among the nc candidates = its output slot
-      const uint64_t mk = lane < nc ? ck[lane] : 0;
-      const int mp = lane < nc ? ce[lane] : 0;
-      int rank = 0;
-      for (int q = 0; q < nc; ++q) {
-        const uint64_t ok = ck[q];
-        const int op = ce[q];
-        rank += (ok > mk || (ok == mk && op < mp)) ? 1 : 0;
-      }
-      if (lane < nc && rank < KK) {
-        cand_v[obase + rank] = key_value(mk);
-        cand_i[obase + rank] = seg0 + mp;
-      }
-      if (lane >= nc && lane < KK) {  // fewer candidates than kk: empty slots
-        cand_v[obase + lane] = key_value(0);
-        cand_i[obase + lane] = -1;
-      }
-      return;
-    }
-    KI c{0, INT64_MAX};
-    if (lane < nc) c = KI{ck[lane], seg0 + ce[lane]};
-    for (int q = 0; q < KK; ++q) {
-      const KI w = wave_best_ki(c);
-      if (lane == 0) {
-        cand_v[obase + q] = key_value(w.k);
-        cand_i[obase + q] = w.i == INT64_MAX ? -1 : w.i;
-      }
-      if (w.i == c.i) c.i = INT64_MAX;
-    }
-    return;
-  }
-  // heavy ties: exact selection by rescans (the winning lane drops its item)
-  uint32_t live_mask = nmine >= 32 ? 0xffffffffu : ((1u << nmine) - 1u);  // kFusePer <= 32
-  auto rescan = [&](KI& m2) {
-    m2 = KI{0, INT64_MAX};
-#pragma unroll
-    for (int e = 0; e < kFusePer; ++e) {
-      const KI x{key[e], seg0 + (int64_t)e * 64 + lane};
-      if (((live_mask >> e) & 1u) && ki_better(x, m2)) m2 = x;
-    }
-  };
-  KI m2;
-  rescan(m2);
-  for (int q = 0; q < KK; ++q) {
-    const KI w = wave_best_ki(m2);
-    if (lane == 0) {
-      cand_v[obase + q] = key_value(w.k);
-      cand_i[obase + q] = w.i == INT64_MAX ? -1 : w.i;
-    }
-    if (w.i != INT64_MAX && w.i == m2.i) {
-      live_mask &= ~(1u << (int)((w.i - seg0) >> 6));
-      rescan(m2);
-    }
-  }
-}
-
-template <int KK>
-__global__ __launch_bounds__(256) void fuse_segment_topk_kernel(
-    const float* __restrict__ als, const float* __restrict__ tt, int64_t n, int64_t ld, int64_t segs,
-    const float* __restrict__ als_mm, const float* __restrict__ tt_mm, double w0, double w1,
-    double* __restrict__ cand_v, int64_t* __restrict__ cand_i, const int* __restrict__ gate, int* __restrict__ clear) {
-  // clear (the sample launch): reset the filter's overflow flag for this call
-  if (clear && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *clear = 0;
-  if (gate && *gate == 0) return;
-  __shared__ uint64_t ck_sh[4][128];
-  __shared__ int ce_sh[4][128];
-  const int wv = threadIdx.x >> 6;
-  // block-stride over the row's segment groups (a gated launch uses one block
-  // per row, so skipping it costs a small grid)
-  for (int64_t sb = blockIdx.x; sb * 4 < segs; sb += gridDim.x) {
-    const int64_t seg = sb * 4 + wv;
-    if (seg < segs)
-      fuse_segment_one<KK>(seg, blockIdx.y, gridDim.y, als, tt, n, ld, segs, als_mm, tt_mm, w0, w1, cand_v, cand_i,
-                           ck_sh[wv], ce_sh[wv]);
-  }
-}
-
-// Threshold filter for the batched fusion top-k (kk <= kFuseK): the same
-// fused f64 keys as fuse_segment_topk_kernel, one wave per segment, but each
-// row first takes a threshold key tk = the best of its sample segments'
-// kk-th best keys (fuse_segment_topk_kernel over the row's first G segments
-// -> samp). Those are kk distinct items of the row, so at least kk items have
-// key >= tk and the row's top kk all do. Per item: the fusion, one compare
-// and a ballot; the (few) items with key >= tk are compacted into LDS and
-// the segment's stable top-kk among them is taken by rank (each candidate
-// counts the better ones, a handful of broadcast LDS reads) -> [row][seg*kk]
-// like fuse_segment_topk_kernel, and the same merge follows. A segment with
-// more than kFuseSlots candidates (heavy ties, or a row whose best items
-// cluster) raises *overflow, which gates the exact segment path on the
-// device (the sample launch of fuse_segment_topk_kernel resets it first).
-constexpr int kFuseSlots = 64;
-__global__ __launch_bounds__(256) void fuse_filter_kernel(
-    const float* __restrict__ als, const float* __restrict__ tt, int64_t n, int64_t ld, int64_t segs,
-    const float* __restrict__ als_mm, const float* __restrict__ tt_mm, double w0, double w1,
-    const double* __restrict__ samp, int G, int kk, double* __restrict__ cand_v, int64_t* __restrict__ cand_i,
-    int* __restrict__ overflow) {
-#pragma clang fp contract(off)
-  __shared__ uint64_t ck_sh[4][kFuseSlots];
-  __shared__ int ce_sh[4][kFuseSlots];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t seg = (int64_t)blockIdx.x * 4 + wv;
-  if (seg >= segs) return;
-  const int64_t r = blockIdx.y;
-  const int64_t R = gridDim.y;
-  uint64_t tk = 0;
-  for (int g = 0; g < G; ++g) {
-    const uint64_t k = order_key(samp[(r * G + g) * kk + kk - 1]);
-    tk = k > tk ? k : tk;
-  }
-  const double amin = (double)als_mm[r], amax = (double)als_mm[R + r];
-  double arange = amax - amin;
-  if (arange < 10.0 * DBL_EPSILON) arange = 1.0;
-  const double ascale = 1.0 / arange;
-  const double amin_ = 0.0 - amin * ascale;
-  const float tmin = tt_mm[r], tmax = tt_mm[R + r];
-  float trange = tmax - tmin;
-  if (trange < 10.0f * FLT_EPSILON) trange = 1.0f;
-  const float tscale = 1.0f / trange;
-  const float tmin_ = 0.0f - tmin * tscale;
-  const int64_t seg0 = seg * kFuseSeg;
-  const float* __restrict__ ar = als + r * ld + seg0 + lane;
-  const float* __restrict__ tr = tt + r * ld + seg0 + lane;
-  const int nvalid = (int)((n - seg0) < kFuseSeg ? (n - seg0) : kFuseSeg);
-  float av[kFusePer], tv[kFusePer];
-  if (nvalid == kFuseSeg) {
-#pragma unroll
-    for (int e = 0; e < kFusePer; ++e) {
-      av[e] = ar[e * 64];
-      tv[e] = tr[e * 64];
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < kFusePer; ++e) {
-      const int off = e * 64 + lane < nvalid ? e * 64 : 0;
-      av[e] = ar[off];
-      tv[e] = tr[off];
-    }
-  }
-  int nc = 0;
-#pragma unroll
-  for (int e = 0; e < kFusePer; ++e) {
-    const double an = (double)av[e] * ascale + amin_;
-    const float tn = tv[e] * tscale + tmin_;
-    const uint64_t key = order_key(w0 * an + w1 * (double)tn);
-    const bool c = e * 64 + lane < nvalid && key >= tk;
-    const uint64_t m = __ballot(c);
-    if (m == 0) continue;  // wave-uniform
-    const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    const int slot = nc + below;
-    if (c && slot < kFuseSlots) {
-      ck_sh[wv][slot] = key;
-      ce_sh[wv][slot] = e * 64 + lane;
-    }
-    nc += __popcll(m);
-  }
-  if (nc > kFuseSlots) {
-    if (lane == 0) *overflow = 1;
-    return;
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  // each candidate's rank among the nc (key desc, position asc) = its slot
-  const uint64_t mk = lane < nc ? ck_sh[wv][lane] : 0;
-  const int mp = lane < nc ? ce_sh[wv][lane] : 0;
-  int rank = 0;
-  for (int q = 0; q < nc; ++q) {
-    const uint64_t ok = ck_sh[wv][q];
-    const int op = ce_sh[wv][q];
-    rank += (ok > mk || (ok == mk && op < mp)) ? 1 : 0;
-  }
-  const int64_t obase = (r * segs + seg) * kk;
-  if (lane < nc && rank < kk) {
-    cand_v[obase + rank] = key_value(mk);
-    cand_i[obase + rank] = seg0 + mp;
-  }
-  if (lane >= nc && lane < kk) {  // fewer candidates than kk: empty slots
-    cand_v[obase + lane] = key_value(0);
-    cand_i[obase + lane] = -1;
-  }
-}
-
-__global__ void add_offset_kernel(int64_t* __restrict__ idx, int64_t n, int64_t off) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n && idx[i] >= 0) idx[i] += off;
-}
-
 }  // namespace hrec
 
 using namespace hrec;
-
-// Workspace for a stable top-k of n_rows rows of n elements (bytes) by the
-// segment selections (kk <= kTopkSelectMax). Each pass keeps kk of every
-// kTopkSeg elements, so it shrinks the row only while kk < kTopkSeg / 2; the
-// loop stops as soon as a pass would not shrink it (larger kk go through the
-// sort path, csrc/sort_topk.hip).
-namespace hrec {
-size_t topk_ws_bytes(int64_t n_rows, int64_t n, int kk, size_t elem) {
-  size_t total = 0;
-  int64_t m = n;
-  if (kk < 1 || kk > kTopkSelectMax) return 256;
-  while (true) {
-    const int64_t segs = (m + kTopkSeg - 1) / kTopkSeg;
-    if (segs <= 1) break;
-    const int64_t cand = segs * kk;
-    if (cand >= m) break;
-    total += (size_t)n_rows * (size_t)cand * (elem + 8);
-    m = cand;
-  }
-  return total + 256;
-}
-}  // namespace hrec
-
-namespace hrec {
-template <typename T>
-int topk_rows(const T* vals, int64_t n_rows, int64_t n, int64_t row_stride, int kk, int64_t* out_idx,
-              T* out_val, void* ws, size_t ws_bytes, hipStream_t s, const int64_t* src_idx, const int* row_n,
-              const int* gate) {
-  // Multi-pass: segments -> candidates (kk per segment) -> ... -> one segment.
-  const T* cur_v = vals;
-  const int64_t* cur_i = src_idx;
-  int64_t m = n, stride = row_stride;
-  char* w = (char*)ws;
-  size_t used = 0;
-  while (true) {
-    const int64_t segs = (m + kTopkSeg - 1) / kTopkSeg;
-    if (segs <= 1 || (m <= kTopkWaveMax && kk <= 16)) {
-      if (kk <= 16 && m <= kTopkWaveMax) {
-        const dim3 g((unsigned)((n_rows + 3) / 4));
-#define HREC_TOPK_WAVE(KK)                                                                                    \
-  hipLaunchKernelGGL((topk_wave_kernel<T, KK>), g, dim3(256), 0, s, cur_v, cur_i, row_n, n_rows, m, stride, kk, \
-                     out_val, out_idx, (int64_t)kk, gate)
-        if (kk <= 2)
-          HREC_TOPK_WAVE(2);
-        else if (kk <= 4)
-          HREC_TOPK_WAVE(4);
-        else if (kk == 5)  // the reference's default top_k: 5-deep lane lists
-          HREC_TOPK_WAVE(5);
-        else if (kk <= 8)
-          HREC_TOPK_WAVE(8);
-        else
-          HREC_TOPK_WAVE(16);
-#undef HREC_TOPK_WAVE
-        return check_launch("topk_wave_kernel");
-      }
-      hipLaunchKernelGGL((topk_segment_kernel<T>), dim3(1, (unsigned)n_rows), dim3(kTopkBlock), 0, s, cur_v,
-                         cur_i, row_n, m, stride, kk, out_val, out_idx, (int64_t)kk, gate);
-      return check_launch("topk_segment_kernel");
-    }
-    const int64_t cand = segs * kk;
-    const size_t vb = (size_t)n_rows * cand * sizeof(T), ib = (size_t)n_rows * cand * 8;
-    if (used + vb + ib > ws_bytes) {
-      set_error("topk: workspace too small");
-      return HREC_E_INVALID;
-    }
-    int64_t* ni = (int64_t*)(w + used);
-    T* nv = (T*)(w + used + ib);
-    used += vb + ib;
-    hipLaunchKernelGGL((topk_segment_kernel<T>), dim3((unsigned)segs, (unsigned)n_rows), dim3(kTopkBlock), 0, s,
-                       cur_v, cur_i, row_n, m, stride, kk, nv, ni, cand, gate);
-    int rc = check_launch("topk_segment_kernel");
-    if (rc) return rc;
-    cur_v = nv;
-    cur_i = ni;
-    row_n = nullptr;  // later passes: every row holds segs * kk entries
-    m = cand;
-    stride = cand;
-  }
-}
-template int topk_rows<float>(const float*, int64_t, int64_t, int64_t, int, int64_t*, float*, void*, size_t,
-                              hipStream_t, const int64_t*, const int*, const int*);
-template int topk_rows<double>(const double*, int64_t, int64_t, int64_t, int, int64_t*, double*, void*, size_t,
-                               hipStream_t, const int64_t*, const int*, const int*);
-}  // namespace hrec
 
 extern "C" int hrec_als_score(const float* user_factors, const int64_t* user_rows, int n_users,
                               const float* item_factors_t, int64_t ld_items, const int64_t* item_rows,
@@ -1115,100 +280,6 @@ extern "C" int hrec_als_score(const float* user_factors, const int64_t* user_row
   return check_launch("als_score_kernel");
 }
 
-extern "C" size_t hrec_topk_workspace_bytes(int64_t n_rows, int64_t n, int top_k, int is_f64) {
-  const int64_t kk = top_k < n ? top_k : n;
-  if (kk > kTopkSelectMax) return sort_topk_ws_bytes(n_rows, n);
-  return topk_ws_bytes(n_rows, n, (int)kk, is_f64 ? 8 : 4);
-}
-
-extern "C" int hrec_topk_f32(const float* vals, int64_t n_rows, int64_t n, int64_t row_stride, int top_k,
-                             int64_t* out_idx, float* out_val, void* workspace, size_t workspace_bytes,
-                             void* stream) {
-  HREC_REQUIRE(n_rows >= 0 && n >= 0 && row_stride >= n, "topk_f32: bad shape");
-  HREC_REQUIRE(top_k >= 1, "topk_f32: top_k must be >= 1");
-  if (n_rows == 0 || n == 0) return HREC_OK;
-  HREC_REQUIRE(n_rows < 65536, "topk_f32: at most 65535 rows per call");
-  HREC_REQUIRE(vals && out_idx && out_val, "topk_f32: null pointer");
-  const int kk = (int)(top_k < n ? top_k : n);
-  if (kk > kTopkSelectMax)
-    return sort_topk_rows<float>(vals, n_rows, n, row_stride, kk, out_idx, out_val, workspace, workspace_bytes,
-                                as_stream(stream));
-  return topk_rows<float>(vals, n_rows, n, row_stride, kk, out_idx, out_val, workspace, workspace_bytes,
-                          as_stream(stream));
-}
-
-extern "C" int hrec_topk_f64(const double* vals, int64_t n_rows, int64_t n, int64_t row_stride, int top_k,
-                             int64_t* out_idx, double* out_val, void* workspace, size_t workspace_bytes,
-                             void* stream) {
-  HREC_REQUIRE(n_rows >= 0 && n >= 0 && row_stride >= n, "topk_f64: bad shape");
-  HREC_REQUIRE(top_k >= 1, "topk_f64: top_k must be >= 1");
-  if (n_rows == 0 || n == 0) return HREC_OK;
-  HREC_REQUIRE(n_rows < 65536, "topk_f64: at most 65535 rows per call");
-  HREC_REQUIRE(vals && out_idx && out_val, "topk_f64: null pointer");
-  const int kk = (int)(top_k < n ? top_k : n);
-  if (kk > kTopkSelectMax)
-    return sort_topk_rows<double>(vals, n_rows, n, row_stride, kk, out_idx, out_val, workspace, workspace_bytes,
-                                as_stream(stream));
-  return topk_rows<double>(vals, n_rows, n, row_stride, kk, out_idx, out_val, workspace, workspace_bytes,
-                           as_stream(stream));
-}
-
-static constexpr int kMinmaxParts = 256;
-
-extern "C" size_t hrec_fuse_workspace_bytes(int64_t n, int top_k) {
-  const int64_t kk = top_k < n ? top_k : n;
-  const size_t t = kk > kTopkSelectMax ? sort_topk_ws_bytes(1, n) : topk_ws_bytes(1, n, (int)kk, 8);
-  return (size_t)kMinmaxParts * 4 * 8 + 64 + (size_t)n * 8 + t;
-}
-
-extern "C" int hrec_fuse_topk(const double* als, const void* tt, int tt_is_f32, int64_t n, int als_wins,
-                              int top_k, int64_t* out_idx, double* out_score, double* out_fused,
-                              double* out_minmax, void* workspace, size_t workspace_bytes, void* stream) {
-  HREC_REQUIRE(n >= 0, "fuse_topk: negative n");
-  HREC_REQUIRE(top_k >= 0, "fuse_topk: top_k must be >= 0");
-  if (n == 0) return HREC_OK;
-  HREC_REQUIRE(als && tt, "fuse_topk: null input");
-  HREC_REQUIRE(top_k == 0 || (out_idx && out_score), "fuse_topk: null output");
-  const size_t need = hrec_fuse_workspace_bytes(n, top_k);
-  HREC_REQUIRE(workspace && workspace_bytes >= need, "fuse_topk: workspace %zu < %zu", workspace_bytes, need);
-  hipStream_t s = as_stream(stream);
-  char* w = (char*)workspace;
-  double* part = (double*)w;
-  double* coef = (double*)(w + kMinmaxParts * 4 * 8);
-  double* fused = out_fused ? out_fused : (double*)(w + kMinmaxParts * 4 * 8 + 64);
-  char* tws = w + kMinmaxParts * 4 * 8 + 64 + (size_t)n * 8;
-  const size_t tws_bytes = workspace_bytes - (kMinmaxParts * 4 * 8 + 64 + (size_t)n * 8);
-  const int parts = (int)((n + 255) / 256 < kMinmaxParts ? (n + 255) / 256 : kMinmaxParts);
-  hipLaunchKernelGGL(minmax_partial_kernel, dim3(parts), dim3(256), 0, s, als, tt, tt_is_f32, n, part);
-  int rc = check_launch("minmax_partial_kernel");
-  if (rc) return rc;
-  hipLaunchKernelGGL(minmax_final_kernel, dim3(1), dim3(64), 0, s, part, parts, tt_is_f32, coef,
-                     out_minmax);
-  rc = check_launch("minmax_final_kernel");
-  if (rc) return rc;
-  // src/hybrid_system.py:69 — strict '>' picks (0.8, 0.2), else (0.2, 0.8).
-  const double w0 = als_wins ? 0.8 : 0.2, w1 = als_wins ? 0.2 : 0.8;
-  hipLaunchKernelGGL(fuse_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, als, tt, tt_is_f32, n,
-                     coef, w0, w1, fused);
-  rc = check_launch("fuse_kernel");
-  if (rc || top_k == 0) return rc;
-  const int kk = (int)(top_k < n ? top_k : n);
-  if (kk > kTopkSelectMax) return sort_topk_rows<double>(fused, 1, n, n, kk, out_idx, out_score, tws, tws_bytes, s);
-  rc = topk_rows<double>(fused, 1, n, n, kk, out_idx, out_score, tws, tws_bytes, s);
-  return rc;
-}
-
-extern "C" int hrec_cosine_sim(const double* feats, int64_t n_items, int dim, const int64_t* query_rows,
-                               int64_t n_query, double* out, void* stream) {
-  HREC_REQUIRE(n_items >= 0 && n_query >= 0 && dim >= 1, "cosine_sim: bad shape");
-  if (n_items == 0 || n_query == 0) return HREC_OK;
-  HREC_REQUIRE(n_query < 65536, "cosine_sim: at most 65535 queries per call");
-  HREC_REQUIRE(feats && query_rows && out, "cosine_sim: null pointer");
-  const dim3 grid((unsigned)((n_items + 255) / 256), (unsigned)n_query);
-  hipLaunchKernelGGL(cosine_kernel, grid, dim3(256), 0, as_stream(stream), feats, n_items, dim, query_rows, out);
-  return check_launch("cosine_kernel");
-}
-
 #ifndef HREC_SCORE_UB
 #define HREC_SCORE_UB 16
 #endif
@@ -1220,22 +291,43 @@ static constexpr int kSample = HREC_SCORE_SAMPLE;  // items scored for the survi
 static constexpr int kSampleUB = 4;
 static constexpr int kCap = 4096;
 
-extern "C" size_t hrec_als_score_topk_workspace_bytes(int n_users, int64_t n_items, int top_k) {
-  const size_t B = (size_t)n_users;
-  const int64_t S = n_items < kSample ? n_items : kSample;
-  size_t b = B * (size_t)S * 4 + 256;                          // sample scores
-  b += topk_ws_bytes(B, S, top_k, 4) + 256;                     // sample top-k workspace
-  b += B * (size_t)top_k * 12 + 256;                            // sample top-k values / indices
-  b += B * (size_t)kCap * 12 + 256;                             // candidates
-  b += B * 4 + 256 + 16;                                        // counters + flag
-  b += topk_ws_bytes(B, kCap, top_k, 4) + 256;                  // final top-k workspace
-  return b;
+// Workspace of the fused path, in carve order.
+struct ScoreWs {
+  float* samp;  // [B][S] sample scores
+  char* tws;    // sample top-k workspace
+  float* sv;    // [B][kk] sample top-k values / indices
+  int64_t* si;
+  float* cv;    // [B][kCap] candidates
+  int64_t* ci;
+  int* cn;      // [B] counters
+  char* fws;    // final top-k workspace
+  size_t total;
+};
+
+static ScoreWs score_layout(void* base, int B, int64_t N, int kk) {
+  ScoreWs w{};
+  Carver c(base);
+  const int64_t S = N < kSample ? N : kSample;
+  w.samp = (float*)c.take((size_t)B * S * 4);
+  w.tws = c.take(topk_ws_bytes(B, S, kk, 4));
+  w.sv = (float*)c.take((size_t)B * kk * 4);
+  w.si = (int64_t*)c.take((size_t)B * kk * 8);
+  w.cv = (float*)c.take((size_t)B * kCap * 4);
+  w.ci = (int64_t*)c.take((size_t)B * kCap * 8);
+  w.cn = (int*)c.take((size_t)B * 4 + 16);
+  w.fws = c.take(topk_ws_bytes(B, kCap, kk, 4));
+  w.total = c.total() + 256;
+  return w;
 }
 
-static char* carve(char*& p, size_t bytes) {
-  char* r = p;
-  p += (bytes + 255) & ~(size_t)255;
-  return r;
+// kk of a call: min(top_k, n_items), within the selection kernels' [1, 1024]
+static int score_kk(int64_t n_items, int top_k) {
+  const int64_t kk = top_k < n_items ? top_k : n_items;
+  return (int)(kk < 1 ? 1 : (kk > 1024 ? 1024 : kk));
+}
+
+extern "C" size_t hrec_als_score_topk_workspace_bytes(int n_users, int64_t n_items, int top_k) {
+  return score_layout(nullptr, n_users > 0 ? n_users : 0, n_items > 0 ? n_items : 0, score_kk(n_items, top_k)).total;
 }
 
 extern "C" int hrec_als_score_topk(const float* user_factors, const int64_t* user_rows, int n_users,
@@ -1255,47 +347,39 @@ extern "C" int hrec_als_score_topk(const float* user_factors, const int64_t* use
   HREC_REQUIRE(workspace_bytes >= need, "als_score_topk: workspace %zu < %zu", workspace_bytes, need);
   hipStream_t s = as_stream(stream);
   const int kk = (int)(top_k < n_items ? top_k : n_items);
-  char* p = (char*)workspace;
   const int64_t S = n_items < kSample ? n_items : kSample;
-  float* samp = (float*)carve(p, (size_t)n_users * S * 4);
-  char* tws = carve(p, topk_ws_bytes(n_users, S, kk, 4));
-  float* sv = (float*)carve(p, (size_t)n_users * kk * 4);
-  int64_t* si = (int64_t*)carve(p, (size_t)n_users * kk * 8);
-  float* cv = (float*)carve(p, (size_t)n_users * kCap * 4);
-  int64_t* ci = (int64_t*)carve(p, (size_t)n_users * kCap * 8);
-  int* cn = (int*)carve(p, (size_t)n_users * 4 + 16);
-  char* fws = carve(p, topk_ws_bytes(n_users, kCap, kk, 4));
+  const ScoreWs w = score_layout(workspace, n_users, n_items, kk);
   const dim3 blk(256);
   const unsigned gy = (unsigned)((n_users + kScoreUB - 1) / kScoreUB);
   if (hipMemsetAsync(overflow, 0, sizeof(int), s) != hipSuccess) return check_launch("score_topk memset");
   if (n_items <= kSample) {  // small: score everything, exact top-k
     hipLaunchKernelGGL((als_score_fast_kernel<kScoreUB, false>), dim3(gy, (unsigned)((n_items + 1023) / 1024)), blk,
-                       0, s, user_factors, user_rows, n_users, item_factors_t, ld_items, n_items, k, kp, samp,
+                       0, s, user_factors, user_rows, n_users, item_factors_t, ld_items, n_items, k, kp, w.samp,
                        nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr);
     int rc = check_launch("als_score_fast_kernel");
     if (rc) return rc;
-    return topk_rows<float>(samp, n_users, n_items, n_items, kk, out_idx, out_val, tws, (size_t)1 << 62, s);
+    return topk_rows<float>(w.samp, n_users, n_items, n_items, kk, out_idx, out_val, w.tws, (size_t)1 << 62, s);
   }
   // 1) thresholds: the kk-th best of the first S items bounds the final kk-th from below
   //    (4 users per block: the sample is too small to fill the chip with 16)
   hipLaunchKernelGGL((als_score_fast_kernel<kSampleUB, false>),
                      dim3((unsigned)((n_users + kSampleUB - 1) / kSampleUB), (unsigned)((S + 1023) / 1024)), blk, 0,
-                     s, user_factors, user_rows, n_users, item_factors_t, ld_items, S, k, kp, samp, nullptr, 0, 0,
+                     s, user_factors, user_rows, n_users, item_factors_t, ld_items, S, k, kp, w.samp, nullptr, 0, 0,
                      nullptr, nullptr, nullptr, nullptr);
   int rc = check_launch("als_score_fast_kernel(sample)");
   if (rc) return rc;
-  const float* thr = sv + (kk - 1);
+  const float* thr = w.sv + (kk - 1);
   int thr_stride = kk;
   if (kk <= 64) {  // a lower bound suffices: the 64 lane maxima's kk-th
     // (also zeroes the survivor counters: no separate memset launch)
-    hipLaunchKernelGGL(sample_threshold_kernel, dim3((unsigned)((n_users + 3) / 4)), dim3(256), 0, s, samp,
-                       (int64_t)n_users, S, kk, sv, cn);
+    hipLaunchKernelGGL(sample_threshold_kernel, dim3((unsigned)((n_users + 3) / 4)), dim3(256), 0, s, w.samp,
+                       (int64_t)n_users, S, kk, w.sv, w.cn);
     rc = check_launch("sample_threshold_kernel");
-    thr = sv;
+    thr = w.sv;
     thr_stride = 1;
   } else {
-    rc = topk_rows<float>(samp, n_users, S, S, kk, si, sv, tws, (size_t)1 << 62, s);
-    if (rc == HREC_OK && hipMemsetAsync(cn, 0, (size_t)n_users * 4, s) != hipSuccess)
+    rc = topk_rows<float>(w.samp, n_users, S, S, kk, w.si, w.sv, w.tws, (size_t)1 << 62, s);
+    if (rc == HREC_OK && hipMemsetAsync(w.cn, 0, (size_t)n_users * 4, s) != hipSuccess)
       return check_launch("score_topk memset");
   }
   if (rc) return rc;
@@ -1303,11 +387,11 @@ extern "C" int hrec_als_score_topk(const float* user_factors, const int64_t* use
   //    kCap raises *overflow from inside the filter (the caller falls back)
   hipLaunchKernelGGL((als_score_fast_kernel<kScoreUB, true>), dim3(gy, (unsigned)((n_items + 1023) / 1024)), blk, 0,
                      s, user_factors, user_rows, n_users, item_factors_t, ld_items, n_items, k, kp, nullptr,
-                     thr, thr_stride, kCap, cv, ci, cn, overflow);
+                     thr, thr_stride, kCap, w.cv, w.ci, w.cn, overflow);
   rc = check_launch("als_score_fast_kernel(filter)");
   if (rc) return rc;
   // 3) exact stable top-k over the candidates (original item index breaks ties)
-  return topk_rows<float>(cv, n_users, kCap, kCap, kk, out_idx, out_val, fws, (size_t)1 << 62, s, ci, cn);
+  return topk_rows<float>(w.cv, n_users, kCap, kCap, kk, out_idx, out_val, w.fws, (size_t)1 << 62, s, w.ci, w.cn);
 }
 
 // ---------------------------------------------------- K2p: pruned ALS top-k
@@ -1362,11 +446,6 @@ __device__ __forceinline__ float pr_down(double x) {
   if ((double)f > x) f = nextafterf(f, -INFINITY);
   return f;
 }
-__device__ __forceinline__ uint16_t pr_bf16(float v) {  // round to nearest even (NaN stays NaN)
-  const uint32_t x = __float_as_uint(v);
-  if ((x & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((x >> 16) | 0x40u);
-  return (uint16_t)((x + 0x7fffu + ((x >> 16) & 1u)) >> 16);
-}
 
 // Item operand: bf16 rows [N][dk] (zero beyond k) and the largest row norm
 // rounded up (+inf for a non-finite value), one thread per row.
@@ -1383,7 +462,7 @@ __global__ __launch_bounds__(256) void als_items_bf16_kernel(const float* __rest
       const float v1 = c + 1 < k ? V[row * ldv + c + 1] : 0.f;
       ss += (double)v0 * v0 + (double)v1 * v1;
       bad = bad || !isfinite(v0) || !isfinite(v1);
-      o[c >> 1] = (uint32_t)pr_bf16(v0) | ((uint32_t)pr_bf16(v1) << 16);
+      o[c >> 1] = bf16_rne(v0) | (bf16_rne(v1) << 16);
     }
   }
   const double nrm = sqrt(ss) * (1.0 + 1e-6);
@@ -1414,7 +493,7 @@ __global__ __launch_bounds__(256) void als_prune_user_kernel(const float* __rest
     const float v = (r >= 0 && c < k) ? U[r * kp + c] : 0.f;
     ss += (double)v * v;
     bad = bad || !isfinite(v);
-    uop[(int64_t)b * dk + c] = pr_bf16(v);
+    uop[(int64_t)b * dk + c] = (uint16_t)bf16_rne(v);
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
@@ -1995,7 +1074,7 @@ static int prune_dk(int k) { return k <= 32 ? 32 : (k <= 64 ? 64 : (k <= 128 ? 1
 
 extern "C" size_t hrec_als_items_bf16_bytes(int64_t n_items, int k) {
   const int64_t n = n_items > 0 ? n_items : 0;
-  return (((size_t)n * prune_dk(k) * 2 + 255) & ~(size_t)255) + 256;
+  return al256((size_t)n * prune_dk(k) * 2) + 256;
 }
 
 extern "C" int hrec_als_items_bf16(const float* item_factors, int64_t ld_v, int64_t n_items, int k, void* out,
@@ -2036,36 +1115,30 @@ struct PruneWs {
 
 static PruneWs prune_layout(char* base, int B, int64_t N, int kk, int dk) {
   PruneWs w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* r = base ? base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return r;
-  };
+  Carver c(base);
   const int64_t S = N < kPruneSample ? N : kPruneSample;
-  w.samp = (float*)take((size_t)B * S * 4);
-  w.tws = take(topk_ws_bytes(B, S, kk, 4));
-  w.sv = (float*)take((size_t)B * kk * 4);
-  w.si = (int64_t*)take((size_t)B * kk * 8);
-  w.err = (double*)take((size_t)B * 8);
-  w.tau = (float*)take((size_t)B * 4);
-  w.thr2 = (float*)take((size_t)B * 4);
-  w.uop = (uint16_t*)take((size_t)B * dk * 2);
-  w.pi = (int64_t*)take((size_t)B * kCap * 8);
-  w.pn = (int*)take((size_t)B * 4);
-  w.cv = (float*)take((size_t)B * kCap * 4);
-  w.ci = (int64_t*)take((size_t)B * kCap * 8);
-  w.cn = (int*)take((size_t)B * 4);
-  w.fws = take(topk_ws_bytes(B, kCap, kk, 4));
-  w.total = off + 256;
+  w.samp = (float*)c.take((size_t)B * S * 4);
+  w.tws = c.take(topk_ws_bytes(B, S, kk, 4));
+  w.sv = (float*)c.take((size_t)B * kk * 4);
+  w.si = (int64_t*)c.take((size_t)B * kk * 8);
+  w.err = (double*)c.take((size_t)B * 8);
+  w.tau = (float*)c.take((size_t)B * 4);
+  w.thr2 = (float*)c.take((size_t)B * 4);
+  w.uop = (uint16_t*)c.take((size_t)B * dk * 2);
+  w.pi = (int64_t*)c.take((size_t)B * kCap * 8);
+  w.pn = (int*)c.take((size_t)B * 4);
+  w.cv = (float*)c.take((size_t)B * kCap * 4);
+  w.ci = (int64_t*)c.take((size_t)B * kCap * 8);
+  w.cn = (int*)c.take((size_t)B * 4);
+  w.fws = c.take(topk_ws_bytes(B, kCap, kk, 4));
+  w.total = c.total() + 256;
   return w;
 }
 
 extern "C" size_t hrec_als_score_topk_pruned_workspace_bytes(int n_users, int64_t n_items, int top_k, int k) {
   const int B = n_users > 0 ? n_users : 0;
   const int64_t N = n_items > 0 ? n_items : 0;
-  int kk = (int)(top_k < N ? top_k : N);
-  kk = kk < 1 ? 1 : (kk > 1024 ? 1024 : kk);
+  const int kk = score_kk(N, top_k);
   const size_t fused = hrec_als_score_topk_workspace_bytes(n_users, n_items, top_k);  // the small-catalogue path
   const size_t own = prune_layout(nullptr, B, N, kk, prune_dk(k)).total;
   return own > fused ? own : fused;
@@ -2194,167 +1267,4 @@ extern "C" int hrec_als_score_topk_pruned(const float* user_factors, const int64
   if (rc) return rc;
   // 4) the same exact stable top-k over the candidates
   return topk_rows<float>(w.cv, n_users, kCap, kCap, kk, out_idx, out_val, w.fws, (size_t)1 << 62, s, w.ci, w.cn);
-}
-
-extern "C" int hrec_rows_minmax_f32(const float* x, int64_t n_rows, int64_t n, int64_t ld, float* out, void* stream) {
-  HREC_REQUIRE(n_rows >= 0 && n >= 0 && ld >= n, "rows_minmax: bad shape");
-  if (n_rows == 0) return HREC_OK;
-  HREC_REQUIRE(n_rows < (1ll << 31), "rows_minmax: too many rows");
-  HREC_REQUIRE(x && out, "rows_minmax: null pointer");
-  const int vec4 = (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-  hipLaunchKernelGGL(rows_minmax_kernel, dim3((unsigned)n_rows), dim3(1024), 0, as_stream(stream), x, n, ld, vec4,
-                     out);
-  return check_launch("rows_minmax_kernel");
-}
-
-// Threshold-filter path (kk <= kFuseK): sample segments per row
-static int64_t fuse_sample_segs(int64_t n, int /*kk*/) {
-  // ~kk / G expected candidates per segment (the bound is the best of G
-  // segments' kk-th best) against kFuseSlots
-  const int64_t segs = (n + kFuseSeg - 1) / kFuseSeg;
-  return segs < 4 ? segs : 4;
-}
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-extern "C" size_t hrec_fuse_rows_workspace_bytes(int64_t n_rows, int64_t n, int top_k) {
-  const int kk = (int)(top_k < n ? top_k : n);
-  if (kk >= 1 && kk <= kFuseK) {
-    const int64_t segs = (n + kFuseSeg - 1) / kFuseSeg, G = fuse_sample_segs(n, kk);
-    const size_t seg_path = 2 * al256((size_t)n_rows * segs * kk * 8) + topk_ws_bytes(n_rows, segs * kk, kk, 8);
-    return 2 * al256((size_t)n_rows * G * kk * 8) + al256(4) + 2 * seg_path + 256;
-  }
-  return (size_t)n_rows * n * 8 + 256 + topk_ws_bytes(n_rows, n, top_k, 8);
-}
-
-extern "C" int hrec_fuse_rows_topk(const float* als, const float* tt, int64_t n_rows, int64_t n, int64_t ld,
-                                   const float* als_minmax, const float* tt_minmax, int als_wins, int top_k,
-                                   int64_t idx_offset, int64_t* out_idx, double* out_val, void* workspace,
-                                   size_t workspace_bytes, void* stream) {
-  HREC_REQUIRE(n_rows >= 0 && n >= 1 && ld >= n, "fuse_rows_topk: bad shape");
-  HREC_REQUIRE(n_rows < 65536, "fuse_rows_topk: at most 65535 rows per call");
-  HREC_REQUIRE(top_k >= 1 && top_k <= 1024, "fuse_rows_topk: top_k must be in [1, 1024]");
-  if (n_rows == 0) return HREC_OK;
-  HREC_REQUIRE(als && tt && als_minmax && tt_minmax && out_idx && out_val && workspace, "fuse_rows_topk: null pointer");
-  const size_t need = hrec_fuse_rows_workspace_bytes(n_rows, n, top_k);
-  HREC_REQUIRE(workspace_bytes >= need, "fuse_rows_topk: workspace %zu < %zu", workspace_bytes, need);
-  hipStream_t s = as_stream(stream);
-  const double w0 = als_wins ? 0.8 : 0.2, w1 = als_wins ? 0.2 : 0.8;
-  const int kk = (int)(top_k < n ? top_k : n);
-  int rc;
-  if (kk <= kFuseK) {
-    // 1. sample: the exact top-kk of each row's first G segments
-    // 2. filter: every item whose fused key reaches the sample bound -> row list
-    // 3. exact keyed top-kk of the lists
-    // 4. (gated on overflow) the exact segment path over every segment
-    const int64_t segs = (n + kFuseSeg - 1) / kFuseSeg, G = fuse_sample_segs(n, kk);
-    char* p = (char*)workspace;
-    auto take = [&](size_t b) { char* q = p; p += al256(b); return q; };
-    double* sv = (double*)take((size_t)n_rows * G * kk * 8);
-    int64_t* si = (int64_t*)take((size_t)n_rows * G * kk * 8);
-    int* over = (int*)take(4);
-    double* cv = (double*)take((size_t)n_rows * segs * kk * 8);
-    int64_t* ci = (int64_t*)take((size_t)n_rows * segs * kk * 8);
-    char* tws = take(topk_ws_bytes(n_rows, segs * kk, kk, 8));
-    double* gv = (double*)take((size_t)n_rows * segs * kk * 8);
-    int64_t* gi = (int64_t*)take((size_t)n_rows * segs * kk * 8);
-    char* gws = p;
-#define HREC_FUSE_K(K, GRID, SEGS, V, I, GATE, CLEAR)                                                           \
-  case K:                                                                                                       \
-    hipLaunchKernelGGL(fuse_segment_topk_kernel<K>, GRID, dim3(256), 0, s, als, tt, n, ld, SEGS, als_minmax,   \
-                       tt_minmax, w0, w1, V, I, GATE, CLEAR);                                                   \
-    break;
-#define HREC_FUSE_SWITCH(GRID, SEGS, V, I, GATE, CLEAR)                                                          \
-  switch (kk) {                                                                                                 \
-    HREC_FUSE_K(1, GRID, SEGS, V, I, GATE, CLEAR) HREC_FUSE_K(2, GRID, SEGS, V, I, GATE, CLEAR)                \
-    HREC_FUSE_K(3, GRID, SEGS, V, I, GATE, CLEAR) HREC_FUSE_K(4, GRID, SEGS, V, I, GATE, CLEAR)                \
-    HREC_FUSE_K(5, GRID, SEGS, V, I, GATE, CLEAR) HREC_FUSE_K(6, GRID, SEGS, V, I, GATE, CLEAR)                \
-    HREC_FUSE_K(7, GRID, SEGS, V, I, GATE, CLEAR) default : HREC_FUSE_K(8, GRID, SEGS, V, I, GATE, CLEAR)      \
-  }
-    const dim3 gs((unsigned)((G + 3) / 4), (unsigned)n_rows);
-    HREC_FUSE_SWITCH(gs, G, sv, si, nullptr, over)  // also clears the overflow flag
-    rc = check_launch("fuse_segment_topk_kernel (sample)");
-    if (rc) return rc;
-    const dim3 gf((unsigned)((segs + 3) / 4), (unsigned)n_rows);
-    hipLaunchKernelGGL(fuse_filter_kernel, gf, dim3(256), 0, s, als, tt, n, ld, segs, als_minmax, tt_minmax, w0, w1,
-                       sv, (int)G, kk, cv, ci, over);
-    rc = check_launch("fuse_filter_kernel");
-    if (rc) return rc;
-    rc = topk_rows<double>(cv, n_rows, segs * kk, segs * kk, kk, out_idx, out_val, tws, (size_t)1 << 62, s, ci);
-    if (rc) return rc;
-    // exact path, run only if some row overflowed its list (one block per
-    // row: a skipped launch costs a small grid)
-    HREC_FUSE_SWITCH(dim3(1, (unsigned)n_rows), segs, gv, gi, over, nullptr)
-#undef HREC_FUSE_SWITCH
-#undef HREC_FUSE_K
-    rc = check_launch("fuse_segment_topk_kernel (gated)");
-    if (rc) return rc;
-    rc = topk_rows<double>(gv, n_rows, segs * kk, segs * kk, kk, out_idx, out_val, gws, (size_t)1 << 62, s, gi,
-                           nullptr, over);
-  } else {
-    double* fused = (double*)workspace;
-    char* tws = (char*)workspace + (((size_t)n_rows * n * 8 + 255) & ~(size_t)255);
-    hipLaunchKernelGGL(fuse_rows_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)n_rows), dim3(256), 0, s, als,
-                       tt, n, ld, als_minmax, tt_minmax, w0, w1, fused);
-    rc = check_launch("fuse_rows_kernel");
-    if (rc) return rc;
-    rc = topk_rows<double>(fused, n_rows, n, n, kk, out_idx, out_val, tws, (size_t)1 << 62, s);
-  }
-  if (rc || idx_offset == 0) return rc;
-  const int64_t tot = n_rows * kk;
-  hipLaunchKernelGGL(add_offset_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, out_idx, tot, idx_offset);
-  return check_launch("add_offset_kernel");
-}
-
-namespace hrec {
-// The exact segment path of hrec_fuse_rows_topk (kk <= kFuseK), gated on a
-// device flag (launches do nothing while *gate == 0): the pruned hybrid
-// top-k's fallback (csrc/hybrid_prune.hip). One block per row walks every
-// segment; then the keyed top-kk of the segments' candidates.
-size_t fuse_rows_exact_ws_bytes(int64_t n_rows, int64_t n, int kk) {
-  const int64_t segs = (n + kFuseSeg - 1) / kFuseSeg;
-  return 2 * al256((size_t)n_rows * segs * kk * 8) + topk_ws_bytes(n_rows, segs * kk, kk, 8) + 256;
-}
-
-int fuse_rows_exact(const float* als, const float* tt, int64_t n_rows, int64_t n, int64_t ld, const float* als_mm,
-                    const float* tt_mm, double w0, double w1, int kk, int64_t* out_idx, double* out_val, void* ws,
-                    hipStream_t s, const int* gate) {
-  if (kk < 1 || kk > kFuseK) {
-    set_error("fuse_rows_exact: kk must be in [1, %d]", kFuseK);
-    return HREC_E_INVALID;
-  }
-  const int64_t segs = (n + kFuseSeg - 1) / kFuseSeg;
-  char* p = (char*)ws;
-  double* gv = (double*)p;
-  p += al256((size_t)n_rows * segs * kk * 8);
-  int64_t* gi = (int64_t*)p;
-  p += al256((size_t)n_rows * segs * kk * 8);
-  const dim3 grid(1, (unsigned)n_rows);
-  switch (kk) {
-#define HREC_FX(K)                                                                                                  \
-  case K:                                                                                                           \
-    hipLaunchKernelGGL(fuse_segment_topk_kernel<K>, grid, dim3(256), 0, s, als, tt, n, ld, segs, als_mm, tt_mm, w0, \
-                       w1, gv, gi, gate, nullptr);                                                                  \
-    break;
-    HREC_FX(1) HREC_FX(2) HREC_FX(3) HREC_FX(4) HREC_FX(5) HREC_FX(6) HREC_FX(7) default : HREC_FX(8)
-#undef HREC_FX
-  }
-  const int rc = check_launch("fuse_segment_topk_kernel (exact, gated)");
-  if (rc) return rc;
-  return topk_rows<double>(gv, n_rows, segs * kk, segs * kk, kk, out_idx, out_val, p, (size_t)1 << 62, s, gi, nullptr,
-                           gate);
-}
-}  // namespace hrec
-
-extern "C" int hrec_topk_f64_keyed(const double* vals, const int64_t* keys, int64_t n_rows, int64_t n, int top_k,
-                                   int64_t* out_idx, double* out_val, void* workspace, size_t workspace_bytes,
-                                   void* stream) {
-  HREC_REQUIRE(n_rows >= 0 && n >= 0, "topk_f64_keyed: bad shape");
-  HREC_REQUIRE(top_k >= 1 && top_k <= 1024, "topk_f64_keyed: top_k must be in [1, 1024]");
-  if (n_rows == 0 || n == 0) return HREC_OK;
-  HREC_REQUIRE(n_rows < 65536, "topk_f64_keyed: at most 65535 rows per call");
-  HREC_REQUIRE(vals && keys && out_idx && out_val, "topk_f64_keyed: null pointer");
-  const int kk = (int)(top_k < n ? top_k : n);
-  HREC_REQUIRE(workspace_bytes >= topk_ws_bytes(n_rows, n, kk, 8), "topk_f64_keyed: workspace too small");
-  return topk_rows<double>(vals, n_rows, n, n, kk, out_idx, out_val, workspace, workspace_bytes, as_stream(stream),
-                           keys);
 }

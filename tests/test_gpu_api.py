@@ -1012,16 +1012,20 @@ def _fuse_rows_reference(als, tt, als_wins, kk):
 
 
 @pytest.mark.parametrize("n,kk,pattern", [(100_000, 5, "random"), (100_000, 1, "random"), (37_000, 8, "quantised"),
-                                          (5000, 5, "constant"), (3000, 3, "two_levels"), (70, 5, "random"),
+                                          (5000, 5, "constant"), (5000, 5, "tiny_range"), (3000, 3, "two_levels"),
+                                          (70, 5, "random"),
                                           (6_000_000, 5, "random"), (20_000, 10, "random")])
 def test_fuse_rows_topk_filter_matches_reference(device, n, kk, pattern):
     """hrec_fuse_rows_topk's threshold-filter path (sample bound -> candidate
     lists -> keyed top-k; overflowing rows take the exact segment path on the
     device) returns the reference's fused top-k: indices bit-exact, values
     bit-exact (same f64 arithmetic). Covers ties (quantised scores, two
-    levels), constant rows (every item a candidate -> overflow), short rows,
-    a 6M-item shard and kk above the filter path's 8."""
+    levels), constant rows (every item a candidate -> overflow), rows whose
+    range is below the scaler's 10 eps but not 0 (both sides, the ALS side
+    only, the two-tower side only), short rows, a 6M-item shard and kk above
+    the filter path's 8."""
     from src import _hrec
+    from test_gpu_core import tiny_range_rows
 
     rng = np.random.default_rng(n + kk)
     B = 3 if n > 1_000_000 else 7
@@ -1032,6 +1036,10 @@ def test_fuse_rows_topk_filter_matches_reference(device, n, kk, pattern):
     elif pattern == "constant":
         a[:] = 2.0
         t[1:] = 0.5
+    elif pattern == "tiny_range":
+        ta, tt_ = tiny_range_rows(B, n)
+        a[[0, 1, 3, 4, 5, 6]] = ta[[0, 1, 3, 4, 5, 6]]  # row 2: only the two-tower side tiny
+        t[[0, 2, 3, 4, 5, 6]] = tt_[[0, 2, 3, 4, 5, 6]]  # row 1: only the ALS side tiny
     elif pattern == "two_levels":
         a = (rng.random((B, n)) < 0.5).astype(np.float32)
         t = (rng.random((B, n)) < 0.5).astype(np.float32)

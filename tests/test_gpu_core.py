@@ -257,7 +257,7 @@ def test_topk_stable(device, n, k, dtype):
 @pytest.mark.parametrize("k", [1, 2, 3, 8, 16, 17])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 def test_topk_wave_path_ties_nan(device, n, k, dtype):
-    """kk <= 16 over rows of <= 8192 run the wave-per-row kernel (csrc/score.hip
+    """kk <= 16 over rows of <= 8192 run the wave-per-row kernel (csrc/topk.hip
     topk_wave_kernel); kk = 17 and n = 8193 the block kernel: same order
     (larger first, ties -> smaller index, NaN last) either way."""
     h = _hrec()
@@ -286,10 +286,36 @@ def _fuse_gpu(device, als_scores, tt_scores, als_wins, top_k):
     return idx.cpu().numpy(), sc.cpu().numpy(), fused.cpu().numpy()
 
 
-@pytest.mark.parametrize("case", load_golden("fusion.json")["cases"], ids=lambda c: c["name"])
+def tiny_range_rows(n_rows, n):
+    """Score rows whose range is below MinMaxScaler's 10 eps without being 0
+    (the scaler then divides by 1): ALS alternating between f32 1e-9 and the
+    next f32 (f64 range ~1e-16 < 10 * 2.2e-16), two-tower between 1 and
+    1 + 4 ulp (range 4.8e-7 < 10 * 1.2e-7)."""
+    hi = (np.arange(n)[None, :] + np.arange(n_rows)[:, None]) % 2 == 1
+    a0 = np.float32(1e-9)
+    a = np.where(hi, np.nextafter(a0, np.float32(1)), a0).astype(np.float32)
+    t = np.where(hi, np.float32(1 + 4 * 2.0 ** -23), np.float32(1)).astype(np.float32)
+    assert 0 < float(a.max()) - float(a.min()) < 10 * np.finfo(np.float64).eps
+    assert 0 < t.max() - t.min() < 10 * np.finfo(np.float32).eps
+    return a, t
+
+
+def _tiny_range_cases():
+    """fusion.json-shaped cases (undecoded pairs replaced by `pairs`): one with
+    only the ALS side's range tiny, one with only the two-tower side's."""
+    n = 300
+    rng = np.random.default_rng(17)
+    a, t = tiny_range_rows(1, n)
+    ids = range(n)
+    als_tiny = (list(zip(ids, a[0].astype(np.float64).tolist())), list(zip(ids, rng.normal(size=n).astype(np.float32))))
+    tt_tiny = (list(zip(ids, rng.normal(size=n).tolist())), list(zip(ids, t[0])))
+    return [{"name": "tiny_range_als", "pairs": als_tiny, "als_f1": 0.3, "tt_f1": 0.1, "top_k": 5},
+            {"name": "tiny_range_tt", "pairs": tt_tiny, "als_f1": 0.1, "tt_f1": 0.3, "top_k": 5}]
+
+
+@pytest.mark.parametrize("case", load_golden("fusion.json")["cases"] + _tiny_range_cases(), ids=lambda c: c["name"])
 def test_fusion_gpu_vs_oracle_legacy(device, case):
-    als = dec_pairs(case["als"])
-    tt = dec_pairs(case["tt"])
+    als, tt = case["pairs"] if "pairs" in case else (dec_pairs(case["als"]), dec_pairs(case["tt"]))
     combined = ofus.adaptive_fusion(als, tt, case["als_f1"], case["tt_f1"], legacy=True)
     items = [i for i, _ in combined]
     ad, td = dict(als), dict(tt)
@@ -482,6 +508,58 @@ def test_als_score_topk_pruned_matches_fused(device, n_items, k, kp, B, top_k, c
     got_i, got_v = pi.cpu().numpy()[known], pv.cpu().numpy()[known]
     np.testing.assert_array_equal(got_i, exp_i)
     np.testing.assert_array_equal(got_v.view(np.int32), np.take_along_axis(full, exp_i, 1).view(np.int32))
+
+
+_BF16_PATTERNS = np.array([
+    0x00000000, 0x80000000,                          # +-0
+    0x00000001, 0x00008000, 0x00008001, 0x00018000,  # denormals: smallest, a tie (-> 0), rounds up, tie from odd
+    0x807FFFFF, 0x007FFFFF, 0x00800000,              # the largest denormals (-> +-min normal), min normal
+    0x3F800000, 0x3F808000, 0x3F818000,              # 1, exact ties from even and from odd
+    0x3F808001, 0x3F807FFF, 0x3F818001, 0x3F817FFF,  # one above / below each tie
+    0xBF808000, 0xBF818000, 0xBF808001, 0xBF807FFF,  # the same, negative
+    0x3F7FFFFF,                                      # carries into the exponent (-> 1)
+    0x7F7F7FFF, 0x7F7F8000, 0x7F7FFFFF, 0xFF7FFFFF,  # near the largest finite: stays, tie -> inf, -> +-inf
+    0x7F800000, 0xFF800000,                          # +-inf
+    0x7FC00000, 0xFFC00000, 0x7FFFFFFF, 0xFFFFFFFF,  # quiet NaNs
+    0x7F800001, 0xFF800001, 0x7FBFFFFF, 0xFFBFFFFF,  # signalling NaNs
+    0x7F80FFFF,                                      # a NaN whose payload is below the kept bits
+    0x3EAAAAAB, 0x40490FDB, 0xC2F6E979, 0x477FE000,  # ordinary values
+], dtype=np.uint32)
+
+
+def _bf16_expected(bits):
+    """f32 bit patterns -> bf16 bits by the integer formula: round to nearest
+    even on the 16 dropped bits; a NaN keeps its top bits and is made quiet."""
+    x = bits.astype(np.uint64)
+    nan = (x & 0x7FFFFFFF) > 0x7F800000
+    rne = (x + 0x7FFF + ((x >> 16) & 1)) >> 16
+    return np.where(nan, (x >> 16) | 0x40, rne).astype(np.uint16)
+
+
+def test_bf16_rounding_bit_patterns(device):
+    """The one f32 -> bf16 rounding of the library, pinned directly: hrec_f32_to_bf16
+    on fixed bit patterns (zeros, denormals, ties to even and to odd and their
+    neighbours, overflow to inf, infinities, quiet and signalling NaNs) against
+    the integer formula; and the pruned ALS top-k's item operand
+    (hrec_als_items_bf16, rows [N][32] for k = 20) == to_bf16 of the rows,
+    zero-padded past k."""
+    h = _hrec()
+
+    def to_bits(f32_bits):
+        x = torch.from_numpy(f32_bits.view(np.int32).copy()).to(device).view(torch.float32)
+        return h.to_bf16(x).view(torch.int16).cpu().numpy().view(np.uint16)
+
+    np.testing.assert_array_equal(to_bits(_BF16_PATTERNS), _bf16_expected(_BF16_PATTERNS))
+    n, k, dk = 70, 20, 32
+    V = np.random.default_rng(3).normal(size=(n, k)).astype(np.float32)
+    V.reshape(-1).view(np.uint32)[:len(_BF16_PATTERNS)] = _BF16_PATTERNS
+    dV = torch.from_numpy(V.view(np.int32).copy()).to(device).view(torch.float32)
+    ops = h.als_items_bf16(dV, k)
+    got = ops[:n * dk * 2].view(torch.int16).cpu().numpy().view(np.uint16).reshape(n, dk)
+    want = np.zeros((n, dk), np.uint16)
+    want[:, :k] = to_bits(V.reshape(-1).view(np.uint32)).reshape(n, k)
+    np.testing.assert_array_equal(got, want)
+    np.testing.assert_array_equal(want[:, :k], _bf16_expected(V.view(np.uint32)))
 
 
 # ------------------------------------------------ multi-rank on one device

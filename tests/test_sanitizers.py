@@ -50,8 +50,8 @@ def _run(cmd, env=None):
 @pytest.mark.skipif(not (os.path.exists(HIPCC) and os.path.exists(CLANG)), reason="ROCm toolchain not present")
 def test_capi_argument_checks_under_asan_ubsan():
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
-    deps = srcs + [os.path.join(CSRC, "common.h"), os.path.join(ROOT, "include", "hrec.h"),
-                   os.path.join(SAN, "capi_checks.cpp")]
+    hdrs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
+    deps = srcs + hdrs + [os.path.join(ROOT, "include", "hrec.h"), os.path.join(SAN, "capi_checks.cpp")]
     tag = _digest(deps, FLAGS)
     bdir = os.path.join(OUT, "capi_" + tag)
     exe = os.path.join(bdir, "capi_checks")
