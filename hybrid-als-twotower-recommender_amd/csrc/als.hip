@@ -5,6 +5,9 @@
 // Per destination row r (one wave per row):
 //   A = sum_j v_j v_j^T  (f64),  b = sum_j r_j v_j (f64),  n = #ratings
 //   A[d][d] += reg * n, solve A x = b (Cholesky, f64), store f32.
+// Implicit feedback (IMP, Spark's implicitPrefs branch), c1_j = alpha |r_j|:
+//   A = YtY + sum_j c1_j v_j v_j^T,  b = sum_{r_j > 0} (1 + c1_j) v_j,
+//   A[d][d] += reg * #{r_j > 0}  (YtY: csrc/als_gramian.hip).
 //
 // Gramian on the matrix cores: v_mfma_f64_16x16x4_f64 with the 4 nnz of a
 // step as the K dimension. Each lane loads ONE 16-B vector (NT floats) of a
@@ -246,18 +249,28 @@ struct NoHook {
 // `before_lds` runs once the row's Gramian is in registers, before the first
 // LDS write (b, MODE 1 re-layout) — a no-op in the product kernel (the
 // producer/consumer splits that waited there measured slower).
-template <int NT, int CH, int MODE, typename Hook = NoHook, bool S64 = false>
+// IMP: the A-side MFMA operand of a step carries the rating's confidence
+// weight c1 = alpha |r| (the K index of both operands is the step's nnz, so
+// the products are c1 v v^T), the rhs weight is 1 + c1 for r > 0 and 0
+// otherwise, n_pos = #{r > 0} replaces n on the diagonal and YtY is added to
+// the tiles before the factorisation. *npos receives n_pos (wave-uniform).
+// Implicit rows take the chunked gather loop at every kp (the ring pipeline
+// of kp = 64 is left to the explicit kernels, whose code must not change).
+template <int NT, int CH, int MODE, typename Hook = NoHook, bool S64 = false, bool IMP = false>
 __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, const int32_t* __restrict__ indices,
                                          const float* __restrict__ values, const float* __restrict__ src,
                                          int64_t n_src, int k, double reg, d4 (&acc)[NT * (NT + 1) / 2],
                                          double* __restrict__ bsh, double* __restrict__ stage,
-                                         Hook before_lds = Hook()) {
+                                         Hook before_lds = Hook(), double alpha = 0.0,
+                                         const double* __restrict__ yty = nullptr, int* npos = nullptr) {
+  static_assert(!IMP || (MODE == 0 && !S64), "implicit feedback: f64 accumulation of f32 sources only");
   constexpr int KP = 16 * NT;
   constexpr int NPAIR = NT * (NT + 1) / 2;
   constexpr int CHN = 4 * CH;  // nnz per chunk (<= 64)
   const int sub = lane >> 4;  // which nnz of the step this lane loads
   const int col = lane & 15;  // which NT-column group
   const int64_t n = end - beg;
+  int n_pos = 0;  // IMP: ratings > 0 (one ballot per window / chunk of ratings)
 
   STAMP_DECL;
   STAMP(0);
@@ -299,7 +312,7 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
 
   // PIPE for kp = 64 (at kp <= 32 the scheduler hoists the unrolled window
   // into a spill; those sizes keep the chunked loop)
-  if constexpr (HREC_ALS_PIPE && NT == 4) {
+  if constexpr (HREC_ALS_PIPE && NT == 4 && !IMP) {
   // Ring pipeline over WINDOWS of 16 steps (64 nnz: one index and one rating
   // per lane). Step s's gather is issued PF steps ahead into ring slot
   // s % PF; the index reaches the lane group by ds_bpermute and feeds a
@@ -594,6 +607,7 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
     int i2;
     float r2;
     load_iv(base + 2 * CHN, i2, r2);
+    if constexpr (IMP) n_pos += __builtin_popcountll(__ballot(r0 > 0.f));
     if (MODE == 1) {
 #pragma unroll
       for (int p = 0; p < NPAIR; ++p) fa[p] = f4{0.f, 0.f, 0.f, 0.f};
@@ -604,20 +618,31 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
       double a[NT];
 #pragma unroll
       for (int t = 0; t < NT; ++t) a[t] = (double)buf[s].x[t];
+      double aw[NT], bw = rv;
+      if constexpr (IMP) {
+        const double c1 = alpha * fabs(rv);
+        bw = rv > 0.0 ? 1.0 + c1 : 0.0;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) aw[t] = c1 * a[t];
+      }
+      auto lhs = [&](int t) -> double {
+        if constexpr (IMP) return aw[t];
+        else return a[t];
+      };
       int p = 0;
 #pragma unroll
       for (int I = 0; I < NT; ++I) {
 #pragma unroll
         for (int J = I; J < NT; ++J) {
           if (MODE == 0)
-            acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[I], a[J], acc[p], 0, 0, 0);
+            acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(lhs(I), a[J], acc[p], 0, 0, 0);
           else
             fa[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(buf[s].x[I], buf[s].x[J], fa[p], 0, 0, 0);
           ++p;
         }
       }
 #pragma unroll
-      for (int t = 0; t < NT; ++t) bp[t] = fma(rv, a[t], bp[t]);
+      for (int t = 0; t < NT; ++t) bp[t] = fma(bw, a[t], bp[t]);
     }
     if (MODE == 1) {
 #pragma unroll
@@ -673,8 +698,22 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
     }
   }
   STAMP(2);  // phase 2: b + layout
+  if constexpr (IMP) {
+    // + YtY: tile (I, J) register rr holds G[NT * (sub + 4 rr) + I][NT * col + J]
+    int p = 0;
+#pragma unroll
+    for (int I = 0; I < NT; ++I) {
+#pragma unroll
+      for (int J = I; J < NT; ++J) {
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) acc[p][rr] += yty[(NT * (sub + 4 * rr) + I) * KP + NT * col + J];
+        ++p;
+      }
+    }
+    *npos = n_pos;
+  }
   // lambda = numExplicits * regParam on the diagonal (1.0 on padding columns)
-  const double lambda = (double)n * reg;
+  const double lambda = (double)(IMP ? (int64_t)n_pos : n) * reg;
   {
     int p = 0;
 #pragma unroll
@@ -876,11 +915,12 @@ __device__ __forceinline__ void factor_row(int lane, d4 (&acc)[NT * (NT + 1) / 2
 }
 
 
-template <int NT, int CH, int MODE, bool S64 = false>
+template <int NT, int CH, int MODE, bool S64 = false, bool IMP = false>
 __device__ __forceinline__ void als_row(int64_t row, int lane, const int64_t* __restrict__ indptr,
                                         const int32_t* __restrict__ indices, const float* __restrict__ values,
                                         const float* __restrict__ src, int64_t n_src, int k, double reg,
-                                        float* __restrict__ dst, double* __restrict__ lds) {
+                                        float* __restrict__ dst, double* __restrict__ lds, double alpha = 0.0,
+                                        const double* __restrict__ yty = nullptr) {
   constexpr int KP = 16 * NT;
   const int64_t beg = indptr[row];
   const int64_t end = indptr[row + 1];
@@ -892,7 +932,17 @@ __device__ __forceinline__ void als_row(int64_t row, int lane, const int64_t* __
   d4 acc[NT * (NT + 1) / 2];
   double* scratch = lds + RowLds<KP>::kUpPad;
   double* bsh = scratch + 128 + 2 * KP;
-  gram_row<NT, CH, MODE, NoHook, S64>(beg, end, lane, indices, values, src, n_src, k, reg, acc, bsh, lds);
+  if constexpr (IMP) {
+    int n_pos = 0;
+    gram_row<NT, CH, MODE, NoHook, S64, true>(beg, end, lane, indices, values, src, n_src, k, reg, acc, bsh, lds,
+                                              NoHook(), alpha, yty, &n_pos);
+    if (n_pos == 0) {  // no rating > 0: b = 0, the factor is exactly zero (wave-uniform)
+      if (lane < KP) out[lane] = 0.f;
+      return;
+    }
+  } else {
+    gram_row<NT, CH, MODE, NoHook, S64>(beg, end, lane, indices, values, src, n_src, k, reg, acc, bsh, lds);
+  }
   factor_row<NT>(lane, acc, lds, scratch, bsh, out);
 }
 
@@ -904,6 +954,18 @@ __global__ __launch_bounds__(64, HREC_ALS_WAVES) void als_half_sweep_f64_kernel(
     int k, double reg, float* __restrict__ dst) {
   __shared__ __attribute__((aligned(16))) double lds[RowLds<16 * NT>::kSize];
   als_row<NT, CH, MODE, S64>(blockIdx.x, threadIdx.x, indptr, indices, values, src, n_src, k, reg, dst, lds);
+}
+
+// The implicit-feedback half-sweep: the same row pipeline with the confidence
+// weights and the source Gramian yty[KP][KP] (row-major f64).
+template <int NT, int CH>
+__global__ __launch_bounds__(64, HREC_ALS_WAVES) void als_half_sweep_implicit_kernel(
+    const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+    const float* __restrict__ values, int64_t n_rows, const float* __restrict__ src, int64_t n_src,
+    int k, double reg, double alpha, const double* __restrict__ yty, float* __restrict__ dst) {
+  __shared__ __attribute__((aligned(16))) double lds[RowLds<16 * NT>::kSize];
+  als_row<NT, CH, 0, false, true>(blockIdx.x, threadIdx.x, indptr, indices, values, src, n_src, k, reg, dst, lds,
+                                  alpha, yty);
 }
 
 __global__ __launch_bounds__(256) void f32_to_f64_kernel(const float* __restrict__ in, int64_t n,
@@ -974,6 +1036,37 @@ extern "C" int hrec_als_half_sweep(const int64_t* indptr, const int32_t* indices
   }
 #undef HREC_SWEEP
   return check_launch("als_half_sweep_f64_kernel");
+}
+
+extern "C" int hrec_als_half_sweep_implicit(const int64_t* indptr, const int32_t* indices, const float* values,
+                                            int64_t n_rows, const float* src_factors, int64_t n_src, int k, int kp,
+                                            double reg_param, double alpha, const double* yty, float* dst_factors,
+                                            void* stream) {
+  HREC_REQUIRE(kp == 16 || kp == 32 || kp == 64,
+               "als_half_sweep_implicit: kp must be 16, 32 or 64 (implicit feedback supports rank <= 64; got kp %d)",
+               kp);
+  HREC_REQUIRE(k >= 1 && k <= kp, "als_half_sweep_implicit: need 1 <= k <= kp (k=%d kp=%d)", k, kp);
+  HREC_REQUIRE(n_rows >= 0 && n_src >= 0, "als_half_sweep_implicit: negative size");
+  HREC_REQUIRE(n_rows < 0x7fffffffll && n_src < 0x7fffffffll, "als_half_sweep_implicit: too many rows for one launch");
+  HREC_REQUIRE(alpha >= 0.0, "als_half_sweep_implicit: alpha must be >= 0 (got %g)", alpha);
+  HREC_REQUIRE(reg_param >= 0.0, "als_half_sweep_implicit: reg_param must be >= 0");
+  HREC_REQUIRE(kp != 64 || n_src * (int64_t)kp * 4 <= (int64_t)0xffffffffll,
+               "als_half_sweep_implicit: %lld source rows of %d floats exceed the 4 GiB a gather resource spans; "
+               "shard the source side", (long long)n_src, kp);
+  if (n_rows == 0) return HREC_OK;
+  HREC_REQUIRE(indptr && dst_factors && yty, "als_half_sweep_implicit: null pointer");
+  HREC_REQUIRE(n_src > 0 && src_factors && indices && values,
+               "als_half_sweep_implicit: null source factors / CSR arrays");
+  hipStream_t s = as_stream(stream);
+  const dim3 grid((unsigned)n_rows), block(64);
+#define HREC_SWEEP(NT, CH)                                                                                  \
+  hipLaunchKernelGGL((als_half_sweep_implicit_kernel<NT, CH>), grid, block, 0, s, indptr, indices, values, \
+                     n_rows, src_factors, n_src, k, reg_param, alpha, yty, dst_factors)
+  if (kp == 64) HREC_SWEEP(4, HREC_ALS_CH0);
+  else if (kp == 32) HREC_SWEEP(2, 8);
+  else HREC_SWEEP(1, 8);
+#undef HREC_SWEEP
+  return check_launch("als_half_sweep_implicit_kernel");
 }
 
 extern "C" int hrec_f32_to_f64(const float* in, int64_t n, double* out, void* stream) {

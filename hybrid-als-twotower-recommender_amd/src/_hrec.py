@@ -42,6 +42,10 @@ _SIGNATURES = {
     "hrec_als_init_factors": (_c_i32, [_c_u64, _c_i64, _c_i64, _c_i32, _c_i32, _vp, _vp]),
     "hrec_als_half_sweep_src64": (_c_i32, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i32, _c_i32, _c_dbl, _vp, _vp]),
     "hrec_f32_to_f64": (_c_i32, [_vp, _c_i64, _vp, _vp]),
+    "hrec_als_gramian_workspace_bytes": (_c_sz, [_c_i64, _c_i32]),
+    "hrec_als_gramian": (_c_i32, [_vp, _c_i64, _c_i32, _c_i32, _vp, _vp, _c_sz, _vp]),
+    "hrec_als_half_sweep_implicit": (_c_i32, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i32, _c_i32, _c_dbl, _c_dbl,
+                                              _vp, _vp, _vp]),
     "hrec_als_half_sweep": (_c_i32, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i32, _c_i32, _c_dbl,
                                      _c_i32, _vp, _vp]),
     "hrec_transpose_f32": (_c_i32, [_vp, _c_i64, _c_i64, _vp, _c_i64, _vp]),
@@ -371,6 +375,35 @@ def als_half_sweep(indptr, indices, values, src_factors, k, reg_param, dst_facto
         _dev(src_factors, torch.float32, "src_factors"), src_factors.shape[0], k, kp,
         float(reg_param), int(accum_mode), _dev(dst_factors, torch.float32, "dst_factors"),
         _stream()))
+
+
+def als_gramian(src_factors, k):
+    """YtY of the implicit-feedback half-sweep (hrec_als_gramian): f64
+    [kp, kp] = sum over the rows of src_factors [n_src, kp] f32 of y y^T;
+    rows and columns >= k are zero. The same bits for the same buffer."""
+    n_src, kp = src_factors.shape
+    dev = src_factors.device
+    out = torch.empty((kp, kp), dtype=torch.float64, device=dev)
+    need = int(lib().hrec_als_gramian_workspace_bytes(n_src, kp))
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    _check("hrec_als_gramian", lib().hrec_als_gramian(
+        _dev(src_factors, torch.float32, "src_factors"), n_src, int(k), kp, _dev(out, torch.float64, "yty"),
+        _dev(ws, torch.uint8, "ws"), ws.numel(), _stream()))
+    return out
+
+
+def als_half_sweep_implicit(indptr, indices, values, src_factors, k, reg_param, alpha, yty, dst_factors):
+    """The implicit-feedback half-sweep (hrec_als_half_sweep_implicit): yty =
+    als_gramian(src_factors, k); kp 16, 32 or 64."""
+    n_rows = indptr.numel() - 1
+    kp = dst_factors.shape[1]
+    if src_factors.shape[1] != kp or dst_factors.shape[0] < n_rows or tuple(yty.shape) != (kp, kp):
+        raise HrecError("als_half_sweep_implicit: factor / Gramian shapes do not match")
+    _check("hrec_als_half_sweep_implicit", lib().hrec_als_half_sweep_implicit(
+        _dev(indptr, torch.int64, "indptr"), _dev(indices, torch.int32, "indices"),
+        _dev(values, torch.float32, "values"), n_rows, _dev(src_factors, torch.float32, "src_factors"),
+        src_factors.shape[0], int(k), kp, float(reg_param), float(alpha), _dev(yty, torch.float64, "yty"),
+        _dev(dst_factors, torch.float32, "dst_factors"), _stream()))
 
 
 def f32_to_f64(x, out=None):

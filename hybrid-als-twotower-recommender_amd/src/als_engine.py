@@ -167,8 +167,15 @@ class DeviceALS:
 
     def __init__(self, n_users, n_items, rank_k, reg_param, user_csr: DeviceCSR,
                  item_csc: DeviceCSR, world=1, rank=0, group=None, accum_mode=0, sweep=None, chunks=1,
-                 item_chunks=1, user_layout=None, item_layout=None, remap=None):
-        """user_layout / item_layout (RowLayout): the shards' row layout;
+                 item_chunks=1, user_layout=None, item_layout=None, remap=None, implicit=False, alpha=1.0,
+                 gramian=None):
+        """implicit / alpha: Spark's implicitPrefs objective with confidence
+        weight alpha (rank <= 64, accum_mode 0): each half-sweep computes YtY
+        once from the whole replicated source buffer (gramian, default
+        hrec_als_gramian; injectable like sweep) and hands it to every chunk
+        launch; sweep then takes (indptr, indices, values, src, k, reg,
+        alpha, yty, dst).
+        user_layout / item_layout (RowLayout): the shards' row layout;
         default RowLayout.equal(n, world, chunks). With a non-identity layout
         the shards are this rank's parts padded to cs rows each (see
         synthetic.generate_layout) with GLOBAL column ids; they are remapped
@@ -183,11 +190,20 @@ class DeviceALS:
         self.accum_mode = int(accum_mode)
         # the half-sweep launcher (K1); tests inject the CPU oracle here to
         # exercise the sharding/all-gather logic on gloo without a GPU
-        self.sweep = sweep or _hrec.als_half_sweep
+        self.implicit, self.alpha = bool(implicit), float(alpha)
+        if self.implicit:
+            if self.kp > 64:
+                raise ValueError(f"implicit feedback supports rank <= 64 (got rank {self.k})")
+            if self.accum_mode != 0:
+                raise ValueError("implicit feedback supports accum_mode 0 (f64 accumulation) only")
+            if not self.alpha >= 0.0:
+                raise ValueError(f"implicit feedback needs alpha >= 0 (got {alpha})")
+        self.sweep = sweep or (_hrec.als_half_sweep_implicit if self.implicit else _hrec.als_half_sweep)
+        self.gramian = gramian or _hrec.als_gramian
         # f64 copies of sources that stay in the on-chip caches (the device
         # sweep only): hrec_als_half_sweep_src64, same results, no per-row
-        # conversion in the gather
-        self._src64_ok = sweep is None and self.kp == 64 and self.accum_mode == 0
+        # conversion in the gather (explicit feedback only)
+        self._src64_ok = sweep is None and self.kp == 64 and self.accum_mode == 0 and not self.implicit
         self._s64 = None
         dev = user_csr.indptr.device
         self.u_per = user_csr.n_rows
@@ -266,20 +282,30 @@ class DeviceALS:
         out = self._s64[: src.numel()].view(src.shape)
         return _hrec.f32_to_f64(src, out)
 
-    def _sweep(self, csr, src, local, full, cs, chunks):
-        """One half-sweep of this rank's rows + replication of the result."""
+    def _launcher(self, src):
+        """launch(indptr, indices, values, dst) of one half-sweep from `src`:
+        the per-half-sweep operands (the f64 source copy; implicit feedback:
+        YtY of the whole replicated source buffer) are formed once here and
+        shared by every chunk launch."""
+        if self.implicit:
+            yty = self.gramian(src, self.k)
+            return lambda ip, ix, v, dst: self.sweep(ip, ix, v, src, self.k, self.reg, self.alpha, yty, dst)
         s64 = self._src64(src)
         extra = {} if s64 is None else {"src64": s64}
+        return lambda ip, ix, v, dst: self.sweep(ip, ix, v, src, self.k, self.reg, dst, self.accum_mode, **extra)
+
+    def _sweep(self, csr, src, local, full, cs, chunks):
+        """One half-sweep of this rank's rows + replication of the result."""
+        launch = self._launcher(src)
         if chunks == 1:
-            self.sweep(csr.indptr, csr.indices, csr.values, src, self.k, self.reg, local, self.accum_mode, **extra)
+            launch(csr.indptr, csr.indices, csr.values, local)
             self._gather(full, local)
             return
         W = self.world
         compute = torch.cuda.current_stream() if self.comm is not None else None
         for c in range(chunks):
             rows = slice(c * cs, (c + 1) * cs)
-            self.sweep(csr.indptr[c * cs: (c + 1) * cs + 1], csr.indices, csr.values, src, self.k, self.reg,
-                       local[rows], self.accum_mode, **extra)
+            launch(csr.indptr[c * cs: (c + 1) * cs + 1], csr.indices, csr.values, local[rows])
             out = full[c * W * cs: (c + 1) * W * cs]
             if self.comm is None:
                 dist.all_gather_into_tensor(out, local[rows], group=self.group)
@@ -305,11 +331,9 @@ class DeviceALS:
         (bench.py: epoch time minus this = collective time not hidden)."""
         for csr, src, local, cs, chunks in ((self.item_csc, self.U, self.V_local, self.i_cs, self.i_chunks),
                                             (self.user_csr, self.V, self.U_local, self.u_cs, self.u_chunks)):
-            s64 = self._src64(src)
-            extra = {} if s64 is None else {"src64": s64}
+            launch = self._launcher(src)
             for c in range(chunks):
-                self.sweep(csr.indptr[c * cs: (c + 1) * cs + 1], csr.indices, csr.values, src, self.k, self.reg,
-                           local[c * cs: (c + 1) * cs], self.accum_mode, **extra)
+                launch(csr.indptr[c * cs: (c + 1) * cs + 1], csr.indices, csr.values, local[c * cs: (c + 1) * cs])
 
     def epoch(self):
         """One Spark iteration: items from users, then users from items."""

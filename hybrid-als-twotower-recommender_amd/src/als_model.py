@@ -12,7 +12,11 @@ ALSModel.transform at :75) is replaced by libhrec's HIP kernels:
                       are split into nnz-balanced row shards, the factors
                       replicated by RCCL all-gathers after each half-sweep,
                       and every rank ends with the full model: the factors
-                      are bit-identical to the one-rank fit)
+                      are bit-identical to the one-rank fit; with
+                      implicit_prefs=True the row layouts permute the
+                      summation order of YtY, so the implicit fit equals the
+                      one-rank fit within the fit tolerance, rtol 1e-4 /
+                      atol 1e-5, not bit for bit)
   predict_for_user -> hrec_als_score (JVM-exact f32 dot, NaN for unknown
                       ids = coldStartStrategy "drop")                [K2]
                       + cold-start fallback via hrec_cosine_sim +
@@ -219,7 +223,13 @@ class ALSModel:
 
     CHUNKS = 4  # W > 1: user-side row chunks per rank (overlapped all-gathers)
 
-    def __init__(self, rank=10, max_iter=10, reg_param=0.1, cold_start_strategy="drop", seed=None):
+    def __init__(self, rank=10, max_iter=10, reg_param=0.1, cold_start_strategy="drop", seed=None,
+                 implicit_prefs=False, alpha=1.0):
+        """implicit_prefs / alpha: Spark ALS's implicitPrefs and alpha (the
+        confidence 1 + alpha |r| of the implicit-feedback objective); rank
+        <= 64 when set."""
+        self.implicit_prefs = implicit_prefs
+        self.alpha = alpha
         self.rank = rank
         self.max_iter = max_iter
         self.reg_param = reg_param
@@ -267,6 +277,13 @@ class ALSModel:
         items_h = _int_ids(data["itemId"], "itemId")
         ratings_h = np.asarray(data["average_review_rating"], dtype=np.float32)
         k = int(self.rank)
+        imp = {}
+        if self.implicit_prefs:
+            if padded_k(k) > 64:
+                raise ValueError(f"implicit_prefs=True supports rank <= 64 (got rank {k})")
+            if not float(self.alpha) >= 0.0:
+                raise ValueError(f"alpha must be >= 0 (got {self.alpha})")
+            imp = {"implicit": True, "alpha": float(self.alpha)}
         world, rank, group = process_group()
         track = dev.type == "cuda"
         if track:  # the ingest's peak device memory (tests: W = 2 holds about half of W = 1)
@@ -299,9 +316,9 @@ class ALSModel:
             self.ingest_peak_bytes = int(torch.cuda.max_memory_allocated(dev) - base)
         if world > 1:
             eng = DeviceALS(n_u, n_i, k, float(self.reg_param), csr, csc, world=world, rank=rank, group=group,
-                            chunks=self.CHUNKS, item_chunks=1, user_layout=ulay, item_layout=ilay)
+                            chunks=self.CHUNKS, item_chunks=1, user_layout=ulay, item_layout=ilay, **imp)
         else:
-            eng = DeviceALS(n_u, n_i, k, float(self.reg_param), csr, csc)
+            eng = DeviceALS(n_u, n_i, k, float(self.reg_param), csr, csc, **imp)
         if U0 is not None:
             eng.set_user_factors(U0)
         else:
@@ -585,6 +602,8 @@ class ALSModel:
                 "reg_param": self.reg_param,
                 "global_mean": self.global_mean,
                 "item_features": self.item_features,
+                "implicit_prefs": bool(self.implicit_prefs),
+                "alpha": float(self.alpha),
             }
             with open(f"{model_path}_metadata.pkl", "wb") as f:
                 pickle.dump(metadata, f)
@@ -604,6 +623,8 @@ class ALSModel:
                 self.reg_param = metadata["reg_param"]
                 self.global_mean = metadata["global_mean"]
                 self.item_features = metadata["item_features"]
+                self.implicit_prefs = metadata.get("implicit_prefs", False)  # absent in older pickles
+                self.alpha = metadata.get("alpha", 1.0)
             return self
         except Exception as e:
             print(f"Loading error: {str(e)}")

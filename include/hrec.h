@@ -178,6 +178,35 @@ int hrec_als_half_sweep_src64(const int64_t* indptr, const int32_t* indices, con
 /* out[i] = (double)in[i]. */
 int hrec_f32_to_f64(const float* in, int64_t n, double* out, void* stream);
 
+/* Implicit feedback (Spark ALS implicitPrefs = true, confidence weight alpha;
+ * ALS.computeFactors, implicit branch [ext]). Additive to ABI 7.
+ *
+ * hrec_als_gramian: yty[kp*kp] (row-major f64) = sum_s y_s y_s^T over the
+ * n_src rows of src_factors[n_src*kp] (f32, converted to f64) — Spark's
+ * computeYtY. Zero rows contribute nothing; rows and columns >= k are zero.
+ * Slabs of source rows are summed on the f64 matrix cores into per-slab
+ * partials in the workspace and the partials in a fixed order: no atomics,
+ * the same bits for the same buffer on every call, device and rank.
+ * kp = 16, 32 or 64. Workspace: hrec_als_gramian_workspace_bytes(n_src, kp)
+ * (0 for an unsupported kp or a negative n_src). */
+size_t hrec_als_gramian_workspace_bytes(int64_t n_src, int kp);
+int hrec_als_gramian(const float* src_factors, int64_t n_src, int k, int kp,
+                     double* yty, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
+/* One implicit-feedback half-sweep: for every local dst row r with ratings
+ * (j, r_j), v_j = src_factors[indices[j]] in f64 and c1_j = alpha*|r_j|,
+ *   A = yty + sum_j c1_j v_j v_j^T,   b = sum_{j: r_j > 0} (1 + c1_j) v_j,
+ *   A[d][d] += reg_param * #{j: r_j > 0},   A x_r = b  (f64), stored as f32.
+ * yty = hrec_als_gramian of the same src_factors. Rows without ratings and
+ * rows whose ratings are all <= 0 get a zero vector; a rating of 0 adds
+ * nothing; duplicate entries stay separate terms. alpha >= 0; kp = 16, 32
+ * or 64 (rank <= 64), f64 accumulation of f32 sources only. */
+int hrec_als_half_sweep_implicit(const int64_t* indptr, const int32_t* indices, const float* values,
+                                 int64_t n_rows, const float* src_factors, int64_t n_src, int k, int kp,
+                                 double reg_param, double alpha, const double* yty, float* dst_factors,
+                                 void* stream);
+
 /* out[c*ld_out + r] = in[r*cols + c] (f32), ld_out >= rows. */
 int hrec_transpose_f32(const float* in, int64_t rows, int64_t cols, float* out,
                        int64_t ld_out, void* stream);
