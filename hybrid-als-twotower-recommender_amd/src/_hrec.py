@@ -46,6 +46,8 @@ _SIGNATURES = {
     "hrec_als_gramian": (_c_i32, [_vp, _c_i64, _c_i32, _c_i32, _vp, _vp, _c_sz, _vp]),
     "hrec_als_half_sweep_implicit": (_c_i32, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i32, _c_i32, _c_dbl, _c_dbl,
                                               _vp, _vp, _vp]),
+    "hrec_als_half_sweep_nonneg": (_c_i32, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i32, _c_i32, _c_dbl, _c_i32,
+                                            _c_dbl, _vp, _vp, _vp, _vp]),
     "hrec_als_half_sweep": (_c_i32, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i32, _c_i32, _c_dbl,
                                      _c_i32, _vp, _vp]),
     "hrec_transpose_f32": (_c_i32, [_vp, _c_i64, _c_i64, _vp, _c_i64, _vp]),
@@ -404,6 +406,29 @@ def als_half_sweep_implicit(indptr, indices, values, src_factors, k, reg_param, 
         _dev(values, torch.float32, "values"), n_rows, _dev(src_factors, torch.float32, "src_factors"),
         src_factors.shape[0], int(k), kp, float(reg_param), float(alpha), _dev(yty, torch.float64, "yty"),
         _dev(dst_factors, torch.float32, "dst_factors"), _stream()))
+
+
+def als_half_sweep_nonneg(indptr, indices, values, src_factors, k, reg_param, dst_factors, implicit=False, alpha=0.0,
+                          yty=None, iters=None):
+    """The non-negative half-sweep (hrec_als_half_sweep_nonneg, Spark's
+    nonnegative=True): the explicit normal equations, or with implicit=True
+    the implicit ones (alpha, yty = als_gramian(src_factors, k)), solved by
+    NNLS; kp 16, 32 or 64. iters (optional int32 [>= n_rows]) receives each
+    row's iteration count."""
+    n_rows = indptr.numel() - 1
+    kp = dst_factors.shape[1]
+    if src_factors.shape[1] != kp or dst_factors.shape[0] < n_rows:
+        raise HrecError("als_half_sweep_nonneg: factor shapes do not match")
+    if implicit and (yty is None or tuple(yty.shape) != (kp, kp)):
+        raise HrecError("als_half_sweep_nonneg: implicit=True needs the [kp, kp] Gramian yty")
+    if iters is not None and iters.numel() < n_rows:
+        raise HrecError("als_half_sweep_nonneg: iters is shorter than the rows")
+    _check("hrec_als_half_sweep_nonneg", lib().hrec_als_half_sweep_nonneg(
+        _dev(indptr, torch.int64, "indptr"), _dev(indices, torch.int32, "indices"),
+        _dev(values, torch.float32, "values"), n_rows, _dev(src_factors, torch.float32, "src_factors"),
+        src_factors.shape[0], int(k), kp, float(reg_param), 1 if implicit else 0, float(alpha),
+        _dev(yty, torch.float64, "yty") if implicit else None, _dev(dst_factors, torch.float32, "dst_factors"),
+        _dev(iters, torch.int32, "iters"), _stream()))
 
 
 def f32_to_f64(x, out=None):

@@ -168,13 +168,17 @@ class DeviceALS:
     def __init__(self, n_users, n_items, rank_k, reg_param, user_csr: DeviceCSR,
                  item_csc: DeviceCSR, world=1, rank=0, group=None, accum_mode=0, sweep=None, chunks=1,
                  item_chunks=1, user_layout=None, item_layout=None, remap=None, implicit=False, alpha=1.0,
-                 gramian=None):
+                 gramian=None, nonnegative=False):
         """implicit / alpha: Spark's implicitPrefs objective with confidence
         weight alpha (rank <= 64, accum_mode 0): each half-sweep computes YtY
         once from the whole replicated source buffer (gramian, default
         hrec_als_gramian; injectable like sweep) and hands it to every chunk
         launch; sweep then takes (indptr, indices, values, src, k, reg,
         alpha, yty, dst).
+        nonnegative: Spark's nonnegative=True — every row is solved by NNLS
+        (hrec_als_half_sweep_nonneg) in place of Cholesky (rank <= 64,
+        accum_mode 0); combines with implicit. sweep then takes (indptr,
+        indices, values, src, k, reg, dst, implicit=, alpha=, yty=).
         user_layout / item_layout (RowLayout): the shards' row layout;
         default RowLayout.equal(n, world, chunks). With a non-identity layout
         the shards are this rank's parts padded to cs rows each (see
@@ -198,12 +202,20 @@ class DeviceALS:
                 raise ValueError("implicit feedback supports accum_mode 0 (f64 accumulation) only")
             if not self.alpha >= 0.0:
                 raise ValueError(f"implicit feedback needs alpha >= 0 (got {alpha})")
-        self.sweep = sweep or (_hrec.als_half_sweep_implicit if self.implicit else _hrec.als_half_sweep)
+        self.nonnegative = bool(nonnegative)
+        if self.nonnegative:
+            if self.kp > 64:
+                raise ValueError(f"nonnegative supports rank <= 64 (got rank {self.k})")
+            if self.accum_mode != 0:
+                raise ValueError("nonnegative supports accum_mode 0 (f64 accumulation) only")
+        self.sweep = sweep or (_hrec.als_half_sweep_nonneg if self.nonnegative else
+                               _hrec.als_half_sweep_implicit if self.implicit else _hrec.als_half_sweep)
         self.gramian = gramian or _hrec.als_gramian
         # f64 copies of sources that stay in the on-chip caches (the device
         # sweep only): hrec_als_half_sweep_src64, same results, no per-row
         # conversion in the gather (explicit feedback only)
-        self._src64_ok = sweep is None and self.kp == 64 and self.accum_mode == 0 and not self.implicit
+        self._src64_ok = sweep is None and self.kp == 64 and self.accum_mode == 0 and not self.implicit and \
+            not self.nonnegative
         self._s64 = None
         dev = user_csr.indptr.device
         self.u_per = user_csr.n_rows
@@ -287,6 +299,10 @@ class DeviceALS:
         the per-half-sweep operands (the f64 source copy; implicit feedback:
         YtY of the whole replicated source buffer) are formed once here and
         shared by every chunk launch."""
+        if self.nonnegative:
+            yty = self.gramian(src, self.k) if self.implicit else None
+            return lambda ip, ix, v, dst: self.sweep(ip, ix, v, src, self.k, self.reg, dst, implicit=self.implicit,
+                                                     alpha=self.alpha if self.implicit else 0.0, yty=yty)
         if self.implicit:
             yty = self.gramian(src, self.k)
             return lambda ip, ix, v, dst: self.sweep(ip, ix, v, src, self.k, self.reg, self.alpha, yty, dst)

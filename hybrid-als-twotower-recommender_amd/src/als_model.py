@@ -16,7 +16,10 @@ ALSModel.transform at :75) is replaced by libhrec's HIP kernels:
                       implicit_prefs=True the row layouts permute the
                       summation order of YtY, so the implicit fit equals the
                       one-rank fit within the fit tolerance, rtol 1e-4 /
-                      atol 1e-5, not bit for bit)
+                      atol 1e-5, not bit for bit; nonnegative=True solves
+                      every row by Spark's NNLS instead of Cholesky
+                      (hrec_als_half_sweep_nonneg): explicit still
+                      bit-identical, implicit within the fit tolerance)
   predict_for_user -> hrec_als_score (JVM-exact f32 dot, NaN for unknown
                       ids = coldStartStrategy "drop")                [K2]
                       + cold-start fallback via hrec_cosine_sim +
@@ -224,10 +227,12 @@ class ALSModel:
     CHUNKS = 4  # W > 1: user-side row chunks per rank (overlapped all-gathers)
 
     def __init__(self, rank=10, max_iter=10, reg_param=0.1, cold_start_strategy="drop", seed=None,
-                 implicit_prefs=False, alpha=1.0):
+                 implicit_prefs=False, alpha=1.0, nonnegative=False):
         """implicit_prefs / alpha: Spark ALS's implicitPrefs and alpha (the
         confidence 1 + alpha |r| of the implicit-feedback objective); rank
-        <= 64 when set."""
+        <= 64 when set. nonnegative: Spark ALS's nonnegative (every factor
+        row solved by NNLS, so all factors are >= 0); rank <= 64 when set."""
+        self.nonnegative = nonnegative
         self.implicit_prefs = implicit_prefs
         self.alpha = alpha
         self.rank = rank
@@ -284,6 +289,10 @@ class ALSModel:
             if not float(self.alpha) >= 0.0:
                 raise ValueError(f"alpha must be >= 0 (got {self.alpha})")
             imp = {"implicit": True, "alpha": float(self.alpha)}
+        if self.nonnegative:
+            if padded_k(k) > 64:
+                raise ValueError(f"nonnegative=True supports rank <= 64 (got rank {k})")
+            imp["nonnegative"] = True
         world, rank, group = process_group()
         track = dev.type == "cuda"
         if track:  # the ingest's peak device memory (tests: W = 2 holds about half of W = 1)
@@ -604,6 +613,7 @@ class ALSModel:
                 "item_features": self.item_features,
                 "implicit_prefs": bool(self.implicit_prefs),
                 "alpha": float(self.alpha),
+                "nonnegative": bool(self.nonnegative),
             }
             with open(f"{model_path}_metadata.pkl", "wb") as f:
                 pickle.dump(metadata, f)
@@ -625,6 +635,7 @@ class ALSModel:
                 self.item_features = metadata["item_features"]
                 self.implicit_prefs = metadata.get("implicit_prefs", False)  # absent in older pickles
                 self.alpha = metadata.get("alpha", 1.0)
+                self.nonnegative = metadata.get("nonnegative", False)
             return self
         except Exception as e:
             print(f"Loading error: {str(e)}")

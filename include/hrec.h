@@ -207,6 +207,26 @@ int hrec_als_half_sweep_implicit(const int64_t* indptr, const int32_t* indices, 
                                  double reg_param, double alpha, const double* yty, float* dst_factors,
                                  void* stream);
 
+/* One non-negative half-sweep (Spark ALS nonnegative = true: NNLSSolver in
+ * place of CholeskySolver [ext]). Additive to ABI 7. The normal equations of
+ * every local dst row are those of hrec_als_half_sweep (implicit = 0: A =
+ * sum_j v_j v_j^T + reg_param*n*I, b = sum_j r_j v_j) or of
+ * hrec_als_half_sweep_implicit (implicit = 1, with alpha and yty =
+ * hrec_als_gramian of the same src_factors); the row is then
+ *   argmin_{x >= 0} x^T A x / 2 - b^T x
+ * by Spark's mllib NNLS.solve: projected gradients with conjugate-gradient
+ * directions from x = 0 in f64, at most max(400, 20 k) iterations, stored as
+ * f32. Every entry is >= 0; padding columns are 0. Rows without ratings
+ * (implicit: without a rating > 0) get a zero vector. yty must be non-null
+ * when implicit is 1 and is ignored otherwise. iters_out: NULL, or
+ * int32[n_rows] that receives each row's iteration count (0 for skipped
+ * rows). alpha >= 0; kp = 16, 32 or 64 (rank <= 64), f64 accumulation of f32
+ * sources only. */
+int hrec_als_half_sweep_nonneg(const int64_t* indptr, const int32_t* indices, const float* values,
+                               int64_t n_rows, const float* src_factors, int64_t n_src, int k, int kp,
+                               double reg_param, int implicit, double alpha, const double* yty,
+                               float* dst_factors, int32_t* iters_out, void* stream);
+
 /* out[c*ld_out + r] = in[r*cols + c] (f32), ld_out >= rows. */
 int hrec_transpose_f32(const float* in, int64_t rows, int64_t cols, float* out,
                        int64_t ld_out, void* stream);
