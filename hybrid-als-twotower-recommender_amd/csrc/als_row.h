@@ -56,6 +56,16 @@
 #ifndef HREC_ALS_PR
 #define HREC_ALS_PR 2  // DIAG4 = 3: prefetch distance of the rotated loads (steps)
 #endif
+// The pooled kernel (3 waves per SIMD, <= 168 VGPRs) takes its own gather knobs.
+#ifndef HREC_ALS_POOL_PF
+#define HREC_ALS_POOL_PF 8  // as HREC_ALS_PF
+#endif
+#ifndef HREC_ALS_POOL_PF64
+#define HREC_ALS_POOL_PF64 4  // as HREC_ALS_PF64
+#endif
+#ifndef HREC_ALS_POOL_ROT1DPP64
+#define HREC_ALS_POOL_ROT1DPP64 1  // as HREC_ALS_ROT1DPP64; 0 keeps 16 more VGPRs of rotated loads in flight and spills in the step loop
+#endif
 
 namespace hrec {
 
@@ -242,13 +252,21 @@ struct NoHook {
 // the tiles before the factorisation. *npos receives n_pos (wave-uniform).
 // Implicit rows take the chunked gather loop at every kp (the ring pipeline
 // of kp = 64 is left to the explicit kernels, whose code must not change).
-template <int NT, int CH, int MODE, typename Hook = NoHook, bool S64 = false, bool IMP = false>
+// `acquire` (pooled kernel only): called once the ring loop is done, before
+// the first LDS write of the row (the DIAG4 staging); returns the wave's LDS
+// slice, which replaces stage / bsh. The default takes both as passed.
+template <int NT, int CH, int MODE, typename Hook = NoHook, bool S64 = false, bool IMP = false,
+          bool POOLED = false, typename Acq = NoHook>
 __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, const int32_t* __restrict__ indices,
                                          const float* __restrict__ values, const float* __restrict__ src,
                                          int64_t n_src, int k, double reg, d4 (&acc)[NT * (NT + 1) / 2],
                                          double* __restrict__ bsh, double* __restrict__ stage,
                                          Hook before_lds = Hook(), double alpha = 0.0,
-                                         const double* __restrict__ yty = nullptr, int* npos = nullptr) {
+                                         const double* __restrict__ yty = nullptr, int* npos = nullptr,
+                                         Acq acquire = Acq()) {
+  constexpr bool kAcq = !std::is_same_v<Acq, NoHook>;
+  static_assert(!kAcq || (HREC_ALS_PIPE && NT == 4 && !IMP && HREC_ALS_ABLATE != 4),
+                "late slice acquisition: the kp-64 ring pipeline only");
   static_assert(!IMP || (MODE == 0 && !S64), "implicit feedback: f64 accumulation of f32 sources only");
   constexpr int KP = 16 * NT;
   constexpr int NPAIR = NT * (NT + 1) / 2;
@@ -306,7 +324,8 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
   // voffset = this lane's 16-B column slice). Padding entries carry index -1:
   // the buffer range check returns zeros for them, so the loop has no
   // branches, masks or address arithmetic on the VALU.
-  constexpr int PF = S64 ? HREC_ALS_PF64 : HREC_ALS_PF;  // f64 sources sit in the MALL: shorter distance
+  // f64 sources sit in the MALL: shorter distance
+  constexpr int PF = POOLED ? (S64 ? HREC_ALS_POOL_PF64 : HREC_ALS_POOL_PF) : (S64 ? HREC_ALS_PF64 : HREC_ALS_PF);
   static_assert(16 % PF == 0, "prefetch distance must divide the window");
   static_assert(!S64 || (NT == 4 && MODE == 0 && (HREC_ALS_DIAG4 == 0 || HREC_ALS_DIAG4 == 3)),
                 "f64 sources: kp 64, f64 accumulation only");
@@ -358,7 +377,8 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
   constexpr bool kAhead = HREC_ALS_DIAG4 == 2 && MODE == 0;
   constexpr bool kMemRot = HREC_ALS_DIAG4 == 3 && MODE == 0;
   constexpr int PR = kMemRot ? HREC_ALS_PR : 1;  // rotated-load prefetch distance (steps)
-  constexpr bool kRot1Dpp = kMemRot && (S64 ? HREC_ALS_ROT1DPP64 : HREC_ALS_ROT1DPP);
+  constexpr bool kRot1Dpp =
+      kMemRot && (S64 ? (POOLED ? HREC_ALS_POOL_ROT1DPP64 : HREC_ALS_ROT1DPP64) : HREC_ALS_ROT1DPP);
   static_assert(PR < PF, "rotated loads are issued from the current windows");
   const int voff1 = (S64 ? 8 : 4) * NT * ((col + 4) & 15), voff2 = (S64 ? 8 : 4) * NT * ((col + 8) & 15);
   auto rot_load = [&](int vi, int vo) -> RingT {
@@ -550,6 +570,11 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
     iw1 = iw2;
     rw1 = rw2;
   }
+  if constexpr (kAcq) {
+    double* base = acquire();
+    stage = base;
+    bsh = base + RowLds<KP>::kUpPad + 128 + 2 * KP;
+  }
   if constexpr (kDiag4) {
     // 4x4x4 block C[i][j] of block q sits at lane 16 i + 4 q + j and holds
     // G[4q + i][4((q + s) & 3) + j] for rotation s; write it and its mirror
@@ -716,8 +741,14 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
 // Factor + solve of one row's normal equations on one wave: acc (tile layout,
 // consumed), b in bsh; Ut in Up (KP(KP+1)/2), row buffers and pivots in
 // scratch (128 + 2 KP); x -> out[0..KP).
-template <int NT>
-__device__ __forceinline__ void factor_row(int lane, d4 (&acc)[NT * (NT + 1) / 2], double* __restrict__ Up,
+// LDSG (factor_row_lds): the Gramian leaves the accumulator registers at once
+// — all tiles go to Up, in the layout step (a) writes — and every trailing
+// tile is loaded from Up, updated by the same 4 MFMAs in the same order and
+// stored back (q <= c; the lower halves of diagonal tiles are never read, so
+// what gets loaded for them does not matter). Same operations on the same
+// values as the register form: the same bits, in 80 fewer live VGPRs.
+template <int NT, bool LDSG>
+__device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1) / 2], double* __restrict__ Up,
                                            double* __restrict__ scratch, const double* __restrict__ bsh,
                                            float* __restrict__ out) {
   constexpr int KP = 16 * NT;
@@ -750,16 +781,22 @@ __device__ __forceinline__ void factor_row(int lane, d4 (&acc)[NT * (NT + 1) / 2
   double bs = 0.0;
 #pragma unroll
   for (int J = 0; J < NT; ++J) {
-    // (a) block row J -> LDS (only q <= c: the upper triangle)
+    // (a) block row J -> LDS (only q <= c: the upper triangle); LDSG: every
+    //     block row, once
+    if (!LDSG || J == 0) {
 #pragma unroll
-    for (int K = J; K < NT; ++K) {
+      for (int I = J; I < (LDSG ? NT : J + 1); ++I) {
 #pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int q = 16 * J + sub + 4 * rr, c = 16 * K + col;
-        if (q <= c) Up[tri(c) + q] = acc[pidx(J, K)][rr];
+        for (int K = I; K < NT; ++K) {
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) {
+            const int q = 16 * I + sub + 4 * rr, c = 16 * K + col;
+            if (q <= c) Up[tri(c) + q] = acc[pidx(I, K)][rr];
+          }
+        }
       }
+      wave_lds_sync();
     }
-    wave_lds_sync();
     if (J == 0) bs = lane < KP ? bsh[lane] : 0.0;
     // (b) lane c >= 16J owns column c of block row J
     const int c = lane;
@@ -872,12 +909,29 @@ __device__ __forceinline__ void factor_row(int lane, d4 (&acc)[NT * (NT + 1) / 2
       for (int K = J + 1; K < NT; ++K) {
 #pragma unroll
         for (int M = K; M < NT; ++M) {
+          if constexpr (LDSG) {
+            // q > c of a diagonal tile reads past its column, still inside Up
+            // (tri(c) + q <= tri(KP - 2) + KP - 1 < kUp), and is not stored
+            d4 t;
 #pragma unroll
-          for (int rr = 0; rr < 4; ++rr)
-            acc[pidx(K, M)] = __builtin_amdgcn_mfma_f64_16x16x4f64(-acc[pidx(J, K)][rr], yv[M][rr],
-                                                                    acc[pidx(K, M)], 0, 0, 0);
+            for (int rr = 0; rr < 4; ++rr) t[rr] = Up[tri(16 * M + col) + 16 * K + sub + 4 * rr];
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr)
+              t = __builtin_amdgcn_mfma_f64_16x16x4f64(-acc[pidx(J, K)][rr], yv[M][rr], t, 0, 0, 0);
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+              const int q = 16 * K + sub + 4 * rr, c = 16 * M + col;
+              if (q <= c) Up[tri(c) + q] = t[rr];
+            }
+          } else {
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr)
+              acc[pidx(K, M)] = __builtin_amdgcn_mfma_f64_16x16x4f64(-acc[pidx(J, K)][rr], yv[M][rr],
+                                                                      acc[pidx(K, M)], 0, 0, 0);
+          }
         }
       }
+      if constexpr (LDSG) wave_lds_sync();  // the next panel reads what other lanes stored
     }
   }
   STAMP(3);  // phase 3: factorisation
@@ -898,6 +952,20 @@ __device__ __forceinline__ void factor_row(int lane, d4 (&acc)[NT * (NT + 1) / 2
   STAMP(4);  // phase 4: triangular solves
   if (lane < KP) out[NT * (lane & 15) + (lane >> 4)] = (float)bi;
   wave_lds_sync();  // the next row on this wave reuses the LDS slice
+}
+
+template <int NT>
+__device__ __forceinline__ void factor_row(int lane, d4 (&acc)[NT * (NT + 1) / 2], double* __restrict__ Up,
+                                           double* __restrict__ scratch, const double* __restrict__ bsh,
+                                           float* __restrict__ out) {
+  factor_row_impl<NT, false>(lane, acc, Up, scratch, bsh, out);
+}
+
+template <int NT>
+__device__ __forceinline__ void factor_row_lds(int lane, d4 (&acc)[NT * (NT + 1) / 2], double* __restrict__ Up,
+                                               double* __restrict__ scratch, const double* __restrict__ bsh,
+                                               float* __restrict__ out) {
+  factor_row_impl<NT, true>(lane, acc, Up, scratch, bsh, out);
 }
 
 }  // namespace hrec

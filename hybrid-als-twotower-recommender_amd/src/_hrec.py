@@ -41,6 +41,8 @@ _SIGNATURES = {
     "hrec_coo_to_csr_sorted": (_c_i32, [_vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp]),
     "hrec_als_init_factors": (_c_i32, [_c_u64, _c_i64, _c_i64, _c_i32, _c_i32, _vp, _vp]),
     "hrec_als_half_sweep_src64": (_c_i32, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_i32, _c_i32, _c_dbl, _vp, _vp]),
+    "hrec_als_half_sweep_kernel": (_c_i32, [_vp, _vp, _vp, _c_i64, _vp, _c_i32, _c_i64, _c_i32, _c_i32, _c_dbl, _c_i32,
+                                            _vp, _vp]),
     "hrec_f32_to_f64": (_c_i32, [_vp, _c_i64, _vp, _vp]),
     "hrec_als_gramian_workspace_bytes": (_c_sz, [_c_i64, _c_i32]),
     "hrec_als_gramian": (_c_i32, [_vp, _c_i64, _c_i32, _c_i32, _vp, _vp, _c_sz, _vp]),
@@ -355,14 +357,29 @@ def als_init_factors(seed, row_begin, n_rows, k, kp, out):
         seed, row_begin, n_rows, k, kp, _dev(out, torch.float32, "out"), _stream()))
 
 
-def als_half_sweep(indptr, indices, values, src_factors, k, reg_param, dst_factors, accum_mode=0, src64=None):
+def als_half_sweep(indptr, indices, values, src_factors, k, reg_param, dst_factors, accum_mode=0, src64=None,
+                   kernel=None):
     """K1. src64 (optional): the source factors already converted to f64
     (f32_to_f64 of src_factors) — same results, no conversion per gathered
-    row (hrec_als_half_sweep_src64; kp 64, accum_mode 0)."""
+    row (hrec_als_half_sweep_src64; kp 64, accum_mode 0).
+    kernel (optional; kp 64, accum_mode 0): 0 = one wave per row, 1 = pooled
+    (hrec_als_half_sweep_kernel); None leaves the choice to the library.
+    Same bits either way."""
     n_rows = indptr.numel() - 1
     kp = dst_factors.shape[1]
     if src_factors.shape[1] != kp or dst_factors.shape[0] < n_rows:
         raise HrecError("als_half_sweep: factor shapes do not match")
+    if kernel is not None:
+        if accum_mode != 0 or kp != 64:
+            raise HrecError("als_half_sweep: an explicit kernel needs kp 64 and accum_mode 0")
+        if src64 is not None and src64.shape != src_factors.shape:
+            raise HrecError("als_half_sweep: src64 needs the source factors' shape")
+        src = _dev(src_factors, torch.float32, "src_factors") if src64 is None else _dev(src64, torch.float64, "src64")
+        _check("hrec_als_half_sweep_kernel", lib().hrec_als_half_sweep_kernel(
+            _dev(indptr, torch.int64, "indptr"), _dev(indices, torch.int32, "indices"),
+            _dev(values, torch.float32, "values"), n_rows, src, 0 if src64 is None else 1, src_factors.shape[0], k,
+            kp, float(reg_param), int(kernel), _dev(dst_factors, torch.float32, "dst_factors"), _stream()))
+        return
     if src64 is not None:
         if accum_mode != 0 or src64.shape != src_factors.shape:
             raise HrecError("als_half_sweep: src64 needs accum_mode 0 and the source factors' shape")

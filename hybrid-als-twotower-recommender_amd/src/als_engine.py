@@ -32,6 +32,10 @@ from .synthetic import DeviceCSR
 # ones are gathered in f32): the c2 user side (51 MB) qualifies, its item
 # side (512 MB) does not
 SRC64_MAX_BYTES = int(os.environ.get("HREC_ALS_SRC64_MB", "128")) << 20
+# The kp-64 f64 half-sweep's kernel on both sides: None = the library's choice
+# per launch (csrc/als.hip pick_kernel), 0 = one wave per row, 1 = pooled.
+# Same bits either way.
+HALF_SWEEP_KERNEL = {"": None, "0": 0, "1": 1}[os.environ.get("HREC_ALS_KERNEL", "")]
 
 
 def padded_k(k):
@@ -308,6 +312,8 @@ class DeviceALS:
             return lambda ip, ix, v, dst: self.sweep(ip, ix, v, src, self.k, self.reg, self.alpha, yty, dst)
         s64 = self._src64(src)
         extra = {} if s64 is None else {"src64": s64}
+        if HALF_SWEEP_KERNEL is not None and self._src64_ok:  # the device sweep at kp 64, accum_mode 0
+            extra["kernel"] = HALF_SWEEP_KERNEL
         return lambda ip, ix, v, dst: self.sweep(ip, ix, v, src, self.k, self.reg, dst, self.accum_mode, **extra)
 
     def _sweep(self, csr, src, local, full, cs, chunks):

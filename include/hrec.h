@@ -175,6 +175,15 @@ int hrec_als_half_sweep(const int64_t* indptr, const int32_t* indices,
 int hrec_als_half_sweep_src64(const int64_t* indptr, const int32_t* indices, const float* values,
                               int64_t n_rows, const double* src64, int64_t n_src, int k, int kp,
                               double reg_param, float* dst_factors, void* stream);
+/* The kp = 64, accum_mode 0 half-sweep with the kernel chosen by the caller
+ * (the two entries above choose from the launch's shape): kernel 0 = one wave
+ * per row, 1 = pooled (one persistent 12-wave workgroup per CU, three waves
+ * per SIMD sharing 8 LDS solve slices, rows claimed one by one). Both give
+ * the same bits. src: f32 factors (src_f64 = 0) or their f64 copy
+ * (src_f64 = 1, 16-B aligned). Additive to ABI 7. */
+int hrec_als_half_sweep_kernel(const int64_t* indptr, const int32_t* indices, const float* values,
+                               int64_t n_rows, const void* src, int src_f64, int64_t n_src, int k, int kp,
+                               double reg_param, int kernel, float* dst_factors, void* stream);
 /* out[i] = (double)in[i]. */
 int hrec_f32_to_f64(const float* in, int64_t n, double* out, void* stream);
 
