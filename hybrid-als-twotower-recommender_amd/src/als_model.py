@@ -355,7 +355,14 @@ class ALSModel:
                 return False
             self.item_features = get_item_features(data)
             self.global_mean = data["average_review_rating"].mean()
-            self.model = self._fit(data, initial_user_factors)
+            model = self._fit(data, initial_user_factors)
+            # A row whose normal equations are singular (reg_param 0 and fewer
+            # independent ratings than the rank) comes out of the half-sweep
+            # as NaN; Spark's CholeskySolver raises there and :62 fails.
+            if not bool((torch.isfinite(model.U).all() & torch.isfinite(model.V).all()).item()):
+                raise ArithmeticError("ALS factors are not finite: a row's normal equations are singular "
+                                      "(reg_param = 0 needs at least rank independent ratings in every row)")
+            self.model = model
             return True
         except Exception as e:
             print(f"Training error: {str(e)}")

@@ -92,6 +92,55 @@ def test_als_train_error_sentinel(device, capsys):
     assert m.predict_for_user(1, [1, 2]) == []  # no model -> reference sentinel
 
 
+def _reg0_frame():
+    """60 x 45, 3000 ratings: every user and item has >= 16 distinct partners,
+    so at rank 8 every Gramian is definite without regularisation."""
+    df = _ratings_frame(np.random.default_rng(4), n=3000)
+    for a, b in (("userId", "itemId"), ("itemId", "userId")):
+        assert df.groupby(a)[b].nunique().min() >= 16
+    return df
+
+
+def test_als_train_reg0_singular_row_is_a_training_error(device, capsys):
+    """reg_param = 0 (Spark accepts regParam 0): user 9001 has a single rating,
+    of item 8001 that nobody else rated. With that user's initial factors in
+    {0, 1, 2} item 8001's Gramian is u u^T exactly — singular and exactly
+    representable — so its row comes out NaN, and so does the user's in the
+    next half-sweep. Spark's Cholesky raises there and the reference's train
+    prints "Training error" and returns False (src/als_model.py:64-66)."""
+    from src.als_model import ALSModel
+
+    k = 8
+    df = _reg0_frame()
+    extra = {c: [df[c].iloc[0]] for c in df.columns}
+    extra.update(userId=[9001], itemId=[8001], average_review_rating=[4])
+    df = pd.concat([df, pd.DataFrame(extra)], ignore_index=True)
+    n_u = df["userId"].nunique()
+    U0 = np.random.default_rng(5).normal(size=(n_u, k)).astype(np.float32)
+    U0[-1] = np.array([2, 1, 0, 1, 2, 2, 0, 1], np.float32)  # userId 9001 sorts last
+    m = ALSModel(rank=k, max_iter=2, reg_param=0.0)
+    assert m.train(df, initial_user_factors=U0) is False
+    assert "Training error" in capsys.readouterr().out
+    assert m.model is None and m.predict_for_user(9001, [8001]) == []
+    # the same frame trains with regularisation
+    assert ALSModel(rank=k, max_iter=2, reg_param=0.1).train(df, initial_user_factors=U0) is True
+
+
+def test_als_train_reg0_full_rank_matches_oracle(device):
+    from src.als_model import ALSModel
+
+    k = 8
+    df = _reg0_frame()
+    u_ids, i_ids, ucsr, icsc = _frame_csr(df)
+    U0 = np.random.default_rng(6).normal(size=(len(u_ids), k)).astype(np.float32)
+    m = ALSModel(rank=k, max_iter=5, reg_param=0.0)
+    assert m.train(df, initial_user_factors=U0) is True
+    U, V = oals.fit(ucsr, icsc, U0, k, 0.0, 5, sweep=obuild.half_sweep)
+    assert np.isfinite(U).all() and np.isfinite(V).all()
+    np.testing.assert_allclose(m.model.U[:, :k].cpu().numpy(), U, rtol=1e-4, atol=1e-5)
+    np.testing.assert_allclose(m.model.V[:, :k].cpu().numpy(), V, rtol=1e-4, atol=1e-5)
+
+
 def _rank1_model(device, item_scores, item_features, global_mean):
     """A fitted model whose JVM-order dot reproduces given predictions (k=1,
     U = [1.0]: 0 + 1*v is exact)."""
