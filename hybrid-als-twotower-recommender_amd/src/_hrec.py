@@ -55,6 +55,10 @@ _SIGNATURES = {
     "hrec_transpose_f32": (_c_i32, [_vp, _c_i64, _c_i64, _vp, _c_i64, _vp]),
     "hrec_als_score": (_c_i32, [_vp, _vp, _c_i32, _vp, _c_i64, _vp, _c_i64, _c_i32, _c_i32, _vp,
                                 _vp]),
+    "hrec_als_predict_pairs": (_c_i32, [_vp, _c_i64, _vp, _c_i64, _c_i32, _c_i32, _vp, _vp, _c_i64, _vp, _vp]),
+    "hrec_als_pair_metrics_workspace_bytes": (_c_sz, [_c_i64]),
+    "hrec_als_pair_metrics": (_c_i32, [_vp, _c_i64, _vp, _c_i64, _c_i32, _c_i32, _vp, _vp, _c_i64, _vp, _vp, _vp,
+                                       _vp, _c_sz, _vp]),
     "hrec_als_score_topk_workspace_bytes": (_c_sz, [_c_i32, _c_i64, _c_i32]),
     "hrec_als_score_topk": (_c_i32, [_vp, _vp, _c_i32, _vp, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32, _vp, _vp, _vp,
                                      _vp, _c_sz, _vp]),
@@ -482,6 +486,53 @@ def als_score(user_factors, user_rows, item_factors_t, item_rows, n_items, k, ou
         _dev(item_rows, torch.int64, "item_rows"), n_items, k, kp,
         _dev(out, torch.float32, "out"), _stream()))
     return out
+
+
+# slots of als_pair_metrics' sums (HREC_PAIR_* of include/hrec.h)
+PAIR_SUMS = ("n_ok", "n_nan", "sum_e", "sum_abs_e", "sum_e2", "sum_y", "sum_y2", "sum_p", "sum_p2", "sum_yp")
+
+
+def _pair_args(name, user_factors, item_factors, user_rows, item_rows):
+    kp = user_factors.shape[1]
+    n = user_rows.numel()
+    if item_factors.shape[1] != kp or item_rows.numel() != n:
+        raise HrecError(f"{name}: factor widths or row list lengths do not match")
+    return kp, n, (_dev(user_factors, torch.float32, "user_factors"), user_factors.shape[0],
+                   _dev(item_factors, torch.float32, "item_factors"), item_factors.shape[0])
+
+
+def als_predict_pairs(user_factors, item_factors, user_rows, item_rows, k, out=None):
+    """f32 [n]: the JVM-exact ALS prediction of every (user_rows[p],
+    item_rows[p]) pair (hrec_als_predict_pairs); both factor matrices
+    row-major [rows, kp]. NaN where either row is outside its matrix (-1)."""
+    kp, n, fac = _pair_args("als_predict_pairs", user_factors, item_factors, user_rows, item_rows)
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=user_factors.device)
+    elif out.numel() != n:
+        raise HrecError("als_predict_pairs: out must have one entry per pair")
+    _check("hrec_als_predict_pairs", lib().hrec_als_predict_pairs(
+        *fac, int(k), kp, _dev(user_rows, torch.int64, "user_rows"), _dev(item_rows, torch.int64, "item_rows"), n,
+        _dev(out, torch.float32, "out"), _stream()))
+    return out
+
+
+def als_pair_metrics(user_factors, item_factors, user_rows, item_rows, k, labels, pred_out=None):
+    """f64 device [len(PAIR_SUMS)]: the counts and sums of
+    hrec_als_pair_metrics over the pairs' predictions against labels (f64
+    [n]); pred_out (f32 [n], optional) also receives the predictions. One
+    scoring launch + a fixed-order reduction: the same bits on every call."""
+    kp, n, fac = _pair_args("als_pair_metrics", user_factors, item_factors, user_rows, item_rows)
+    if labels.numel() != n or (pred_out is not None and pred_out.numel() != n):
+        raise HrecError("als_pair_metrics: labels / pred_out must have one entry per pair")
+    dev = user_factors.device
+    sums = torch.empty(len(PAIR_SUMS), dtype=torch.float64, device=dev)
+    need = int(lib().hrec_als_pair_metrics_workspace_bytes(n))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    _check("hrec_als_pair_metrics", lib().hrec_als_pair_metrics(
+        *fac, int(k), kp, _dev(user_rows, torch.int64, "user_rows"), _dev(item_rows, torch.int64, "item_rows"), n,
+        _dev(labels, torch.float64, "labels"), _dev(pred_out, torch.float32, "pred_out"),
+        _dev(sums, torch.float64, "sums"), _dev(ws, torch.uint8, "ws"), need, _stream()))
+    return sums
 
 
 def als_score_topk(user_factors, user_rows, item_factors_t, n_items, k, top_k, check_overflow=True,

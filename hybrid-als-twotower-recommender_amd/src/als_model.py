@@ -24,6 +24,10 @@ ALSModel.transform at :75) is replaced by libhrec's HIP kernels:
                       ids = coldStartStrategy "drop")                [K2]
                       + cold-start fallback via hrec_cosine_sim +
                       hrec_topk_f64 (_find_similar_items)            [K3]
+  transform / regression_metrics / evaluate (Spark's ALSModel.transform on
+                      a pair frame and RegressionEvaluator; not in the
+                      reference) -> hrec_als_predict_pairs /
+                      hrec_als_pair_metrics                          [K2x]
 
 `initialize_spark` / `stop_spark` keep their names: they bind / release the
 HIP device session that plays the SparkSession's role.
@@ -69,7 +73,7 @@ class DeviceALSFactors:
         self.V = V                               # [n_items, kp] f32 device
         self.k = int(k)
         self.Vt = _hrec.transpose(V) if V.shape[0] else V.t().contiguous()
-        self._item_ids_dev = None
+        self._ids_dev = {}  # "user" / "item" -> the sorted ids on the device (_lookup_device)
 
     @staticmethod
     def _lookup(ids, keys):
@@ -81,13 +85,14 @@ class DeviceALSFactors:
         ok = ids[pos] == keys
         return np.where(ok, pos, -1).astype(np.int64)
 
-    def _lookup_device(self, keys):
-        """_lookup for long candidate lists: the same binary search on the
-        device over a cached copy of the sorted item ids."""
+    def _lookup_device(self, keys, side="item"):
+        """_lookup for long id lists: the same binary search on the device
+        over a cached copy of the sorted item (or user) ids."""
         dev = self.U.device
-        if self._item_ids_dev is None:
-            self._item_ids_dev = torch.as_tensor(np.asarray(self.item_ids, np.int64), device=dev)
-        ids = self._item_ids_dev
+        if side not in self._ids_dev:
+            ids_h = self.item_ids if side == "item" else self.user_ids
+            self._ids_dev[side] = torch.as_tensor(np.asarray(ids_h, np.int64), device=dev)
+        ids = self._ids_dev[side]
         k = torch.as_tensor(keys, device=dev)
         if ids.numel() == 0:
             return torch.full_like(k, -1)
@@ -106,6 +111,37 @@ class DeviceALSFactors:
         else:
             irows = torch.as_tensor(self._lookup(self.item_ids, item_list), device=dev)
         return _hrec.als_score(self.U, urows, self.Vt, irows, irows.numel(), self.k)
+
+    PAIR_DEVICE_LOOKUP = 4096  # id lists longer than this are looked up on the device
+
+    def _pair_rows(self, user_ids, item_ids):
+        """(user rows, item rows): int64 device tensors, -1 for an unknown id."""
+        dev = self.U.device
+        rows = []
+        for side, ids, keys in (("user", self.user_ids, user_ids), ("item", self.item_ids, item_ids)):
+            keys = np.asarray(keys, np.int64)
+            if keys.size > self.PAIR_DEVICE_LOOKUP:
+                rows.append(self._lookup_device(keys, side))
+            else:
+                rows.append(torch.as_tensor(self._lookup(ids, keys), device=dev))
+        if rows[0].numel() != rows[1].numel():
+            raise ValueError("user_ids and item_ids must have the same length")
+        return rows
+
+    def predict_pairs(self, user_ids, item_ids):
+        """f32 device [n]: the prediction of pair (user_ids[p], item_ids[p])
+        (Spark ALSModel.transform on a pair frame, hrec_als_predict_pairs);
+        NaN where either id is unknown. The bits of score() for that pair."""
+        urows, irows = self._pair_rows(user_ids, item_ids)
+        return _hrec.als_predict_pairs(self.U, self.V, urows, irows, self.k)
+
+    def pair_sums(self, user_ids, item_ids, labels):
+        """{name: float} of _hrec.PAIR_SUMS for the pairs' predictions against
+        labels (hrec_als_pair_metrics): one scoring launch, one small copy."""
+        urows, irows = self._pair_rows(user_ids, item_ids)
+        y = torch.as_tensor(np.asarray(labels, np.float64), device=self.U.device)
+        sums = _hrec.als_pair_metrics(self.U, self.V, urows, irows, self.k, y)
+        return dict(zip(_hrec.PAIR_SUMS, sums.tolist()))
 
     # Spark 3.5 ALSModel directory layout (MLWriter): metadata/part-00000 is
     # one JSON line with the model params and "rank"; userFactors/ and
@@ -605,6 +641,72 @@ class ALSModel:
             return self._similar_batch([item_id], k)[0]
         except KeyError:
             return []
+
+    # ------------------------------------------- transform / RegressionEvaluator
+    # Spark's ALSModel.transform on a frame of (userId, itemId) rows and its
+    # RegressionEvaluator over the result. Neither has a counterpart in the
+    # reference, so failures raise instead of printing a sentinel.
+    METRIC_NAMES = ("rmse", "mse", "mae", "r2", "var")
+
+    def _pair_ids(self, data):
+        if self.model is None:
+            raise RuntimeError("the ALS model is not trained or loaded")
+        if self.cold_start_strategy not in ("drop", "nan"):
+            raise ValueError(f"coldStartStrategy {self.cold_start_strategy!r} is not supported")
+        return _int_ids(data["userId"], "userId"), _int_ids(data["itemId"], "itemId")
+
+    def transform(self, data, prediction_col="prediction"):
+        """A copy of `data` (columns userId, itemId) with the f32 prediction
+        of every row in `prediction_col`; NaN where the user or the item is
+        unknown to the model. cold_start_strategy "drop" removes those rows
+        (order and index kept), "nan" keeps them."""
+        users, items = self._pair_ids(data)
+        pred = self.model.predict_pairs(users, items).cpu().numpy()
+        out = data.copy()
+        out[prediction_col] = pred
+        if self.cold_start_strategy == "drop":
+            out = out[~np.isnan(pred)]
+        return out
+
+    def regression_metrics(self, data, label_col="average_review_rating"):
+        """Spark's RegressionMetrics of the predictions for `data` against
+        `label_col` (unweighted, not through the origin), over the n rows
+        kept: {"rmse", "mse", "mae", "r2", "var", "count", "dropped"} with
+        mse = sum e^2 / n, mae = sum |e| / n, r2 = 1 - sum e^2 / sum (y -
+        ybar)^2 and var = sum (p - ybar)^2 / n (ybar the label mean).
+        cold_start_strategy "drop" leaves rows with a NaN prediction out and
+        counts them in "dropped"; "nan" keeps them, and one such row makes
+        every metric NaN. No row kept: NaN metrics, count 0. The predictions
+        never leave the device (hrec_als_pair_metrics)."""
+        users, items = self._pair_ids(data)
+        s = self.model.pair_sums(users, items, np.asarray(data[label_col], np.float64))
+        n_ok, n_nan = int(s["n_ok"]), int(s["n_nan"])
+        nan = float("nan")
+        res = {name: nan for name in self.METRIC_NAMES}
+        if self.cold_start_strategy == "nan":
+            res.update(count=n_ok + n_nan, dropped=0)
+            if n_nan:
+                return res
+        else:
+            res.update(count=n_ok, dropped=n_nan)
+        if n_ok == 0:
+            return res
+        n = float(n_ok)
+        ybar = s["sum_y"] / n
+        ss_tot = s["sum_y2"] - s["sum_y"] * ybar                        # sum (y - ybar)^2
+        ss_reg = s["sum_p2"] - 2.0 * ybar * s["sum_p"] + n * ybar * ybar  # sum (p - ybar)^2
+        mse = s["sum_e2"] / n
+        with np.errstate(all="ignore"):  # constant labels: ss_tot is 0 and r2 is -inf or NaN, as in Spark
+            r2 = float(1.0 - np.float64(s["sum_e2"]) / np.float64(ss_tot))
+        res.update(mse=mse, rmse=float(np.sqrt(mse)), mae=s["sum_abs_e"] / n, var=ss_reg / n, r2=r2)
+        return res
+
+    def evaluate(self, data, metric_name="rmse", label_col="average_review_rating"):
+        """Spark's RegressionEvaluator(metricName=metric_name).evaluate of
+        transform(data): one of rmse, mse, mae, r2, var (a float)."""
+        if metric_name not in self.METRIC_NAMES:
+            raise ValueError(f"metric_name must be one of {', '.join(self.METRIC_NAMES)} (got {metric_name!r})")
+        return float(self.regression_metrics(data, label_col)[metric_name])
 
     # ----------------------------------------------------------- persistence
     def save_model(self, model_path="models/als"):

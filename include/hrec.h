@@ -11,6 +11,9 @@
  *                                                          hrec_als_init_factors,
  *                                                          hrec_als_half_sweep
  *   Spark  ALSModel.transform src/als_model.py:71-76   -> hrec_als_score
+ *   Spark  ALSModel.transform on a pair frame /
+ *          RegressionEvaluator (no reference line)    -> hrec_als_predict_pairs,
+ *                                                          hrec_als_pair_metrics
  *   Python/sklearn fusion     src/hybrid_system.py:57-75,108 -> hrec_fuse_topk
  *   Keras  two-tower graph    src/two_tower_model.py:38-89 -> hrec_tt_*
  *
@@ -250,6 +253,48 @@ int hrec_als_score(const float* user_factors, const int64_t* user_rows,
                    int n_users, const float* item_factors_t, int64_t ld_items,
                    const int64_t* item_rows, int64_t n_items, int k, int kp,
                    float* out, void* stream);
+
+/* ALS predictions for a list of pairs (Spark ALSModel.transform on a frame
+ * of (user, item) rows, and RegressionEvaluator over it). Additive to ABI 7.
+ *
+ * hrec_als_predict_pairs: out[p] = sum_{c<k} U[user_rows[p]][c] *
+ * V[item_rows[p]][c], p < n: the chain of hrec_als_score (f32, sequential in
+ * c from 0.0f, product rounded then sum rounded), so a pair gets the bits the
+ * score matrix holds for it. Both factor matrices are row-major [n_rows, kp]
+ * (the item matrix is NOT transposed here), 16-B aligned. A row index
+ * outside [0, n_rows) on either side (any negative value marks an unknown
+ * id) gives a quiet NaN and is never dereferenced. n == 0 is a no-op.
+ *
+ * hrec_als_pair_metrics: the same predictions (stored when pred_out is not
+ * NULL) and, over the pairs whose prediction is not NaN, with y = labels[p],
+ * p^ = (double)prediction and e = y - p^ in f64, sums_out[HREC_PAIR_SUMS]
+ * (device f64) as named below; HREC_PAIR_N_NAN counts the pairs with a NaN
+ * prediction (unknown row or a NaN chain), which enter no sum. No
+ * floating-point atomics: per-block partials in the workspace (the block
+ * count depends on n alone) are added in a fixed order by a second launch,
+ * so equal inputs give equal bits on every call. n == 0 writes zeros.
+ * Workspace: hrec_als_pair_metrics_workspace_bytes(n). */
+#define HREC_PAIR_N_OK 0      /* pairs with a prediction (as f64, exact) */
+#define HREC_PAIR_N_NAN 1     /* pairs with a NaN prediction             */
+#define HREC_PAIR_SUM_E 2     /* sum e                                   */
+#define HREC_PAIR_SUM_ABS_E 3 /* sum |e|                                 */
+#define HREC_PAIR_SUM_E2 4    /* sum e^2                                 */
+#define HREC_PAIR_SUM_Y 5     /* sum y                                   */
+#define HREC_PAIR_SUM_Y2 6    /* sum y^2                                 */
+#define HREC_PAIR_SUM_P 7     /* sum p^                                  */
+#define HREC_PAIR_SUM_P2 8    /* sum p^^2                                */
+#define HREC_PAIR_SUM_YP 9    /* sum y p^                                */
+#define HREC_PAIR_SUMS 10
+int hrec_als_predict_pairs(const float* user_factors, int64_t n_user_rows,
+                           const float* item_factors, int64_t n_item_rows, int k, int kp,
+                           const int64_t* user_rows, const int64_t* item_rows, int64_t n,
+                           float* out, void* stream);
+size_t hrec_als_pair_metrics_workspace_bytes(int64_t n);
+int hrec_als_pair_metrics(const float* user_factors, int64_t n_user_rows,
+                          const float* item_factors, int64_t n_item_rows, int k, int kp,
+                          const int64_t* user_rows, const int64_t* item_rows, int64_t n,
+                          const double* labels, float* pred_out, double* sums_out,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* Scoring consumed by a top-k, for whole item ranges (no id gather): the
  * same JVM-exact f32 dot as hrec_als_score for every (user, item j < n_items)
