@@ -8,6 +8,7 @@ CPU fallback on the product path.
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -59,6 +60,9 @@ _SIGNATURES = {
     "hrec_als_pair_metrics_workspace_bytes": (_c_sz, [_c_i64]),
     "hrec_als_pair_metrics": (_c_i32, [_vp, _c_i64, _vp, _c_i64, _c_i32, _c_i32, _vp, _vp, _c_i64, _vp, _vp, _vp,
                                        _vp, _c_sz, _vp]),
+    "hrec_ranking_metrics_workspace_bytes": (_c_sz, [_c_i64]),
+    "hrec_ranking_metrics": (_c_i32, [_vp, _c_i64, _c_i32, _vp, _vp, _vp, _c_i64, _c_i32, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _c_sz, _vp]),
     "hrec_als_score_topk_workspace_bytes": (_c_sz, [_c_i32, _c_i64, _c_i32]),
     "hrec_als_score_topk": (_c_i32, [_vp, _vp, _c_i32, _vp, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32, _vp, _vp, _vp,
                                      _vp, _c_sz, _vp]),
@@ -535,6 +539,58 @@ def als_pair_metrics(user_factors, item_factors, user_rows, item_rows, k, labels
     return sums
 
 
+# slots of ranking_metrics' sums (HREC_RANK_* of include/hrec.h)
+RANK_SUMS = ("n_rows", "n_empty", "hits", "sum_precision", "sum_recall", "sum_ap", "sum_ap_k", "sum_ndcg")
+RANK_MAX = 1024  # largest k and list length of hrec_ranking_metrics
+
+
+def rank_tables(k):
+    """The host tables hrec_ranking_metrics reads (numpy f64): gain[i] = 1 /
+    ln(i + 2), i < k, and idcg[j] = gain[0] + ... + gain[j - 1], j <= k,
+    added in that order (cumsum is sequential)."""
+    gain = 1.0 / np.log(np.arange(int(k), dtype=np.float64) + 2.0)
+    return gain, np.concatenate([np.zeros(1), np.cumsum(gain)])
+
+
+def ranking_metrics(pred, label_indptr, labels, k, pred_len=None, pred_len_max=None, want_per_row=False):
+    """Spark's RankingMetrics sums over ranked id lists on the device
+    (hrec_ranking_metrics). pred: int64 [n_rows, ld], row r's list best first
+    in its first pred_len[r] (int32 [n_rows]; None: pred_len_max, default ld)
+    entries; labels[label_indptr[r] : label_indptr[r + 1]] (int64, ascending)
+    its ground truth. Returns (sums f64 [len(RANK_SUMS)], unsorted int32 [1],
+    per_row f64 [n_rows, 5] or None), all on the device; the sums mean nothing
+    when unsorted is 1. The same bits on every call."""
+    n_rows = label_indptr.numel() - 1
+    k = int(k)
+    if pred.dim() != 2 or pred.shape[0] != n_rows or n_rows < 0:
+        raise HrecError("ranking_metrics: pred must be [n_rows, ld] with n_rows = len(label_indptr) - 1")
+    if pred_len is not None and pred_len.numel() != n_rows:
+        raise HrecError("ranking_metrics: pred_len must have one entry per row")
+    dev = label_indptr.device
+    ld = int(pred.shape[1])
+    len_max = ld if pred_len_max is None else int(pred_len_max)
+    if n_rows > 0 and pred.numel() == 0:  # no list entries at all: a stand-in column, never read
+        pred, ld = torch.zeros((n_rows, 1), dtype=torch.int64, device=dev), 1
+    if labels.numel() == 0:
+        labels = torch.zeros(1, dtype=torch.int64, device=dev)
+    gain_h, idcg_h = rank_tables(k) if 1 <= k <= RANK_MAX else (np.zeros(1), np.zeros(2))  # the library rejects k
+    gain, idcg = torch.as_tensor(gain_h, device=dev), torch.as_tensor(idcg_h, device=dev)
+    sums = torch.empty(len(RANK_SUMS), dtype=torch.float64, device=dev)
+    unsorted = torch.empty(1, dtype=torch.int32, device=dev)
+    per_row = torch.empty((n_rows, 5), dtype=torch.float64, device=dev) if want_per_row and n_rows > 0 else None
+    need = int(lib().hrec_ranking_metrics_workspace_bytes(n_rows))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    _check("hrec_ranking_metrics", lib().hrec_ranking_metrics(
+        _dev(pred, torch.int64, "pred"), ld, len_max, _dev(pred_len, torch.int32, "pred_len"),
+        _dev(label_indptr, torch.int64, "label_indptr"), _dev(labels, torch.int64, "labels"), n_rows, k,
+        _dev(gain, torch.float64, "gain"), _dev(idcg, torch.float64, "idcg"), _dev(per_row, torch.float64, "per_row"),
+        _dev(sums, torch.float64, "sums"), _dev(unsorted, torch.int32, "unsorted"), _dev(ws, torch.uint8, "ws"), need,
+        _stream()))
+    if want_per_row and per_row is None:
+        per_row = torch.empty((0, 5), dtype=torch.float64, device=dev)
+    return sums, unsorted, per_row
+
+
 def als_score_topk(user_factors, user_rows, item_factors_t, n_items, k, top_k, check_overflow=True,
                    overflow_out=None):
     """Top-k of the JVM-exact ALS scores over items [0, n_items) for each
@@ -577,22 +633,29 @@ def als_items_bf16(item_factors, k):
 
 
 def als_score_topk_pruned(user_factors, user_rows, item_factors_t, item_factors, items_bf16, n_items, k, top_k,
-                          check_overflow=True, overflow_out=None, workspace=None):
+                          check_overflow=True, overflow_out=None, workspace=None, out=None):
     """als_score_topk with the bf16 matrix-core bound in front of the exact
     chain (hrec_als_score_topk_pruned): the same (ids, scores). item_factors
     is the row-major copy of item_factors_t, items_bf16 from als_items_bf16.
     workspace (uint8 device, optional) is reused when large enough. For
     top_k <= 8 an overflow is resolved on the device inside the call (no
     host read); above, the overflow flag falls back to the full score matrix
-    + top-k as als_score_topk does (check_overflow)."""
+    + top-k as als_score_topk does (check_overflow). out (optional): the
+    contiguous (int64 [B, kk], f32 [B, kk]) tensors to write, e.g. the row
+    slices of a larger result (with check_overflow=False)."""
     kp = user_factors.shape[1]
     B = user_rows.numel()
     kk = min(int(top_k), int(n_items))
     dev = user_factors.device
     if item_factors.stride(1) != 1 or item_factors.shape[0] < n_items:
         raise HrecError("als_score_topk_pruned: item_factors must be row-major with >= n_items rows")
-    out_i = torch.empty((B, kk), dtype=torch.int64, device=dev)
-    out_v = torch.empty((B, kk), dtype=torch.float32, device=dev)
+    if out is not None:
+        out_i, out_v = out
+        if tuple(out_i.shape) != (B, kk) or tuple(out_v.shape) != (B, kk) or check_overflow:
+            raise HrecError("als_score_topk_pruned: out must be two [B, kk] tensors, with check_overflow=False")
+    else:
+        out_i = torch.empty((B, kk), dtype=torch.int64, device=dev)
+        out_v = torch.empty((B, kk), dtype=torch.float32, device=dev)
     flag = overflow_out if overflow_out is not None else torch.empty(1, dtype=torch.int32, device=dev)
     need = int(lib().hrec_als_score_topk_pruned_workspace_bytes(B, n_items, kk, int(k)))
     ws = workspace if workspace is not None and workspace.numel() >= need else \

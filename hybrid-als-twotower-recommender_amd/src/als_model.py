@@ -28,6 +28,17 @@ ALSModel.transform at :75) is replaced by libhrec's HIP kernels:
                       a pair frame and RegressionEvaluator; not in the
                       reference) -> hrec_als_predict_pairs /
                       hrec_als_pair_metrics                          [K2x]
+  recommend_for_all_users / _items / _user_subset / _item_subset (Spark's
+                      recommendForAll* / recommendFor*Subset; not in the
+                      reference) -> DeviceALSFactors.recommend: batches of
+                      4096 query rows through hrec_als_score_topk_pruned
+                      (bf16 matrix-core bound + the JVM-exact chain), raw
+                      ids gathered on the device
+  ranking_metrics / evaluate_ranking (Spark's RankingMetrics /
+                      RankingEvaluator: MAP, MAP@k, precision@k, recall@k,
+                      NDCG@k; not in the reference) -> recommend's lists,
+                      still on the device, against a label CSR ->
+                      hrec_ranking_metrics                           [K2r]
 
 `initialize_spark` / `stop_spark` keep their names: they bind / release the
 HIP device session that plays the SparkSession's role.
@@ -74,6 +85,7 @@ class DeviceALSFactors:
         self.k = int(k)
         self.Vt = _hrec.transpose(V) if V.shape[0] else V.t().contiguous()
         self._ids_dev = {}  # "user" / "item" -> the sorted ids on the device (_lookup_device)
+        self._rec_ops = {}  # "user" / "item" -> recommend()'s operands (_recommend_operands)
 
     @staticmethod
     def _lookup(ids, keys):
@@ -142,6 +154,78 @@ class DeviceALSFactors:
         y = torch.as_tensor(np.asarray(labels, np.float64), device=self.U.device)
         sums = _hrec.als_pair_metrics(self.U, self.V, urows, irows, self.k, y)
         return dict(zip(_hrec.PAIR_SUMS, sums.tolist()))
+
+    RECOMMEND_BATCH = 4096               # query rows per hrec_als_score_topk_pruned call
+    RECOMMEND_FALLBACK_BYTES = 1 << 30   # the overflow fallback's score matrix stays under this (per sub-batch)
+    RECOMMEND_MAX = 1024                 # largest list length (the library's top_k limit)
+
+    def _recommend_operands(self, side):
+        """What ranking the other side for `side`'s rows needs, built once per
+        model and side: (query factors, candidate factors row-major, their
+        transpose, their bf16 operand, the candidates' raw ids on the device).
+        side "item" is side "user" with U and V swapped."""
+        if side not in ("user", "item"):
+            raise ValueError(f"side must be 'user' or 'item' (got {side!r})")
+        cache = self._rec_ops
+        if side not in cache:
+            Q, F = (self.U, self.V) if side == "user" else (self.V, self.U)
+            if side == "user":
+                Ft = self.Vt
+            else:
+                Ft = _hrec.transpose(F) if F.shape[0] else F.t().contiguous()
+            bf = _hrec.als_items_bf16(F, self.k) if F.shape[0] else None
+            ids_h = self.item_ids if side == "user" else self.user_ids
+            ids = torch.as_tensor(np.asarray(ids_h, np.int64), device=Q.device)
+            cache[side] = (Q, F, Ft, bf, ids)
+        return cache[side]
+
+    def recommend(self, side, rows, num):
+        """Top-`num` of the other side for each of `rows` (int64 row indices
+        into `side`'s factor matrix, every one in range): device (ids int64
+        [n, kk], scores f32 [n, kk]), kk = min(num, size of the other side).
+        side "user" ranks items for user rows, "item" ranks users for item
+        rows. ids are raw ids. A score has the bits predict_pairs / transform
+        gives for that pair (the JVM f32 chain); a list is descending, equal
+        scores keep the smaller raw id first (the ids are sorted, the library
+        breaks ties on the row index). Batches of RECOMMEND_BATCH rows go
+        through hrec_als_score_topk_pruned on one workspace; for kk > 8 a
+        batch whose overflow flag is set is redone through hrec_als_score +
+        hrec_topk in sub-batches of at most RECOMMEND_FALLBACK_BYTES of
+        scores (kk <= 8: the library resolves it on the device)."""
+        num = int(num)
+        if not 1 <= num <= self.RECOMMEND_MAX:
+            raise ValueError(f"num must be in [1, {self.RECOMMEND_MAX}] (got {num})")
+        Q, F, Ft, bf, ids = self._recommend_operands(side)
+        dev = Q.device
+        rows = torch.as_tensor(rows, dtype=torch.int64, device=dev).reshape(-1).contiguous()
+        n, n_other = rows.numel(), int(F.shape[0])
+        kk = min(num, n_other)
+        out_i = torch.empty((n, kk), dtype=torch.int64, device=dev)
+        out_v = torch.empty((n, kk), dtype=torch.float32, device=dev)
+        if n == 0 or kk == 0:
+            return out_i, out_v
+        if bool(((rows < 0) | (rows >= Q.shape[0])).any().item()):
+            raise ValueError(f"recommend: a {side} row is outside [0, {Q.shape[0]})")
+        B = int(self.RECOMMEND_BATCH)
+        starts = range(0, n, B)
+        flags = torch.zeros(len(starts), dtype=torch.int32, device=dev)
+        need = int(_hrec.lib().hrec_als_score_topk_pruned_workspace_bytes(min(B, n), n_other, kk, self.k))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        for b, s in enumerate(starts):
+            _hrec.als_score_topk_pruned(Q, rows[s: s + B], Ft, F, bf, n_other, self.k, kk, check_overflow=False,
+                                        overflow_out=flags[b: b + 1], workspace=ws,
+                                        out=(out_i[s: s + B], out_v[s: s + B]))
+        del ws
+        if kk > 8:  # one host read for all batches; a flagged batch is incomplete
+            sub = max(1, self.RECOMMEND_FALLBACK_BYTES // (4 * n_other))
+            for b in torch.nonzero(flags).reshape(-1).tolist():
+                lo, hi = starts[b], min(starts[b] + B, n)
+                for s in range(lo, hi, sub):
+                    e = min(s + sub, hi)
+                    scores = _hrec.als_score(Q, rows[s:e], Ft, None, n_other, self.k)
+                    out_i[s:e], out_v[s:e] = _hrec.topk(scores, kk)
+                    del scores
+        return ids[out_i], out_v
 
     # Spark 3.5 ALSModel directory layout (MLWriter): metadata/part-00000 is
     # one JSON line with the model params and "rank"; userFactors/ and
@@ -707,6 +791,157 @@ class ALSModel:
         if metric_name not in self.METRIC_NAMES:
             raise ValueError(f"metric_name must be one of {', '.join(self.METRIC_NAMES)} (got {metric_name!r})")
         return float(self.regression_metrics(data, label_col)[metric_name])
+
+    # ------------------------------------------------ recommendForAll / Subset
+    # Spark's ALSModel.recommendForAllUsers / recommendForAllItems /
+    # recommendForUserSubset / recommendForItemSubset. No counterpart in the
+    # reference: failures raise. After a fit in a torch.distributed world of
+    # W > 1 ranks every rank holds the full model, and each rank that calls
+    # these computes the whole answer (the recommendation is not sharded).
+    def _trained(self):
+        if self.model is None:
+            raise RuntimeError("the ALS model is not trained or loaded")
+        return self.model
+
+    def _recommend_frame(self, side, subset, num):
+        import pandas as pd
+
+        model = self._trained()
+        col, ids = ("userId", model.user_ids) if side == "user" else ("itemId", model.item_ids)
+        ids = np.asarray(ids, np.int64)
+        if subset is None:
+            rows = np.arange(len(ids), dtype=np.int64)
+        else:
+            if isinstance(subset, pd.DataFrame):
+                subset = subset[col]
+            keys = np.unique(_int_ids(np.asarray(subset).reshape(-1), col))
+            rows = model._lookup(ids, keys)
+            rows = rows[rows >= 0]  # ids the model does not know are left out (Spark's join)
+        rec_ids, scores = model.recommend(side, rows, num)
+        rec_ids, scores = rec_ids.cpu().numpy().tolist(), scores.cpu().numpy().tolist()
+        return pd.DataFrame({col: ids[rows], "recommendations": [list(zip(i, s)) for i, s in zip(rec_ids, scores)]})
+
+    def recommend_for_all_users(self, num_items):
+        """Spark's recommendForAllUsers: a DataFrame with one row per user
+        of the model, `userId` ascending, and `recommendations`: the user's
+        top num_items (1 .. 1024) items as (itemId: int, rating: float)
+        tuples, best first; equal ratings keep the smaller itemId first. A
+        rating is transform's f32 prediction for that pair. Scored and ranked
+        on the device (DeviceALSFactors.recommend); on every rank of a
+        multi-GPU world the whole answer."""
+        return self._recommend_frame("user", None, num_items)
+
+    def recommend_for_all_items(self, num_users):
+        """Spark's recommendForAllItems: per item (`itemId` ascending) its
+        top num_users users as (userId, rating) tuples."""
+        return self._recommend_frame("item", None, num_users)
+
+    def recommend_for_user_subset(self, users, num_items):
+        """Spark's recommendForUserSubset: recommend_for_all_users for the
+        distinct ids of `users` (a DataFrame with a userId column, or an
+        array-like of ids); ids unknown to the model are left out."""
+        return self._recommend_frame("user", users, num_items)
+
+    def recommend_for_item_subset(self, items, num_users):
+        """Spark's recommendForItemSubset (a DataFrame with an itemId column,
+        or an array-like of ids)."""
+        return self._recommend_frame("item", items, num_users)
+
+    # ----------------------------------------- RankingEvaluator / RankingMetrics
+    RANKING_METRIC_NAMES = ("meanAveragePrecision", "meanAveragePrecisionAtK", "precisionAtK", "recallAtK",
+                            "ndcgAtK")
+    RANKING_HOST_ROWS = 1 << 16  # frames up to this many rows: the label CSR is built on the host
+
+    @staticmethod
+    def _label_csr_host(users, items, dev):
+        """(distinct users, indptr, labels) of the (user, item) rows, int64
+        device tensors: users ascending, a user's items ascending (duplicates
+        stay; the kernel counts them once)."""
+        order = np.lexsort((items, users))
+        u, labels = users[order], items[order]
+        first = np.flatnonzero(np.r_[True, u[1:] != u[:-1]]) if len(u) else np.zeros(0, np.int64)
+        indptr = np.r_[first, len(u)].astype(np.int64)
+        return tuple(torch.as_tensor(np.ascontiguousarray(a, np.int64), device=dev) for a in (u[first], indptr, labels))
+
+    @staticmethod
+    def _label_csr_device(users, items, dev):
+        """_label_csr_host with the sorts on the device (two stable sorts)."""
+        u, it = torch.as_tensor(users, device=dev), torch.as_tensor(items, device=dev)
+        it, order = torch.sort(it, stable=True)
+        u, order = torch.sort(u[order], stable=True)
+        uniq, counts = torch.unique_consecutive(u, return_counts=True)
+        indptr = torch.zeros(uniq.numel() + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(counts, 0, out=indptr[1:])
+        return uniq, indptr, it[order].contiguous()
+
+    def ranking_metrics(self, data, k=10, label_col=None, min_rating=None):
+        """Spark's RankingMetrics (binary relevance) of the model's top-k item
+        lists against `data` (columns userId, itemId): {"meanAveragePrecision",
+        "meanAveragePrecisionAtK", "precisionAtK", "recallAtK", "ndcgAtK",
+        "count", "dropped"}. A user's ground truth is the set of its itemIds
+        in `data` — with min_rating, of the rows whose label_col (default
+        average_review_rating) is >= min_rating; a user left with no row does
+        not appear. Items unknown to the model stay in the set: never hit,
+        counted in its size. Each metric is the mean over the `count` users
+        evaluated (NaN when count is 0). cold_start_strategy "drop" leaves
+        users unknown to the model out and counts them in "dropped"; "nan"
+        keeps them with an empty list (every metric 0 for them, as Spark gives
+        for an empty prediction array). The lists never leave the device
+        (DeviceALSFactors.recommend -> hrec_ranking_metrics)."""
+        k = int(k)
+        if not 1 <= k <= _hrec.RANK_MAX:
+            raise ValueError(f"k must be in [1, {_hrec.RANK_MAX}] (got {k})")
+        users, items = self._pair_ids(data)
+        if min_rating is not None:
+            keep = np.asarray(data[label_col or "average_review_rating"], np.float64) >= float(min_rating)
+            users, items = users[keep], items[keep]
+        model, dev = self.model, self.model.U.device
+        dropped = 0
+        if self.cold_start_strategy == "drop":  # pairs of unknown users go before the CSR is built
+            if users.size > model.PAIR_DEVICE_LOOKUP:
+                known = (model._lookup_device(users, "user") >= 0).cpu().numpy()
+            else:
+                known = model._lookup(model.user_ids, users) >= 0
+            dropped = int(np.unique(users[~known]).size)
+            users, items = users[known], items[known]
+        build = self._label_csr_host if users.size <= self.RANKING_HOST_ROWS else self._label_csr_device
+        uniq, indptr, labels = build(users, items, dev)
+        n = int(uniq.numel())
+        res = {name: float("nan") for name in self.RANKING_METRIC_NAMES}
+        res.update(count=n, dropped=dropped)
+        if n == 0:
+            return res
+        rows = model._lookup_device(uniq, "user")
+        known = rows >= 0
+        n_known = n if self.cold_start_strategy == "drop" else int(known.sum().item())
+        pred_len = None
+        if n_known == n:
+            pred, _ = model.recommend("user", rows, k)
+        else:  # "nan": an unknown user keeps its row, with an empty list
+            top, _ = model.recommend("user", rows[known], k)
+            pred = torch.zeros((n, max(int(top.shape[1]), 1)), dtype=torch.int64, device=dev)
+            pred[known, : top.shape[1]] = top
+            pred_len = (known * int(top.shape[1])).to(torch.int32)
+        sums, unsorted, _ = _hrec.ranking_metrics(pred, indptr, labels, k, pred_len=pred_len,
+                                                  pred_len_max=int(pred.shape[1]) if pred.numel() else 0)
+        s = torch.cat([sums, unsorted.to(torch.float64)]).tolist()  # one host read
+        if s[-1] != 0.0:
+            raise RuntimeError("ranking_metrics: a label row is not sorted ascending")
+        s = dict(zip(_hrec.RANK_SUMS, s))
+        if int(s["n_rows"]) != n:
+            raise RuntimeError(f"ranking_metrics: {int(s['n_rows'])} rows evaluated, {n} expected")
+        for name, slot in zip(self.RANKING_METRIC_NAMES, ("sum_ap", "sum_ap_k", "sum_precision", "sum_recall",
+                                                          "sum_ndcg")):
+            res[name] = s[slot] / n
+        return res
+
+    def evaluate_ranking(self, data, metric_name="meanAveragePrecision", k=10, label_col=None, min_rating=None):
+        """Spark's RankingEvaluator(metricName=metric_name, k=k).evaluate of
+        the model's lists for the users of `data` (a float)."""
+        if metric_name not in self.RANKING_METRIC_NAMES:
+            raise ValueError(f"metric_name must be one of {', '.join(self.RANKING_METRIC_NAMES)} "
+                             f"(got {metric_name!r})")
+        return float(self.ranking_metrics(data, k, label_col, min_rating)[metric_name])
 
     # ----------------------------------------------------------- persistence
     def save_model(self, model_path="models/als"):

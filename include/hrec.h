@@ -14,6 +14,10 @@
  *   Spark  ALSModel.transform on a pair frame /
  *          RegressionEvaluator (no reference line)    -> hrec_als_predict_pairs,
  *                                                          hrec_als_pair_metrics
+ *   Spark  ALSModel.recommendForAllUsers / Items /
+ *          UserSubset / ItemSubset (no ref. line)     -> hrec_als_score_topk_pruned
+ *   Spark  RankingEvaluator / RankingMetrics
+ *          (no reference line)                        -> hrec_ranking_metrics
  *   Python/sklearn fusion     src/hybrid_system.py:57-75,108 -> hrec_fuse_topk
  *   Keras  two-tower graph    src/two_tower_model.py:38-89 -> hrec_tt_*
  *
@@ -295,6 +299,50 @@ int hrec_als_pair_metrics(const float* user_factors, int64_t n_user_rows,
                           const int64_t* user_rows, const int64_t* item_rows, int64_t n,
                           const double* labels, float* pred_out, double* sums_out,
                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* Spark 3.5 RankingMetrics with binary relevance over ranked id lists on the
+ * device (RankingEvaluator: precisionAtK, recallAtK, meanAveragePrecision,
+ * meanAveragePrecisionAtK, ndcgAtK). Additive to ABI 7.
+ *
+ * pred[r * pred_ld + i], i < len_r, is row r's list, best first; len_r =
+ * pred_len ? pred_len[r] (clamped to [0, pred_len_max]) : pred_len_max, with
+ * 0 <= pred_len_max <= 1024 and pred_ld >= pred_len_max; entries at i >= len_r
+ * are never read. Ids are raw int64 keys, any value is legal.
+ * labels[label_indptr[r] .. label_indptr[r + 1]) is row r's ground truth,
+ * sorted ascending; duplicates count once (Spark's lab.toSet): m_r distinct
+ * labels. 1 <= k <= 1024. gain[i] = 1 / ln(i + 2), i < k, and idcg[j] =
+ * gain[0] + ... + gain[j - 1], j <= k (k + 1 entries, idcg[0] = 0), are made
+ * by the caller on the host, so no device logarithm decides a bit.
+ *
+ * Per row, f64, hit(i) = pred[i] in labels, cnt(i) = hits at positions <= i:
+ *   precision = #{i < min(len, k): hit} / k     recall = the same count / m
+ *   AP    = sum_{hit i < len} cnt(i) / (i + 1), ascending i,  / m
+ *   AP@k  = the same over i < min(k, len),                    / min(m, k)
+ *   NDCG@k: n = min(max(len, m), k); sum_{hit i < min(n, len)} gain[i],
+ *           ascending i,                                      / idcg[min(m, n)]
+ * m = 0: all five are 0 and the row counts in HREC_RANK_N_EMPTY. per_row
+ * (optional, [n_rows][5] in this order) receives them; sums_out[HREC_RANK_SUMS]
+ * (device f64) the totals named below. *unsorted (device int32, written by the
+ * call) is 1 when some label row has a descending neighbour pair (the sums
+ * are then meaningless), else 0. No floating-point atomics: per-block
+ * partials in the workspace (the block count depends on n_rows alone), added
+ * in a fixed order by a second launch, so equal inputs give equal bits on
+ * every call. n_rows == 0 writes zeros.
+ * Workspace: hrec_ranking_metrics_workspace_bytes(n_rows). */
+#define HREC_RANK_N_ROWS 0        /* rows (users) seen, as f64, exact            */
+#define HREC_RANK_N_EMPTY 1       /* rows with an empty label set (all metrics 0)*/
+#define HREC_RANK_HITS 2          /* sum over rows of hits within the first k    */
+#define HREC_RANK_SUM_PRECISION 3
+#define HREC_RANK_SUM_RECALL 4
+#define HREC_RANK_SUM_AP 5        /* Spark meanAveragePrecision terms            */
+#define HREC_RANK_SUM_AP_K 6      /* meanAveragePrecisionAt(k) terms             */
+#define HREC_RANK_SUM_NDCG 7
+#define HREC_RANK_SUMS 8
+size_t hrec_ranking_metrics_workspace_bytes(int64_t n_rows);
+int hrec_ranking_metrics(const int64_t* pred, int64_t pred_ld, int pred_len_max, const int32_t* pred_len,
+                         const int64_t* label_indptr, const int64_t* labels, int64_t n_rows, int k,
+                         const double* gain, const double* idcg, double* per_row, double* sums_out,
+                         int32_t* unsorted, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Scoring consumed by a top-k, for whole item ranges (no id gather): the
  * same JVM-exact f32 dot as hrec_als_score for every (user, item j < n_items)
