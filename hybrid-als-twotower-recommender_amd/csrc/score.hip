@@ -251,6 +251,90 @@ __global__ __launch_bounds__(256) void sample_threshold_kernel(const float* __re
   }
 }
 
+// ------------------------------------------------- exclusion (seen items)
+// The exclusion set of row i is excl_cols[excl_indptr[r] .. excl_indptr[r + 1])
+// with r = row_ids[i] (r < 0: empty), columns ascending, duplicates allowed.
+// One wave per row, lanes striding the segment: vals[i][c] = fill for every
+// column c in [0, n) of the set (a column outside is skipped, never used as
+// an index), and the walk stops at the first stride that meets a column
+// >= n (ascending: nothing in range follows). kept_out (optional): min(len_cap,
+// n - distinct columns in [0, n)); a column counts where it differs from its
+// left neighbour.
+__global__ __launch_bounds__(256) void mask_rows_kernel(float* __restrict__ vals, int64_t n_rows, int64_t n,
+                                                        int64_t row_stride, const int64_t* __restrict__ row_ids,
+                                                        const int64_t* __restrict__ excl_indptr,
+                                                        const int32_t* __restrict__ excl_cols, float fill,
+                                                        int64_t len_cap, int32_t* __restrict__ kept_out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n_rows) return;  // wave-uniform
+  const int64_t r = row_ids[row];
+  const int64_t lo = r >= 0 ? excl_indptr[r] : 0, hi = r >= 0 ? excl_indptr[r + 1] : 0;
+  float* __restrict__ rv = vals + row * row_stride;
+  int64_t distinct = 0;
+  for (int64_t p0 = lo; p0 < hi; p0 += 64) {  // wave-uniform trip count
+    const int64_t p = p0 + lane;
+    bool counted = false, past = false;
+    if (p < hi) {
+      const int64_t c = excl_cols[p];
+      past = c >= n;
+      if (c >= 0 && !past) {
+        rv[c] = fill;  // duplicates store the same value
+        counted = p == lo || (int64_t)excl_cols[p - 1] != c;
+      }
+    }
+    distinct += __popcll(__ballot(counted));
+    if (__ballot(past)) break;
+  }
+  if (lane == 0 && kept_out) {
+    const int64_t kept = n - distinct;
+    kept_out[row] = (int32_t)(kept < len_cap ? kept : len_cap);
+  }
+}
+
+// The filter's candidates without the excluded items: one block per query, a
+// thread per candidate, a binary search of the query's ascending segment; an
+// excluded candidate's score becomes NaN (better() ranks NaN last, so the
+// top-k over the list passes it only after every candidate that stays).
+// out_len[b] = min(kk, candidates that stay), counted by ballots into an LDS
+// integer. A list past the cap (the filter raised *overflow) is read up to
+// the cap.
+__global__ __launch_bounds__(256) void drop_excluded_kernel(const int64_t* __restrict__ user_rows,
+                                                            const int64_t* __restrict__ excl_indptr,
+                                                            const int32_t* __restrict__ excl_cols,
+                                                            float* __restrict__ cand_v,
+                                                            const int64_t* __restrict__ cand_i,
+                                                            const int* __restrict__ cand_n, int cap, int kk,
+                                                            int32_t* __restrict__ out_len) {
+  __shared__ int s_kept;
+  const int b = blockIdx.x;
+  if (threadIdx.x == 0) s_kept = 0;
+  __syncthreads();
+  const int64_t r = user_rows[b];
+  const int64_t lo = r >= 0 ? excl_indptr[r] : 0, hi = r >= 0 ? excl_indptr[r + 1] : 0;
+  const int n = cand_n[b] < cap ? cand_n[b] : cap;
+  const float qnan = __builtin_nanf("");
+  for (int e0 = 0; e0 < n; e0 += blockDim.x) {  // block-uniform trip count: the ballots see whole waves
+    const int e = e0 + threadIdx.x;
+    bool keep = false;
+    if (e < n) {
+      const int64_t j = cand_i[(int64_t)b * cap + e];
+      int64_t a = lo, z = hi;  // the first position with a column >= j
+      while (a < z) {
+        const int64_t mid = a + ((z - a) >> 1);
+        if ((int64_t)excl_cols[mid] < j) a = mid + 1;
+        else z = mid;
+      }
+      keep = !(a < hi && (int64_t)excl_cols[a] == j);
+      if (!keep) cand_v[(int64_t)b * cap + e] = qnan;
+    }
+    const uint64_t m = __ballot(keep);
+    if (m && (threadIdx.x & 63) == 0) atomicAdd(&s_kept, __popcll(m));  // LDS, integer
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) out_len[b] = s_kept < kk ? s_kept : kk;
+}
+
 }  // namespace hrec
 
 using namespace hrec;
@@ -330,21 +414,40 @@ extern "C" size_t hrec_als_score_topk_workspace_bytes(int n_users, int64_t n_ite
   return score_layout(nullptr, n_users > 0 ? n_users : 0, n_items > 0 ? n_items : 0, score_kk(n_items, top_k)).total;
 }
 
-extern "C" int hrec_als_score_topk(const float* user_factors, const int64_t* user_rows, int n_users,
-                                   const float* item_factors_t, int64_t ld_items, int64_t n_items, int k, int kp,
-                                   int top_k, int64_t* out_idx, float* out_val, int* overflow, void* workspace,
-                                   size_t workspace_bytes, void* stream) {
-  HREC_REQUIRE(hrec_factor_ld_ok(kp), "als_score_topk: kp must be 16, 32, 64, 96, 128, 192 or 256");
-  HREC_REQUIRE(k >= 1 && k <= kp, "als_score_topk: need 1 <= k <= kp");
-  HREC_REQUIRE(n_users >= 0 && n_users < 65536 && n_items >= 0, "als_score_topk: bad shape");
+// The exclusion of a call (on: hrec_als_score_topk_excluding).
+struct ScoreExcl {
+  bool on;
+  const int64_t* indptr;
+  const int32_t* cols;
+  int32_t* out_len;
+};
+
+static int mask_rows_run(float* vals, int64_t n_rows, int64_t n, int64_t row_stride, const int64_t* row_ids,
+                         const ScoreExcl& x, float fill, int64_t len_cap, int32_t* kept_out, hipStream_t s) {
+  hipLaunchKernelGGL(mask_rows_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, s, vals, n_rows, n,
+                     row_stride, row_ids, x.indptr, x.cols, fill, len_cap, kept_out);
+  return check_launch("mask_rows_kernel");
+}
+
+// hrec_als_score_topk and hrec_als_score_topk_excluding (x.indptr set): the
+// same launches, the exclusion's two kernels between them.
+static int score_topk_run(const char* fn, const float* user_factors, const int64_t* user_rows, int n_users,
+                          const float* item_factors_t, int64_t ld_items, int64_t n_items, int k, int kp, int top_k,
+                          int64_t* out_idx, float* out_val, int* overflow, void* workspace, size_t workspace_bytes,
+                          const ScoreExcl& x, void* stream) {
+  const bool excl = x.on;
+  HREC_REQUIRE(hrec_factor_ld_ok(kp), "%s: kp must be 16, 32, 64, 96, 128, 192 or 256", fn);
+  HREC_REQUIRE(k >= 1 && k <= kp, "%s: need 1 <= k <= kp", fn);
+  HREC_REQUIRE(n_users >= 0 && n_users < 65536 && n_items >= 0, "%s: bad shape", fn);
   HREC_REQUIRE(ld_items >= n_items && ld_items % 4 == 0 && ld_items < ((int64_t)1 << 29),
-               "als_score_topk: ld_items must be >= n_items, %% 4 and < 2^29");
-  HREC_REQUIRE(top_k >= 1 && top_k <= 1024, "als_score_topk: top_k must be in [1, 1024]");
+               "%s: ld_items must be >= n_items, %% 4 and < 2^29", fn);
+  HREC_REQUIRE(top_k >= 1 && top_k <= 1024, "%s: top_k must be in [1, 1024]", fn);
   if (n_users == 0 || n_items == 0) return HREC_OK;
   HREC_REQUIRE(user_factors && user_rows && item_factors_t && out_idx && out_val && overflow && workspace,
-               "als_score_topk: null pointer");
+               "%s: null pointer", fn);
+  HREC_REQUIRE(!excl || (x.indptr && x.cols && x.out_len), "%s: null exclusion or out_len", fn);
   const size_t need = hrec_als_score_topk_workspace_bytes(n_users, n_items, top_k);
-  HREC_REQUIRE(workspace_bytes >= need, "als_score_topk: workspace %zu < %zu", workspace_bytes, need);
+  HREC_REQUIRE(workspace_bytes >= need, "%s: workspace %zu < %zu", fn, workspace_bytes, need);
   hipStream_t s = as_stream(stream);
   const int kk = (int)(top_k < n_items ? top_k : n_items);
   const int64_t S = n_items < kSample ? n_items : kSample;
@@ -358,6 +461,10 @@ extern "C" int hrec_als_score_topk(const float* user_factors, const int64_t* use
                        nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr);
     int rc = check_launch("als_score_fast_kernel");
     if (rc) return rc;
+    if (excl) {  // excluded scores -> NaN: ranked after every score that stays
+      rc = mask_rows_run(w.samp, n_users, n_items, n_items, user_rows, x, __builtin_nanf(""), kk, x.out_len, s);
+      if (rc) return rc;
+    }
     return topk_rows<float>(w.samp, n_users, n_items, n_items, kk, out_idx, out_val, w.tws, (size_t)1 << 62, s);
   }
   // 1) thresholds: the kk-th best of the first S items bounds the final kk-th from below
@@ -368,6 +475,12 @@ extern "C" int hrec_als_score_topk(const float* user_factors, const int64_t* use
                      nullptr, nullptr, nullptr, nullptr);
   int rc = check_launch("als_score_fast_kernel(sample)");
   if (rc) return rc;
+  if (excl) {
+    // the bound is over the sample's items that stay: excluded ones -> -inf (a
+    // query with fewer than kk left gets -inf and keeps every item)
+    rc = mask_rows_run(w.samp, n_users, S, S, user_rows, x, -__builtin_inff(), 0, nullptr, s);
+    if (rc) return rc;
+  }
   const float* thr = w.sv + (kk - 1);
   int thr_stride = kk;
   if (kk <= 64) {  // a lower bound suffices: the 64 lane maxima's kk-th
@@ -390,8 +503,48 @@ extern "C" int hrec_als_score_topk(const float* user_factors, const int64_t* use
                      thr, thr_stride, kCap, w.cv, w.ci, w.cn, overflow);
   rc = check_launch("als_score_fast_kernel(filter)");
   if (rc) return rc;
+  if (excl) {  // the filter also kept excluded items that reach the bound
+    hipLaunchKernelGGL(drop_excluded_kernel, dim3((unsigned)n_users), blk, 0, s, user_rows, x.indptr, x.cols, w.cv,
+                       w.ci, w.cn, kCap, kk, x.out_len);
+    rc = check_launch("drop_excluded_kernel");
+    if (rc) return rc;
+  }
   // 3) exact stable top-k over the candidates (original item index breaks ties)
   return topk_rows<float>(w.cv, n_users, kCap, kCap, kk, out_idx, out_val, w.fws, (size_t)1 << 62, s, w.ci, w.cn);
+}
+
+extern "C" int hrec_als_score_topk(const float* user_factors, const int64_t* user_rows, int n_users,
+                                   const float* item_factors_t, int64_t ld_items, int64_t n_items, int k, int kp,
+                                   int top_k, int64_t* out_idx, float* out_val, int* overflow, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  return score_topk_run("als_score_topk", user_factors, user_rows, n_users, item_factors_t, ld_items, n_items, k, kp,
+                        top_k, out_idx, out_val, overflow, workspace, workspace_bytes, ScoreExcl{}, stream);
+}
+
+// The exclusion lives in the caller's buffers: the workspace is the fused path's.
+extern "C" size_t hrec_als_score_topk_excluding_workspace_bytes(int n_users, int64_t n_items, int top_k) {
+  return hrec_als_score_topk_workspace_bytes(n_users, n_items, top_k);
+}
+
+extern "C" int hrec_als_score_topk_excluding(const float* user_factors, const int64_t* user_rows, int n_users,
+                                             const float* item_factors_t, int64_t ld_items, int64_t n_items, int k,
+                                             int kp, int top_k, const int64_t* excl_indptr, const int32_t* excl_cols,
+                                             int64_t* out_idx, float* out_val, int32_t* out_len, int* overflow,
+                                             void* workspace, size_t workspace_bytes, void* stream) {
+  return score_topk_run("als_score_topk_excluding", user_factors, user_rows, n_users, item_factors_t, ld_items,
+                        n_items, k, kp, top_k, out_idx, out_val, overflow, workspace, workspace_bytes,
+                        ScoreExcl{true, excl_indptr, excl_cols, out_len}, stream);
+}
+
+extern "C" int hrec_mask_rows_f32(float* vals, int64_t n_rows, int64_t n, int64_t row_stride, const int64_t* row_ids,
+                                  const int64_t* excl_indptr, const int32_t* excl_cols, float fill,
+                                  int32_t* kept_out, void* stream) {
+  HREC_REQUIRE(n_rows >= 0 && n >= 0 && row_stride >= n, "mask_rows_f32: bad shape");
+  HREC_REQUIRE(n < ((int64_t)1 << 31) && n_rows < ((int64_t)1 << 31), "mask_rows_f32: n and n_rows must be < 2^31");
+  if (n_rows == 0) return HREC_OK;
+  HREC_REQUIRE((vals || n == 0) && row_ids && excl_indptr && excl_cols && kept_out, "mask_rows_f32: null pointer");
+  return mask_rows_run(vals, n_rows, n, row_stride, row_ids, ScoreExcl{true, excl_indptr, excl_cols, nullptr}, fill,
+                       INT64_MAX, kept_out, as_stream(stream));
 }
 
 // ---------------------------------------------------- K2p: pruned ALS top-k

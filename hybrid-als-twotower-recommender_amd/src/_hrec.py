@@ -66,6 +66,10 @@ _SIGNATURES = {
     "hrec_als_score_topk_workspace_bytes": (_c_sz, [_c_i32, _c_i64, _c_i32]),
     "hrec_als_score_topk": (_c_i32, [_vp, _vp, _c_i32, _vp, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32, _vp, _vp, _vp,
                                      _vp, _c_sz, _vp]),
+    "hrec_als_score_topk_excluding_workspace_bytes": (_c_sz, [_c_i32, _c_i64, _c_i32]),
+    "hrec_als_score_topk_excluding": (_c_i32, [_vp, _vp, _c_i32, _vp, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32, _vp,
+                                               _vp, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "hrec_mask_rows_f32": (_c_i32, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
     "hrec_als_items_bf16_bytes": (_c_sz, [_c_i64, _c_i32]),
     "hrec_als_items_bf16": (_c_i32, [_vp, _c_i64, _c_i64, _c_i32, _vp, _c_sz, _vp]),
     "hrec_als_score_topk_pruned_workspace_bytes": (_c_sz, [_c_i32, _c_i64, _c_i32, _c_i32]),
@@ -617,6 +621,69 @@ def als_score_topk(user_factors, user_rows, item_factors_t, n_items, k, top_k, c
         scores = als_score(user_factors, user_rows, item_factors_t, None, n_items, k)
         return topk(scores, kk)
     return out_i, out_v
+
+
+def _excl_args(name, excl_indptr, excl_cols):
+    """The exclusion CSR's two pointers (an empty column list: a stand-in entry, never read)."""
+    if excl_cols.numel() == 0:
+        excl_cols = torch.zeros(1, dtype=torch.int32, device=excl_indptr.device)
+    return _dev(excl_indptr, torch.int64, f"{name}: excl_indptr"), _dev(excl_cols, torch.int32, f"{name}: excl_cols")
+
+
+def als_score_topk_excluding(user_factors, user_rows, item_factors_t, n_items, k, top_k, excl_indptr, excl_cols,
+                             overflow_out=None, workspace=None, out=None):
+    """als_score_topk over the items outside each query's exclusion set
+    (hrec_als_score_topk_excluding): (ids int64 [B, kk], scores f32 [B, kk],
+    lens int32 [B]), a list's entries past its length unspecified.
+    excl_indptr (int64) / excl_cols (int32, ascending per row): a CSR over the
+    rows of user_factors. The overflow flag (overflow_out, device int32 [1])
+    is the caller's to resolve: a set flag means als_score + mask_rows (NaN) +
+    topk. workspace (uint8 device, optional) is reused when large enough; out
+    (optional): the contiguous ([B, kk], [B, kk], [B]) tensors to write."""
+    kp = user_factors.shape[1]
+    B = user_rows.numel()
+    kk = min(int(top_k), int(n_items))
+    dev = user_factors.device
+    if excl_indptr.numel() != user_factors.shape[0] + 1:
+        raise HrecError("als_score_topk_excluding: excl_indptr must have one entry per factor row + 1")
+    if out is not None:
+        out_i, out_v, out_n = out
+        if tuple(out_i.shape) != (B, kk) or tuple(out_v.shape) != (B, kk) or out_n.numel() != B:
+            raise HrecError("als_score_topk_excluding: out must be two [B, kk] tensors and one [B]")
+    else:
+        out_i = torch.empty((B, kk), dtype=torch.int64, device=dev)
+        out_v = torch.empty((B, kk), dtype=torch.float32, device=dev)
+        out_n = torch.empty(B, dtype=torch.int32, device=dev)
+    flag = overflow_out if overflow_out is not None else torch.empty(1, dtype=torch.int32, device=dev)
+    need = int(lib().hrec_als_score_topk_excluding_workspace_bytes(B, n_items, kk))
+    ws = workspace if workspace is not None and workspace.numel() >= need else \
+        torch.empty(need, dtype=torch.uint8, device=dev)
+    _check("hrec_als_score_topk_excluding", lib().hrec_als_score_topk_excluding(
+        _dev(user_factors, torch.float32, "user_factors"), _dev(user_rows, torch.int64, "user_rows"), B,
+        _dev(item_factors_t, torch.float32, "item_factors_t"), item_factors_t.shape[1], n_items, int(k), kp, kk,
+        *_excl_args("als_score_topk_excluding", excl_indptr, excl_cols),
+        _dev(out_i, torch.int64, "out_idx"), _dev(out_v, torch.float32, "out_val"),
+        _dev(out_n, torch.int32, "out_len"), _dev(flag, torch.int32, "overflow"), _dev(ws, torch.uint8, "ws"),
+        ws.numel(), _stream()))
+    return out_i, out_v, out_n
+
+
+def mask_rows(vals, row_ids, excl_indptr, excl_cols, fill=float("nan")):
+    """vals[i, c] = fill (in place) for every column c of the exclusion set
+    of factor row row_ids[i] (hrec_mask_rows_f32; the CSR of
+    als_score_topk_excluding). vals: f32 [n_rows, n], unit column stride.
+    Returns int32 [n_rows]: n - the row's distinct in-range excluded columns."""
+    if vals.dtype != torch.float32 or not vals.is_cuda:
+        raise HrecError("mask_rows: vals must be an f32 device tensor")
+    if vals.dim() != 2 or vals.stride(1) != 1 or row_ids.numel() != vals.shape[0]:
+        raise HrecError("mask_rows: vals must be [n_rows, n] with one row id per row")
+    n_rows, n = vals.shape
+    kept = torch.empty(n_rows, dtype=torch.int32, device=vals.device)
+    _check("hrec_mask_rows_f32", lib().hrec_mask_rows_f32(
+        _vp(vals.data_ptr()), n_rows, n, max(int(vals.stride(0)), n),  # a one-row view may carry any stride
+        _dev(row_ids, torch.int64, "row_ids"), *_excl_args("mask_rows", excl_indptr, excl_cols),
+        ctypes.c_float(fill), _dev(kept, torch.int32, "kept_out"), _stream()))
+    return kept
 
 
 def als_items_bf16(item_factors, k):

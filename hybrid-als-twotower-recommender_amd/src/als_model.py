@@ -33,7 +33,10 @@ ALSModel.transform at :75) is replaced by libhrec's HIP kernels:
                       reference) -> DeviceALSFactors.recommend: batches of
                       4096 query rows through hrec_als_score_topk_pruned
                       (bf16 matrix-core bound + the JVM-exact chain), raw
-                      ids gathered on the device
+                      ids gathered on the device; with exclude= (a frame of
+                      seen pairs, e.g. the training frame) through
+                      hrec_als_score_topk_excluding: the exact chain over
+                      every pair, the seen items left out while ranking
   ranking_metrics / evaluate_ranking (Spark's RankingMetrics /
                       RankingEvaluator: MAP, MAP@k, precision@k, recall@k,
                       NDCG@k; not in the reference) -> recommend's lists,
@@ -179,7 +182,107 @@ class DeviceALSFactors:
             cache[side] = (Q, F, Ft, bf, ids)
         return cache[side]
 
-    def recommend(self, side, rows, num):
+    EXCLUSION_HOST_PAIRS = 1 << 16  # exclusion lists up to this many pairs are built on the host
+
+    @classmethod
+    def _exclusion_host(cls, side, known_users, known_items, user_ids, item_ids):
+        """exclusion() on the host: numpy (indptr int64, cols int32) from the
+        model's sorted ids and the pairs."""
+        u = cls._lookup(known_users, np.asarray(user_ids, np.int64).reshape(-1))
+        i = cls._lookup(known_items, np.asarray(item_ids, np.int64).reshape(-1))
+        if u.size != i.size:
+            raise ValueError("user_ids and item_ids must have the same length")
+        ok = (u >= 0) & (i >= 0)
+        r, c = (u[ok], i[ok]) if side == "user" else (i[ok], u[ok])
+        n_u, n_i = len(known_users), len(known_items)
+        n_rows, n_cols = (n_u, n_i) if side == "user" else (n_i, n_u)
+        key = np.unique(r * max(n_cols, 1) + c)  # ascending: by row, then by column
+        indptr = np.zeros(n_rows + 1, np.int64)
+        np.cumsum(np.bincount(key // max(n_cols, 1), minlength=n_rows), out=indptr[1:])
+        return indptr, (key % max(n_cols, 1)).astype(np.int32)
+
+    def exclusion(self, side, user_ids, item_ids):
+        """The exclusion CSR recommend(side, ..., exclude=) takes, from the
+        (user_ids[p], item_ids[p]) pairs of e.g. the training frame: device
+        (indptr int64 [n_side + 1], cols int32), a row's columns ascending and
+        distinct. Pairs with an id the model does not know are dropped,
+        duplicates removed. side "user": rows are user rows, columns item
+        rows; "item": the transpose. Built on the host up to
+        EXCLUSION_HOST_PAIRS pairs, on the device (one sort of 64-bit keys)
+        above; the ids may be numpy arrays or device tensors."""
+        if side not in ("user", "item"):
+            raise ValueError(f"side must be 'user' or 'item' (got {side!r})")
+        dev = self.U.device
+        on_dev = isinstance(user_ids, torch.Tensor)
+        n_pairs = int(user_ids.numel() if on_dev else np.asarray(user_ids).size)
+        n_u, n_i = len(self.user_ids), len(self.item_ids)
+        n_rows, n_cols = (n_u, n_i) if side == "user" else (n_i, n_u)
+        if not on_dev and n_pairs <= self.EXCLUSION_HOST_PAIRS:
+            indptr, cols = self._exclusion_host(side, self.user_ids, self.item_ids, user_ids, item_ids)
+            return torch.as_tensor(indptr, device=dev), torch.as_tensor(cols, device=dev)
+        u = self._lookup_device(user_ids if on_dev else np.asarray(user_ids, np.int64).reshape(-1), "user")
+        i = self._lookup_device(item_ids if isinstance(item_ids, torch.Tensor)
+                                else np.asarray(item_ids, np.int64).reshape(-1), "item")
+        if u.numel() != i.numel():
+            raise ValueError("user_ids and item_ids must have the same length")
+        r, c = (u, i) if side == "user" else (i, u)
+        key = r * max(n_cols, 1) + c
+        key = torch.unique(key[(r >= 0) & (c >= 0)])  # sorted
+        del u, i, r, c
+        indptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
+        if key.numel():
+            torch.cumsum(torch.bincount(torch.div(key, max(n_cols, 1), rounding_mode="floor"), minlength=n_rows), 0,
+                         out=indptr[1:])
+        return indptr, torch.remainder(key, max(n_cols, 1)).to(torch.int32)
+
+    def _recommend_excluding(self, side, rows, num, exclude):
+        """recommend() under an exclusion: (ids, scores, lens)."""
+        num = int(num)
+        if not 1 <= num <= self.RECOMMEND_MAX:
+            raise ValueError(f"num must be in [1, {self.RECOMMEND_MAX}] (got {num})")
+        Q, F, Ft, _, ids = self._recommend_operands(side)
+        dev = Q.device
+        indptr, cols = exclude
+        if indptr.numel() != Q.shape[0] + 1 or indptr.dtype != torch.int64 or cols.dtype != torch.int32:
+            raise ValueError(f"recommend: exclude must be exclusion('{side}', ...)'s (indptr int64 "
+                             f"[{Q.shape[0] + 1}], cols int32)")
+        rows = torch.as_tensor(rows, dtype=torch.int64, device=dev).reshape(-1).contiguous()
+        n, n_other = rows.numel(), int(F.shape[0])
+        kk = min(num, n_other)
+        out_i = torch.zeros((n, kk), dtype=torch.int64, device=dev)
+        out_v = torch.empty((n, kk), dtype=torch.float32, device=dev)
+        lens = torch.zeros(n, dtype=torch.int32, device=dev)
+        if n == 0 or kk == 0:
+            return out_i, out_v, lens
+        if bool(((rows < 0) | (rows >= Q.shape[0])).any().item()):
+            raise ValueError(f"recommend: a {side} row is outside [0, {Q.shape[0]})")
+        B = int(self.RECOMMEND_BATCH)
+        starts = range(0, n, B)
+        flags = torch.zeros(len(starts), dtype=torch.int32, device=dev)
+        need = int(_hrec.lib().hrec_als_score_topk_excluding_workspace_bytes(min(B, n), n_other, kk))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        for b, s in enumerate(starts):
+            _hrec.als_score_topk_excluding(Q, rows[s: s + B], Ft, n_other, self.k, kk, indptr, cols,
+                                           overflow_out=flags[b: b + 1], workspace=ws,
+                                           out=(out_i[s: s + B], out_v[s: s + B], lens[s: s + B]))
+        del ws
+        # one host read for all batches; a flagged batch is incomplete at every kk
+        sub = max(1, self.RECOMMEND_FALLBACK_BYTES // (4 * n_other))
+        for b in torch.nonzero(flags).reshape(-1).tolist():
+            lo, hi = starts[b], min(starts[b] + B, n)
+            for s in range(lo, hi, sub):
+                e = min(s + sub, hi)
+                scores = _hrec.als_score(Q, rows[s:e], Ft, None, n_other, self.k)
+                kept = _hrec.mask_rows(scores, rows[s:e], indptr, cols)
+                out_i[s:e], out_v[s:e] = _hrec.topk(scores, kk)
+                lens[s:e] = kept.clamp_(max=kk)
+                del scores
+        # past a list's length: id 0, score NaN (what the library left there is unspecified)
+        live = torch.arange(kk, device=dev).unsqueeze(0) < lens.unsqueeze(1)
+        out_ids = torch.where(live, ids[out_i.clamp_(0, n_other - 1)], torch.zeros_like(out_i))
+        return out_ids, torch.where(live, out_v, torch.full_like(out_v, float("nan"))), lens
+
+    def recommend(self, side, rows, num, exclude=None):
         """Top-`num` of the other side for each of `rows` (int64 row indices
         into `side`'s factor matrix, every one in range): device (ids int64
         [n, kk], scores f32 [n, kk]), kk = min(num, size of the other side).
@@ -191,7 +294,17 @@ class DeviceALSFactors:
         through hrec_als_score_topk_pruned on one workspace; for kk > 8 a
         batch whose overflow flag is set is redone through hrec_als_score +
         hrec_topk in sub-batches of at most RECOMMEND_FALLBACK_BYTES of
-        scores (kk <= 8: the library resolves it on the device)."""
+        scores (kk <= 8: the library resolves it on the device).
+        exclude (optional, exclusion(side, ...)'s pair): each list is the full
+        stable ranking with the row's excluded entries deleted, cut to num;
+        returns (ids, scores, lens int32 [n]) with lens = min(kk, size of the
+        other side - the row's excluded entries), and id 0 / score NaN past a
+        list's length. Those batches go through hrec_als_score_topk_excluding
+        (the exact chain over every pair; the pruned path has no exclusion),
+        and a flagged batch, at every kk, through hrec_als_score +
+        hrec_mask_rows_f32 + hrec_topk."""
+        if exclude is not None:
+            return self._recommend_excluding(side, rows, num, exclude)
         num = int(num)
         if not 1 <= num <= self.RECOMMEND_MAX:
             raise ValueError(f"num must be in [1, {self.RECOMMEND_MAX}] (got {num})")
@@ -803,7 +916,11 @@ class ALSModel:
             raise RuntimeError("the ALS model is not trained or loaded")
         return self.model
 
-    def _recommend_frame(self, side, subset, num):
+    def _exclusion(self, side, exclude):
+        """The device exclusion CSR of an `exclude` frame (columns userId, itemId)."""
+        return self.model.exclusion(side, _int_ids(exclude["userId"], "userId"), _int_ids(exclude["itemId"], "itemId"))
+
+    def _recommend_frame(self, side, subset, num, exclude=None):
         import pandas as pd
 
         model = self._trained()
@@ -817,35 +934,49 @@ class ALSModel:
             keys = np.unique(_int_ids(np.asarray(subset).reshape(-1), col))
             rows = model._lookup(ids, keys)
             rows = rows[rows >= 0]  # ids the model does not know are left out (Spark's join)
-        rec_ids, scores = model.recommend(side, rows, num)
+        if exclude is None:
+            (rec_ids, scores), lens = model.recommend(side, rows, num), None
+        else:
+            rec_ids, scores, lens = model.recommend(side, rows, num, exclude=self._exclusion(side, exclude))
         rec_ids, scores = rec_ids.cpu().numpy().tolist(), scores.cpu().numpy().tolist()
-        return pd.DataFrame({col: ids[rows], "recommendations": [list(zip(i, s)) for i, s in zip(rec_ids, scores)]})
+        recs = [list(zip(i, s)) for i, s in zip(rec_ids, scores)]
+        if lens is not None:  # each list cut to its length
+            recs = [rec[:m] for rec, m in zip(recs, lens.cpu().numpy().tolist())]
+        return pd.DataFrame({col: ids[rows], "recommendations": recs})
 
-    def recommend_for_all_users(self, num_items):
+    def recommend_for_all_users(self, num_items, exclude=None):
         """Spark's recommendForAllUsers: a DataFrame with one row per user
         of the model, `userId` ascending, and `recommendations`: the user's
         top num_items (1 .. 1024) items as (itemId: int, rating: float)
         tuples, best first; equal ratings keep the smaller itemId first. A
         rating is transform's f32 prediction for that pair. Scored and ranked
         on the device (DeviceALSFactors.recommend); on every rank of a
-        multi-GPU world the whole answer."""
-        return self._recommend_frame("user", None, num_items)
+        multi-GPU world the whole answer.
+        exclude (optional; here and in the three methods below): a DataFrame
+        with userId and itemId columns, typically the training frame. Its
+        pairs never appear in a list (the left-anti join Spark users apply to
+        the exploded recommendations, done while ranking): each list is the
+        full ranking without them, cut to num_items, so it is shorter than
+        num_items only when fewer entries remain; a row with everything
+        excluded keeps its row with an empty list. Pairs with an id the model
+        does not know, and repeated pairs, change nothing."""
+        return self._recommend_frame("user", None, num_items, exclude)
 
-    def recommend_for_all_items(self, num_users):
+    def recommend_for_all_items(self, num_users, exclude=None):
         """Spark's recommendForAllItems: per item (`itemId` ascending) its
         top num_users users as (userId, rating) tuples."""
-        return self._recommend_frame("item", None, num_users)
+        return self._recommend_frame("item", None, num_users, exclude)
 
-    def recommend_for_user_subset(self, users, num_items):
+    def recommend_for_user_subset(self, users, num_items, exclude=None):
         """Spark's recommendForUserSubset: recommend_for_all_users for the
         distinct ids of `users` (a DataFrame with a userId column, or an
         array-like of ids); ids unknown to the model are left out."""
-        return self._recommend_frame("user", users, num_items)
+        return self._recommend_frame("user", users, num_items, exclude)
 
-    def recommend_for_item_subset(self, items, num_users):
+    def recommend_for_item_subset(self, items, num_users, exclude=None):
         """Spark's recommendForItemSubset (a DataFrame with an itemId column,
         or an array-like of ids)."""
-        return self._recommend_frame("item", items, num_users)
+        return self._recommend_frame("item", items, num_users, exclude)
 
     # ----------------------------------------- RankingEvaluator / RankingMetrics
     RANKING_METRIC_NAMES = ("meanAveragePrecision", "meanAveragePrecisionAtK", "precisionAtK", "recallAtK",
@@ -874,7 +1005,7 @@ class ALSModel:
         torch.cumsum(counts, 0, out=indptr[1:])
         return uniq, indptr, it[order].contiguous()
 
-    def ranking_metrics(self, data, k=10, label_col=None, min_rating=None):
+    def ranking_metrics(self, data, k=10, label_col=None, min_rating=None, exclude=None):
         """Spark's RankingMetrics (binary relevance) of the model's top-k item
         lists against `data` (columns userId, itemId): {"meanAveragePrecision",
         "meanAveragePrecisionAtK", "precisionAtK", "recallAtK", "ndcgAtK",
@@ -887,7 +1018,12 @@ class ALSModel:
         users unknown to the model out and counts them in "dropped"; "nan"
         keeps them with an empty list (every metric 0 for them, as Spark gives
         for an empty prediction array). The lists never leave the device
-        (DeviceALSFactors.recommend -> hrec_ranking_metrics)."""
+        (DeviceALSFactors.recommend -> hrec_ranking_metrics).
+        exclude (optional): a DataFrame with userId and itemId columns,
+        typically the training frame of a held-out split; the lists are
+        ranked without its pairs (recommend_for_all_users' exclude), each
+        evaluated at its own length. An item of `data` that is also excluded
+        can never be hit and still counts in its user's set size."""
         k = int(k)
         if not 1 <= k <= _hrec.RANK_MAX:
             raise ValueError(f"k must be in [1, {_hrec.RANK_MAX}] (got {k})")
@@ -915,13 +1051,23 @@ class ALSModel:
         known = rows >= 0
         n_known = n if self.cold_start_strategy == "drop" else int(known.sum().item())
         pred_len = None
+        excl = self._exclusion("user", exclude) if exclude is not None else None
+
+        def lists(r):
+            """(ids, lens) of the rows' lists; lens None: every list is full."""
+            if excl is None:
+                return model.recommend("user", r, k)[0], None
+            top, _, lens = model.recommend("user", r, k, exclude=excl)
+            return top, lens
+
         if n_known == n:
-            pred, _ = model.recommend("user", rows, k)
+            pred, pred_len = lists(rows)
         else:  # "nan": an unknown user keeps its row, with an empty list
-            top, _ = model.recommend("user", rows[known], k)
+            top, top_len = lists(rows[known])
             pred = torch.zeros((n, max(int(top.shape[1]), 1)), dtype=torch.int64, device=dev)
             pred[known, : top.shape[1]] = top
-            pred_len = (known * int(top.shape[1])).to(torch.int32)
+            pred_len = torch.zeros(n, dtype=torch.int32, device=dev)
+            pred_len[known] = int(top.shape[1]) if top_len is None else top_len
         sums, unsorted, _ = _hrec.ranking_metrics(pred, indptr, labels, k, pred_len=pred_len,
                                                   pred_len_max=int(pred.shape[1]) if pred.numel() else 0)
         s = torch.cat([sums, unsorted.to(torch.float64)]).tolist()  # one host read
@@ -935,13 +1081,15 @@ class ALSModel:
             res[name] = s[slot] / n
         return res
 
-    def evaluate_ranking(self, data, metric_name="meanAveragePrecision", k=10, label_col=None, min_rating=None):
+    def evaluate_ranking(self, data, metric_name="meanAveragePrecision", k=10, label_col=None, min_rating=None,
+                         exclude=None):
         """Spark's RankingEvaluator(metricName=metric_name, k=k).evaluate of
-        the model's lists for the users of `data` (a float)."""
+        the model's lists for the users of `data` (a float); exclude as in
+        ranking_metrics."""
         if metric_name not in self.RANKING_METRIC_NAMES:
             raise ValueError(f"metric_name must be one of {', '.join(self.RANKING_METRIC_NAMES)} "
                              f"(got {metric_name!r})")
-        return float(self.ranking_metrics(data, k, label_col, min_rating)[metric_name])
+        return float(self.ranking_metrics(data, k, label_col, min_rating, exclude)[metric_name])
 
     # ----------------------------------------------------------- persistence
     def save_model(self, model_path="models/als"):

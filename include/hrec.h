@@ -16,6 +16,8 @@
  *                                                          hrec_als_pair_metrics
  *   Spark  ALSModel.recommendForAllUsers / Items /
  *          UserSubset / ItemSubset (no ref. line)     -> hrec_als_score_topk_pruned
+ *          the same minus a training frame's pairs    -> hrec_als_score_topk_excluding,
+ *                                                          hrec_mask_rows_f32
  *   Spark  RankingEvaluator / RankingMetrics
  *          (no reference line)                        -> hrec_ranking_metrics
  *   Python/sklearn fusion     src/hybrid_system.py:57-75,108 -> hrec_fuse_topk
@@ -360,6 +362,43 @@ int hrec_als_score_topk(const float* user_factors, const int64_t* user_rows,
                         int64_t n_items, int k, int kp, int top_k, int64_t* out_idx,
                         float* out_val, int* overflow, void* workspace,
                         size_t workspace_bytes, void* stream);
+
+/* hrec_als_score_topk over the items a query has not seen: the same chain
+ * over every pair, the same stable ranking, with the items of the query's
+ * exclusion set deleted from it (the left-anti join of the recommendations
+ * against a training frame). Additive to ABI 7.
+ *
+ * excl_indptr / excl_cols: a CSR over the factor rows of the query side; the
+ * set of query b is excl_cols[excl_indptr[r] .. excl_indptr[r + 1]) with r =
+ * user_rows[b], so one CSR serves every batch and subset. A row's columns are
+ * ascending; duplicates count once; a column outside [0, n_items) is ignored
+ * and never used as an index. out_len[b] (int32, device) = min(kk, n_items -
+ * distinct in-range excluded columns of b), kk = min(top_k, n_items); the
+ * entries of out_idx / out_val at positions >= out_len[b] are unspecified.
+ * The bound of hrec_als_score_topk is taken over the sample's items that
+ * stay (excluded sample scores are set to -inf first; a query with fewer
+ * than kk of them left gets -inf and keeps every item), the filter pass is
+ * the same, and the excluded candidates are taken out of the lists (NaN
+ * scores, ranked last) before the final top-k. *overflow as there: some query
+ * had more than 4096 candidates, excluded ones included; the result is
+ * incomplete and the caller falls back to hrec_als_score + hrec_mask_rows_f32
+ * (fill NaN) + hrec_topk_f32. Same limits on top_k, kp, ld_items and n_users;
+ * users must be known. The workspace is hrec_als_score_topk's. */
+size_t hrec_als_score_topk_excluding_workspace_bytes(int n_users, int64_t n_items, int top_k);
+int hrec_als_score_topk_excluding(const float* user_factors, const int64_t* user_rows, int n_users,
+                                  const float* item_factors_t, int64_t ld_items, int64_t n_items, int k,
+                                  int kp, int top_k, const int64_t* excl_indptr, const int32_t* excl_cols,
+                                  int64_t* out_idx, float* out_val, int32_t* out_len, int* overflow,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* The masking step of hrec_als_score_topk_excluding on a score matrix:
+ * vals[i * row_stride + c] = fill for every column c in [0, n) of the
+ * exclusion set of factor row row_ids[i] (a negative row id: the empty set);
+ * kept_out[i] (int32) = n - distinct in-range excluded columns. n and n_rows
+ * below 2^31, row_stride >= n. Additive to ABI 7. */
+int hrec_mask_rows_f32(float* vals, int64_t n_rows, int64_t n, int64_t row_stride, const int64_t* row_ids,
+                       const int64_t* excl_indptr, const int32_t* excl_cols, float fill,
+                       int32_t* kept_out, void* stream);
 
 /* Pruned form of hrec_als_score_topk (same outputs, same overflow contract):
  * the sample bound thr_b as there, then a bf16 matrix-core filter keeps
