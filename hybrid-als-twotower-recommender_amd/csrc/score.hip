@@ -569,6 +569,12 @@ extern "C" int hrec_mask_rows_f32(float* vals, int64_t n_rows, int64_t n, int64_
 //   3. the JVM chain over the kept items; those >= tau_b are the candidates,
 //      a superset of the top kk, ranked by the same stable top-k as the
 //      fused path (ties -> smaller item).
+// Under an exclusion (hrec_als_score_topk_pruned_excluding) step 1 takes the
+// kk-th best s~ over the sample's NON-EXCLUDED items (the excluded ones are set
+// to -inf first): kk non-excluded items have s~ >= t_b, hence chain >= t_b -
+// E_b >= tau_b, so the kk-th best non-excluded chain is >= tau_b; steps 2 and
+// 3 are unchanged (they also keep excluded items that reach the bound), and
+// the excluded candidates leave before the ranking (score_topk_pruned_run).
 // Users whose bound is not finite (a non-finite factor anywhere) or whose
 // kept list overflows raise *overflow: the caller's fallback (the
 // materialised scores + hrec_topk_f32) answers the call, as for the fused
@@ -988,7 +994,15 @@ __global__ __launch_bounds__(256) void als_bound_filter_kernel(const uint16_t* _
 // rounds of wave arg-best; absent entries -> (0, -1)), so the call skips the
 // list round trip and the top-k launch. cand_n[b] still counts the
 // candidates (the bench's diagnostics; > cap raises *overflow).
-template <int KK>
+// EXCL (hrec_als_score_topk_pruned_excluding): a candidate whose chain reaches
+// tau_b is looked up in the query's ascending exclusion segment (the binary
+// search of drop_excluded_kernel) and, when found, never enters the LDS list;
+// the ones that stay are counted by ballots (the loop's trip count is rounded
+// up to whole blocks so the ballots see whole waves) into s_n, an LDS integer,
+// which also reserves their slots: cand_n[b] and the overflow tests are then
+// over the candidates that stay, and out_len[b] = min(kk, s_n). Without EXCL
+// the three extra arguments are not read.
+template <int KK, bool EXCL>
 __global__ __launch_bounds__(256) void als_rescore_topk_kernel(const float* __restrict__ U, int kp,
                                                                const int64_t* __restrict__ user_rows, int n_users,
                                                                int k, const float* __restrict__ V, int64_t ldv,
@@ -997,7 +1011,10 @@ __global__ __launch_bounds__(256) void als_rescore_topk_kernel(const float* __re
                                                                const float* __restrict__ tau, int kk,
                                                                int64_t* __restrict__ out_idx,
                                                                float* __restrict__ out_val, int* __restrict__ cand_n,
-                                                               int* __restrict__ overflow) {
+                                                               int* __restrict__ overflow,
+                                                               const int64_t* __restrict__ excl_indptr,
+                                                               const int32_t* __restrict__ excl_cols,
+                                                               int32_t* __restrict__ out_len) {
 #pragma clang fp contract(off)
   constexpr int kL = 2048;  // candidates kept in LDS (more: *overflow, the caller's fallback)
   __shared__ __attribute__((aligned(16))) float su[kScoreKMax];
@@ -1018,23 +1035,58 @@ __global__ __launch_bounds__(256) void als_rescore_topk_kernel(const float* __re
     const float t = tau[b];
     const int kr = (k + 3) & ~3;
     const bool vec = (ldv & 3) == 0 && ((uintptr_t)V & 15) == 0;
-    for (int e = threadIdx.x; e < n; e += blockDim.x) {
-      const int64_t j = pre_i[(int64_t)b * cap + e];
-      const float* v = V + j * ldv;
+    int64_t xlo = 0, xhi = 0;
+    if constexpr (EXCL) {
+      xlo = excl_indptr[r];
+      xhi = excl_indptr[r + 1];
+    }
+    // EXCL: a block-uniform trip count, so the ballots below see whole waves
+    const int e_end = EXCL ? (int)((n + blockDim.x - 1) / blockDim.x * blockDim.x) : n;
+    for (int e = threadIdx.x; e < e_end; e += blockDim.x) {
       float acc = 0.f;
-      int c = 0;
-      if (vec) {
-        for (; c + 4 <= k; c += 4) {
-          const float4 x = *reinterpret_cast<const float4*>(v + c);
-          acc = acc + su[c] * x.x;
-          acc = acc + su[c + 1] * x.y;
-          acc = acc + su[c + 2] * x.z;
-          acc = acc + su[c + 3] * x.w;
+      int64_t j = 0;
+      bool pass = false;
+      if (!EXCL || e < n) {
+        j = pre_i[(int64_t)b * cap + e];
+        const float* v = V + j * ldv;
+        int c = 0;
+        if (vec) {
+          for (; c + 4 <= k; c += 4) {
+            const float4 x = *reinterpret_cast<const float4*>(v + c);
+            acc = acc + su[c] * x.x;
+            acc = acc + su[c + 1] * x.y;
+            acc = acc + su[c + 2] * x.z;
+            acc = acc + su[c + 3] * x.w;
+          }
         }
+        for (; c < k; ++c) acc = acc + su[c] * v[c];
+        for (; c < kr; ++c) acc = acc + 0.f * 0.f;
+        pass = acc >= t;
       }
-      for (; c < k; ++c) acc = acc + su[c] * v[c];
-      for (; c < kr; ++c) acc = acc + 0.f * 0.f;
-      if (acc >= t) {
+      if constexpr (EXCL) {
+        if (pass) {
+          int64_t a = xlo, z = xhi;  // the first position with a column >= j
+          while (a < z) {
+            const int64_t mid = a + ((z - a) >> 1);
+            if ((int64_t)excl_cols[mid] < j) a = mid + 1;
+            else z = mid;
+          }
+          pass = !(a < xhi && (int64_t)excl_cols[a] == j);
+        }
+        const uint64_t keep = __ballot(pass);
+        if (keep) {
+          int base = 0;
+          const int leader = __builtin_ctzll(keep);
+          if (lane == leader) base = atomicAdd(&s_n, __popcll(keep));  // LDS, integer
+          base = __shfl(base, leader, kWave);
+          const int p = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(keep >> 32),
+                                                              __builtin_amdgcn_mbcnt_lo((uint32_t)keep, 0u));
+          if (pass && p < kL) {
+            s_v[p] = acc;
+            s_j[p] = (int)j;
+          }
+        }
+      } else if (pass) {
         const int p = atomicAdd(&s_n, 1);  // LDS
         if (p < kL) {
           s_v[p] = acc;
@@ -1046,6 +1098,7 @@ __global__ __launch_bounds__(256) void als_rescore_topk_kernel(const float* __re
   __syncthreads();
   const int m = s_n;
   if (threadIdx.x == 0) {
+    if constexpr (EXCL) out_len[b] = m < kk ? m : kk;
     cand_n[b] = m;
     // fewer than kk candidates for a known user: tau_b was above the kk-th
     // best chain (a bound slip) -> the caller's exact fallback, never short ids
@@ -1317,25 +1370,55 @@ extern "C" int hrec_als_score_topk_pruned_counts(const void* workspace, int n_us
   return HREC_OK;
 }
 
-extern "C" int hrec_als_score_topk_pruned(const float* user_factors, const int64_t* user_rows, int n_users,
-                                          const float* item_factors_t, int64_t ld_items, const float* item_factors,
-                                          int64_t ld_v, const void* items_bf16, int64_t n_items, int k, int kp,
-                                          int top_k, int64_t* out_idx, float* out_val, int* overflow,
-                                          void* workspace, size_t workspace_bytes, void* stream) {
-  HREC_REQUIRE(hrec_factor_ld_ok(kp), "als_score_topk_pruned: kp must be 16, 32, 64, 96, 128, 192 or 256");
-  HREC_REQUIRE(k >= 1 && k <= kp, "als_score_topk_pruned: need 1 <= k <= kp");
-  HREC_REQUIRE(n_users >= 0 && n_users < 65536 && n_items >= 0, "als_score_topk_pruned: bad shape");
+// The small-catalogue path is hrec_als_score_topk_excluding's: the larger of the two needs.
+extern "C" size_t hrec_als_score_topk_pruned_excluding_workspace_bytes(int n_users, int64_t n_items, int top_k,
+                                                                       int k) {
+  const size_t own = hrec_als_score_topk_pruned_workspace_bytes(n_users, n_items, top_k, k);
+  const size_t fused = hrec_als_score_topk_excluding_workspace_bytes(n_users, n_items, top_k);
+  return own > fused ? own : fused;
+}
+
+// hrec_als_score_topk_pruned and hrec_als_score_topk_pruned_excluding (x.on):
+// the same launches, the exclusion behind x.on.
+//   Under an exclusion the sample bound is taken over the sample's items that
+//   stay: the bf16 scores s~ of the first S = min(n_items, 8192) items are
+//   materialised for every kk (the wave-tile maxima of the kk <= 64 form have
+//   no per-item score to mask), the query's excluded ones set to -inf, and t_b
+//   is the kk-th of the 64 lane maxima (kk <= 64) or the kk-th best (above) of
+//   what is left. Soundness: kk distinct non-excluded items have s~ >= t_b,
+//   hence chain >= t_b - E_b >= tau_b, so the kk-th best non-excluded chain is
+//   >= tau_b: every entry of the answer reaches tau_b, passes the filter at
+//   tau_b - E_b and the exact test, and is not dropped. A row with fewer than
+//   kk such sample items gets t_b = -inf, which pr_bounds turns into the
+//   overflow flag: the caller falls back. The filter also keeps excluded items
+//   that reach the bound; they leave after the exact chain (kk > 8:
+//   drop_excluded_kernel, NaN scores ranked last; kk <= 8: inside the fused
+//   rescore-and-rank kernel). als_rescore_kernel's "fewer than kk candidates"
+//   test counts before the drop and stays right: with a finite bound at least
+//   kk non-excluded items reach tau_b. Nothing is resolved on the device here:
+//   a set *overflow means the answer is incomplete at every kk.
+static int score_topk_pruned_run(const char* fn, const float* user_factors, const int64_t* user_rows, int n_users,
+                                 const float* item_factors_t, int64_t ld_items, const float* item_factors,
+                                 int64_t ld_v, const void* items_bf16, int64_t n_items, int k, int kp, int top_k,
+                                 int64_t* out_idx, float* out_val, int* overflow, void* workspace,
+                                 size_t workspace_bytes, const ScoreExcl& x, void* stream) {
+  const bool excl = x.on;
+  HREC_REQUIRE(hrec_factor_ld_ok(kp), "%s: kp must be 16, 32, 64, 96, 128, 192 or 256", fn);
+  HREC_REQUIRE(k >= 1 && k <= kp, "%s: need 1 <= k <= kp", fn);
+  HREC_REQUIRE(n_users >= 0 && n_users < 65536 && n_items >= 0, "%s: bad shape", fn);
   HREC_REQUIRE(ld_items >= n_items && ld_items % 4 == 0 && ld_items < ((int64_t)1 << 29),
-               "als_score_topk_pruned: ld_items must be >= n_items, %% 4 and < 2^29");
-  HREC_REQUIRE(ld_v >= k, "als_score_topk_pruned: ld_v must be >= k");
-  HREC_REQUIRE(top_k >= 1 && top_k <= 1024, "als_score_topk_pruned: top_k must be in [1, 1024]");
+               "%s: ld_items must be >= n_items, %% 4 and < 2^29", fn);
+  HREC_REQUIRE(ld_v >= k, "%s: ld_v must be >= k", fn);
+  HREC_REQUIRE(top_k >= 1 && top_k <= 1024, "%s: top_k must be in [1, 1024]", fn);
   if (n_users == 0 || n_items == 0) return HREC_OK;
   HREC_REQUIRE(user_factors && user_rows && item_factors_t && item_factors && items_bf16 && out_idx && out_val &&
                    overflow && workspace,
-               "als_score_topk_pruned: null pointer");
-  HREC_REQUIRE(((uintptr_t)items_bf16 & 255) == 0, "als_score_topk_pruned: items_bf16 must be 256-B aligned");
-  const size_t need = hrec_als_score_topk_pruned_workspace_bytes(n_users, n_items, top_k, k);
-  HREC_REQUIRE(workspace_bytes >= need, "als_score_topk_pruned: workspace %zu < %zu", workspace_bytes, need);
+               "%s: null pointer", fn);
+  HREC_REQUIRE(!excl || (x.indptr && x.cols && x.out_len), "%s: null exclusion or out_len", fn);
+  HREC_REQUIRE(((uintptr_t)items_bf16 & 255) == 0, "%s: items_bf16 must be 256-B aligned", fn);
+  const size_t need = excl ? hrec_als_score_topk_pruned_excluding_workspace_bytes(n_users, n_items, top_k, k)
+                           : hrec_als_score_topk_pruned_workspace_bytes(n_users, n_items, top_k, k);
+  HREC_REQUIRE(workspace_bytes >= need, "%s: workspace %zu < %zu", fn, workspace_bytes, need);
   hipStream_t s = as_stream(stream);
   const int kk = (int)(top_k < n_items ? top_k : n_items);
   // kk <= 8: a set *overflow is resolved here, on the device (the gated
@@ -1353,9 +1436,9 @@ extern "C" int hrec_als_score_topk_pruned(const float* user_factors, const int64
     return check_launch("als_exact_topk_kernel");
   };
   if (n_items <= kSample) {  // small: the fused path scores everything anyway
-    const int rc = hrec_als_score_topk(user_factors, user_rows, n_users, item_factors_t, ld_items, n_items, k, kp,
-                                       top_k, out_idx, out_val, overflow, workspace, workspace_bytes, stream);
-    return rc ? rc : exact_fallback();
+    const int rc = score_topk_run(fn, user_factors, user_rows, n_users, item_factors_t, ld_items, n_items, k, kp,
+                                  top_k, out_idx, out_val, overflow, workspace, workspace_bytes, x, stream);
+    return (rc || excl) ? rc : exact_fallback();
   }
   const int dk = prune_dk(k);
   const PruneWs w = prune_layout((char*)workspace, n_users, n_items, kk, dk);
@@ -1367,7 +1450,7 @@ extern "C" int hrec_als_score_topk_pruned(const float* user_factors, const int64
                      user_rows, n_users, k, dk, max_norm, w.uop, w.err, overflow);
   int rc = check_launch("als_prune_user_kernel");
   if (rc) return rc;
-  if (kk <= 64) {
+  if (kk <= 64 && !excl) {
     // per (user, 16 NI-item wave tile) maxima of the sample (no score
     // matrix), then the kk-th of their 64 lane maxima: kk distinct items of
     // the sample reach it; zeroes pn
@@ -1384,12 +1467,26 @@ extern "C" int hrec_als_score_topk_pruned(const float* user_factors, const int64
   } else {
     rc = dot_scores_run(w.uop, n_users, items_bf16, S, dk, 1, w.samp, S, s, kPruneSampleUB);
     if (rc) return rc;
-    rc = topk_rows<float>(w.samp, n_users, S, S, kk, w.si, w.sv, w.tws, (size_t)1 << 62, s);
-    if (rc == HREC_OK && hipMemsetAsync(w.pn, 0, (size_t)n_users * 4, s) != hipSuccess)
-      return check_launch("score_topk_pruned memset");
+    if (excl) {  // the bound is over the sample's items that stay: excluded ones -> -inf
+      rc = mask_rows_run(w.samp, n_users, S, S, user_rows, x, -__builtin_inff(), 0, nullptr, s);
+      if (rc) return rc;
+    }
+    const float* thr = w.sv + (kk - 1);
+    int thr_stride = kk;
+    if (kk <= 64) {  // (under an exclusion only) the 64 lane maxima's kk-th; zeroes pn
+      hipLaunchKernelGGL(sample_threshold_kernel, dim3((unsigned)((n_users + 3) / 4)), dim3(256), 0, s, w.samp,
+                         (int64_t)n_users, S, kk, w.sv, w.pn);
+      rc = check_launch("sample_threshold_kernel");
+      thr = w.sv;
+      thr_stride = 1;
+    } else {
+      rc = topk_rows<float>(w.samp, n_users, S, S, kk, w.si, w.sv, w.tws, (size_t)1 << 62, s);
+      if (rc == HREC_OK && hipMemsetAsync(w.pn, 0, (size_t)n_users * 4, s) != hipSuccess)
+        return check_launch("score_topk_pruned memset");
+    }
     if (rc) return rc;
     hipLaunchKernelGGL(als_prune_thr_kernel, dim3((unsigned)((n_users + 255) / 256)), dim3(256), 0, s, n_users,
-                       w.sv + (kk - 1), kk, w.err, w.tau, w.thr2, w.cn, overflow);
+                       thr, thr_stride, w.err, w.tau, w.thr2, w.cn, overflow);
     rc = check_launch("als_prune_thr_kernel");
     if (rc) return rc;
   }
@@ -1403,13 +1500,19 @@ extern "C" int hrec_als_score_topk_pruned(const float* user_factors, const int64
   // 3) the exact chain over the kept pairs -> candidates (chain >= tau_b);
   //    kk <= 8: ranked in the same block
   if (kk <= 8) {
-#define HREC_RTK(KK)                                                                                          \
-  hipLaunchKernelGGL(als_rescore_topk_kernel<KK>, dim3((unsigned)n_users), dim3(256), 0, s, user_factors, kp,      \
-                     user_rows, n_users, k, item_factors, ld_v, w.pi, w.pn, kCap, w.tau, kk, out_idx, out_val, w.cn, \
-                     overflow)
-    if (kk <= 2) HREC_RTK(2);
-    else if (kk <= 4) HREC_RTK(4);
-    else HREC_RTK(8);
+#define HREC_RTK(KK, EXCL)                                                                                     \
+  hipLaunchKernelGGL((als_rescore_topk_kernel<KK, EXCL>), dim3((unsigned)n_users), dim3(256), 0, s, user_factors,  \
+                     kp, user_rows, n_users, k, item_factors, ld_v, w.pi, w.pn, kCap, w.tau, kk, out_idx, out_val, \
+                     w.cn, overflow, x.indptr, x.cols, x.out_len)
+    if (excl) {  // the excluded candidates never enter the ranked list; writes out_len
+      if (kk <= 2) HREC_RTK(2, true);
+      else if (kk <= 4) HREC_RTK(4, true);
+      else HREC_RTK(8, true);
+      return check_launch("als_rescore_topk_kernel(excluding)");
+    }
+    if (kk <= 2) HREC_RTK(2, false);
+    else if (kk <= 4) HREC_RTK(4, false);
+    else HREC_RTK(8, false);
 #undef HREC_RTK
     rc = check_launch("als_rescore_topk_kernel");
     return rc ? rc : exact_fallback();
@@ -1418,6 +1521,35 @@ extern "C" int hrec_als_score_topk_pruned(const float* user_factors, const int64
                      n_users, k, item_factors, ld_v, w.pi, w.pn, kCap, w.tau, kk, w.cv, w.ci, w.cn, overflow);
   rc = check_launch("als_rescore_kernel");
   if (rc) return rc;
+  if (excl) {  // the filter also kept excluded items that reach the bound
+    hipLaunchKernelGGL(drop_excluded_kernel, dim3((unsigned)n_users), dim3(256), 0, s, user_rows, x.indptr, x.cols,
+                       w.cv, w.ci, w.cn, kCap, kk, x.out_len);
+    rc = check_launch("drop_excluded_kernel");
+    if (rc) return rc;
+  }
   // 4) the same exact stable top-k over the candidates
   return topk_rows<float>(w.cv, n_users, kCap, kCap, kk, out_idx, out_val, w.fws, (size_t)1 << 62, s, w.ci, w.cn);
+}
+
+extern "C" int hrec_als_score_topk_pruned(const float* user_factors, const int64_t* user_rows, int n_users,
+                                          const float* item_factors_t, int64_t ld_items, const float* item_factors,
+                                          int64_t ld_v, const void* items_bf16, int64_t n_items, int k, int kp,
+                                          int top_k, int64_t* out_idx, float* out_val, int* overflow,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+  return score_topk_pruned_run("als_score_topk_pruned", user_factors, user_rows, n_users, item_factors_t, ld_items,
+                               item_factors, ld_v, items_bf16, n_items, k, kp, top_k, out_idx, out_val, overflow,
+                               workspace, workspace_bytes, ScoreExcl{}, stream);
+}
+
+extern "C" int hrec_als_score_topk_pruned_excluding(const float* user_factors, const int64_t* user_rows, int n_users,
+                                                    const float* item_factors_t, int64_t ld_items,
+                                                    const float* item_factors, int64_t ld_v, const void* items_bf16,
+                                                    int64_t n_items, int k, int kp, int top_k,
+                                                    const int64_t* excl_indptr, const int32_t* excl_cols,
+                                                    int64_t* out_idx, float* out_val, int32_t* out_len, int* overflow,
+                                                    void* workspace, size_t workspace_bytes, void* stream) {
+  return score_topk_pruned_run("als_score_topk_pruned_excluding", user_factors, user_rows, n_users, item_factors_t,
+                               ld_items, item_factors, ld_v, items_bf16, n_items, k, kp, top_k, out_idx, out_val,
+                               overflow, workspace, workspace_bytes, ScoreExcl{true, excl_indptr, excl_cols, out_len},
+                               stream);
 }

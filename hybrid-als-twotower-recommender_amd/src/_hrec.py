@@ -76,6 +76,9 @@ _SIGNATURES = {
     "hrec_als_score_topk_pruned": (_c_i32, [_vp, _vp, _c_i32, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _c_i32,
                                             _c_i32, _c_i32, _vp, _vp, _vp, _vp, _c_sz, _vp]),
     "hrec_als_score_topk_pruned_counts": (_c_i32, [_vp, _c_i32, _c_i64, _c_i32, _c_i32, _vp, _vp]),
+    "hrec_als_score_topk_pruned_excluding_workspace_bytes": (_c_sz, [_c_i32, _c_i64, _c_i32, _c_i32]),
+    "hrec_als_score_topk_pruned_excluding": (_c_i32, [_vp, _vp, _c_i32, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _c_i32,
+                                                      _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
     "hrec_topk_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i32, _c_i32]),
     "hrec_topk_f32": (_c_i32, [_vp, _c_i64, _c_i64, _c_i64, _c_i32, _vp, _vp, _vp, _c_sz, _vp]),
     "hrec_topk_f64": (_c_i32, [_vp, _c_i64, _c_i64, _c_i64, _c_i32, _vp, _vp, _vp, _c_sz, _vp]),
@@ -740,8 +743,51 @@ def als_score_topk_pruned(user_factors, user_rows, item_factors_t, item_factors,
     return out_i, out_v
 
 
+def als_score_topk_pruned_excluding(user_factors, user_rows, item_factors_t, item_factors, items_bf16, n_items, k,
+                                    top_k, excl_indptr, excl_cols, overflow_out=None, workspace=None, out=None):
+    """als_score_topk_excluding with the bf16 matrix-core bound in front of
+    the exact chain (hrec_als_score_topk_pruned_excluding): the same (ids int64
+    [B, kk], scores f32 [B, kk], lens int32 [B]), a list's entries past its
+    length unspecified. The operands are als_score_topk_pruned's, the
+    exclusion CSR als_score_topk_excluding's. The overflow flag (overflow_out,
+    device int32 [1]) is the caller's to resolve at every top_k: a set flag
+    means the answer is incomplete and als_score_topk_excluding answers the
+    call. workspace (uint8 device, optional) is reused when large enough; out
+    (optional): the contiguous ([B, kk], [B, kk], [B]) tensors to write."""
+    kp = user_factors.shape[1]
+    B = user_rows.numel()
+    kk = min(int(top_k), int(n_items))
+    dev = user_factors.device
+    if item_factors.stride(1) != 1 or item_factors.shape[0] < n_items:
+        raise HrecError("als_score_topk_pruned_excluding: item_factors must be row-major with >= n_items rows")
+    if excl_indptr.numel() != user_factors.shape[0] + 1:
+        raise HrecError("als_score_topk_pruned_excluding: excl_indptr must have one entry per factor row + 1")
+    if out is not None:
+        out_i, out_v, out_n = out
+        if tuple(out_i.shape) != (B, kk) or tuple(out_v.shape) != (B, kk) or out_n.numel() != B:
+            raise HrecError("als_score_topk_pruned_excluding: out must be two [B, kk] tensors and one [B]")
+    else:
+        out_i = torch.empty((B, kk), dtype=torch.int64, device=dev)
+        out_v = torch.empty((B, kk), dtype=torch.float32, device=dev)
+        out_n = torch.empty(B, dtype=torch.int32, device=dev)
+    flag = overflow_out if overflow_out is not None else torch.empty(1, dtype=torch.int32, device=dev)
+    need = int(lib().hrec_als_score_topk_pruned_excluding_workspace_bytes(B, n_items, kk, int(k)))
+    ws = workspace if workspace is not None and workspace.numel() >= need else \
+        torch.empty(need, dtype=torch.uint8, device=dev)
+    _check("hrec_als_score_topk_pruned_excluding", lib().hrec_als_score_topk_pruned_excluding(
+        _dev(user_factors, torch.float32, "user_factors"), _dev(user_rows, torch.int64, "user_rows"), B,
+        _dev(item_factors_t, torch.float32, "item_factors_t"), item_factors_t.shape[1],
+        _dev(item_factors, torch.float32, "item_factors"), item_factors.stride(0),
+        _dev(items_bf16, torch.uint8, "items_bf16"), n_items, int(k), kp, kk,
+        *_excl_args("als_score_topk_pruned_excluding", excl_indptr, excl_cols),
+        _dev(out_i, torch.int64, "out_idx"), _dev(out_v, torch.float32, "out_val"),
+        _dev(out_n, torch.int32, "out_len"), _dev(flag, torch.int32, "overflow"), _dev(ws, torch.uint8, "ws"),
+        ws.numel(), _stream()))
+    return out_i, out_v, out_n
+
+
 def als_topk_pruned_counts(ws, B, n_items, top_k, k):
-    """Diagnostics of the last als_score_topk_pruned call on workspace ws:
+    """Diagnostics of the last als_score_topk_pruned(_excluding) call on workspace ws:
     (pairs the bf16 bound kept per user, candidates per user), int32 [B]
     each (hrec_als_score_topk_pruned_counts)."""
     out = torch.zeros(2 * B, dtype=torch.int32, device=ws.device)

@@ -35,8 +35,11 @@ ALSModel.transform at :75) is replaced by libhrec's HIP kernels:
                       (bf16 matrix-core bound + the JVM-exact chain), raw
                       ids gathered on the device; with exclude= (a frame of
                       seen pairs, e.g. the training frame) through
-                      hrec_als_score_topk_excluding: the exact chain over
-                      every pair, the seen items left out while ranking
+                      hrec_als_score_topk_pruned_excluding: the same bound
+                      over the unseen items of its sample, the seen items
+                      left out before ranking; a batch without a usable
+                      bound through hrec_als_score_topk_excluding (the
+                      exact chain over every pair)
   ranking_metrics / evaluate_ranking (Spark's RankingMetrics /
                       RankingEvaluator: MAP, MAP@k, precision@k, recall@k,
                       NDCG@k; not in the reference) -> recommend's lists,
@@ -158,7 +161,7 @@ class DeviceALSFactors:
         sums = _hrec.als_pair_metrics(self.U, self.V, urows, irows, self.k, y)
         return dict(zip(_hrec.PAIR_SUMS, sums.tolist()))
 
-    RECOMMEND_BATCH = 4096               # query rows per hrec_als_score_topk_pruned call
+    RECOMMEND_BATCH = 4096               # query rows per hrec_als_score_topk_pruned(_excluding) call
     RECOMMEND_FALLBACK_BYTES = 1 << 30   # the overflow fallback's score matrix stays under this (per sub-batch)
     RECOMMEND_MAX = 1024                 # largest list length (the library's top_k limit)
 
@@ -236,11 +239,17 @@ class DeviceALSFactors:
         return indptr, torch.remainder(key, max(n_cols, 1)).to(torch.int32)
 
     def _recommend_excluding(self, side, rows, num, exclude):
-        """recommend() under an exclusion: (ids, scores, lens)."""
+        """recommend() under an exclusion: (ids, scores, lens). Three levels,
+        each answering only the batches the one before flagged: the bf16-pruned
+        entry (hrec_als_score_topk_pruned_excluding), the exact chain over
+        every pair (hrec_als_score_topk_excluding), the materialised scores
+        (hrec_als_score + hrec_mask_rows_f32 + hrec_topk) in sub-batches. One
+        flag per batch and level; one host read after the last batch of the
+        first level, a second only if that one found a flag."""
         num = int(num)
         if not 1 <= num <= self.RECOMMEND_MAX:
             raise ValueError(f"num must be in [1, {self.RECOMMEND_MAX}] (got {num})")
-        Q, F, Ft, _, ids = self._recommend_operands(side)
+        Q, F, Ft, bf, ids = self._recommend_operands(side)
         dev = Q.device
         indptr, cols = exclude
         if indptr.numel() != Q.shape[0] + 1 or indptr.dtype != torch.int64 or cols.dtype != torch.int32:
@@ -259,16 +268,24 @@ class DeviceALSFactors:
         B = int(self.RECOMMEND_BATCH)
         starts = range(0, n, B)
         flags = torch.zeros(len(starts), dtype=torch.int32, device=dev)
-        need = int(_hrec.lib().hrec_als_score_topk_excluding_workspace_bytes(min(B, n), n_other, kk))
+        # the pruned query covers the exact entry's need: one workspace for both levels
+        need = int(_hrec.lib().hrec_als_score_topk_pruned_excluding_workspace_bytes(min(B, n), n_other, kk, self.k))
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         for b, s in enumerate(starts):
+            _hrec.als_score_topk_pruned_excluding(Q, rows[s: s + B], Ft, F, bf, n_other, self.k, kk, indptr, cols,
+                                                  overflow_out=flags[b: b + 1], workspace=ws,
+                                                  out=(out_i[s: s + B], out_v[s: s + B], lens[s: s + B]))
+        # one host read for all batches; a flagged batch is incomplete at every kk
+        redo = torch.nonzero(flags).reshape(-1).tolist()
+        flags.zero_()
+        for b in redo:  # the exact chain over every pair of that batch
+            s = starts[b]
             _hrec.als_score_topk_excluding(Q, rows[s: s + B], Ft, n_other, self.k, kk, indptr, cols,
                                            overflow_out=flags[b: b + 1], workspace=ws,
                                            out=(out_i[s: s + B], out_v[s: s + B], lens[s: s + B]))
         del ws
-        # one host read for all batches; a flagged batch is incomplete at every kk
         sub = max(1, self.RECOMMEND_FALLBACK_BYTES // (4 * n_other))
-        for b in torch.nonzero(flags).reshape(-1).tolist():
+        for b in (torch.nonzero(flags).reshape(-1).tolist() if redo else ()):
             lo, hi = starts[b], min(starts[b] + B, n)
             for s in range(lo, hi, sub):
                 e = min(s + sub, hi)
@@ -299,10 +316,12 @@ class DeviceALSFactors:
         stable ranking with the row's excluded entries deleted, cut to num;
         returns (ids, scores, lens int32 [n]) with lens = min(kk, size of the
         other side - the row's excluded entries), and id 0 / score NaN past a
-        list's length. Those batches go through hrec_als_score_topk_excluding
-        (the exact chain over every pair; the pruned path has no exclusion),
-        and a flagged batch, at every kk, through hrec_als_score +
-        hrec_mask_rows_f32 + hrec_topk."""
+        list's length. Those batches go through
+        hrec_als_score_topk_pruned_excluding (the bf16 bound over the sample's
+        items that stay, the exact chain for the pairs it keeps); a flagged
+        batch, at every kk, through hrec_als_score_topk_excluding (the exact
+        chain over every pair), and one flagged there too through
+        hrec_als_score + hrec_mask_rows_f32 + hrec_topk."""
         if exclude is not None:
             return self._recommend_excluding(side, rows, num, exclude)
         num = int(num)

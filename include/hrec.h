@@ -16,7 +16,8 @@
  *                                                          hrec_als_pair_metrics
  *   Spark  ALSModel.recommendForAllUsers / Items /
  *          UserSubset / ItemSubset (no ref. line)     -> hrec_als_score_topk_pruned
- *          the same minus a training frame's pairs    -> hrec_als_score_topk_excluding,
+ *          the same minus a training frame's pairs    -> hrec_als_score_topk_pruned_excluding,
+ *                                                          hrec_als_score_topk_excluding,
  *                                                          hrec_mask_rows_f32
  *   Spark  RankingEvaluator / RankingMetrics
  *          (no reference line)                        -> hrec_ranking_metrics
@@ -432,6 +433,43 @@ int hrec_als_score_topk_pruned(const float* user_factors, const int64_t* user_ro
                                size_t workspace_bytes, void* stream);
 int hrec_als_score_topk_pruned_counts(const void* workspace, int n_users, int64_t n_items, int top_k, int k,
                                       int32_t* out, void* stream);
+
+/* hrec_als_score_topk_pruned over the items a query has not seen: the
+ * answer of hrec_als_score_topk_excluding (the full stable ranking, the
+ * query's excluded entries deleted, cut to kk = min(top_k, n_items); out_len[b]
+ * = min(kk, n_items - distinct in-range excluded columns of b); entries at
+ * positions >= out_len[b] unspecified) with the bf16 matrix-core bound in
+ * front of the exact chain. Additive to ABI 7. The exclusion CSR and out_len
+ * are those of hrec_als_score_topk_excluding, the operands and their checks
+ * those of hrec_als_score_topk_pruned.
+ *
+ * The bound is taken over the sample's items that stay: the bf16 scores of
+ * the first min(n_items, 8192) items are materialised at every top_k, the
+ * query's excluded ones set to -inf, and t_b is the kk-th of the 64 lane
+ * maxima (kk <= 64) or the kk-th best (above) of the rest: kk non-excluded
+ * items have chain >= t_b - E = tau_b, so the kk-th best non-excluded chain is
+ * >= tau_b. The filter at tau_b - E and the exact chain are unchanged (they
+ * also keep excluded items that reach the bound); the excluded candidates
+ * leave before the ranking (kk <= 8: inside the fused rescore-and-rank
+ * kernel; above: NaN scores, ranked last).
+ *
+ * *overflow: as for hrec_als_score_topk_pruned, and also when a query has
+ * fewer than kk non-excluded items among the sample's lane maxima / items
+ * (t_b = -inf: no bound). Nothing is resolved on the device here: a set
+ * *overflow means the answer is incomplete at every top_k, and the caller
+ * falls back to hrec_als_score_topk_excluding (and from there as it says).
+ * n_items <= 2048 takes hrec_als_score_topk_excluding itself; the workspace
+ * query returns the larger of the two needs. hrec_als_score_topk_pruned_counts
+ * reads this call's workspace too (for kk <= 8 the candidates are counted
+ * after the exclusion, above 8 before it). */
+size_t hrec_als_score_topk_pruned_excluding_workspace_bytes(int n_users, int64_t n_items, int top_k, int k);
+int hrec_als_score_topk_pruned_excluding(const float* user_factors, const int64_t* user_rows, int n_users,
+                                         const float* item_factors_t, int64_t ld_items,
+                                         const float* item_factors, int64_t ld_v, const void* items_bf16,
+                                         int64_t n_items, int k, int kp, int top_k,
+                                         const int64_t* excl_indptr, const int32_t* excl_cols,
+                                         int64_t* out_idx, float* out_val, int32_t* out_len, int* overflow,
+                                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------- top-k --
  * Stable descending top-k of each of n_rows rows (row i starts at
