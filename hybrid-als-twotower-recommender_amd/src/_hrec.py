@@ -131,6 +131,9 @@ _SIGNATURES.update({
     "hrec_dot_topk_workspace_bytes": (_c_sz, [_c_i32, _c_i64, _c_i32]),
     "hrec_dot_topk": (_c_i32, [_vp, _c_i32, _vp, _c_i64, _c_i32, _c_i32, _c_i32, _vp, _c_i64, _vp, _vp, _vp, _vp,
                                _c_sz, _vp]),
+    "hrec_dot_topk_excluding_workspace_bytes": (_c_sz, [_c_i32, _c_i64, _c_i32]),
+    "hrec_dot_topk_excluding": (_c_i32, [_vp, _c_i32, _vp, _c_i64, _c_i32, _c_i32, _c_i32, _vp, _c_i64, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
     "hrec_dot_filter": (_c_i32, [_vp, _c_i32, _vp, _c_i64, _c_i32, _c_i32, _vp, _c_i32, _c_i64, _c_i32, _vp, _vp,
                                  _vp, _vp]),
     "hrec_hybrid_scores_workspace_bytes": (_c_sz, [_c_i32, _c_i64]),
@@ -1021,6 +1024,68 @@ def dot_topk(U, V, top_k, idx_offset=0, max_rounds=2):
             oi.copy_(ci)
             ov.copy_(cv)
     return out_i, out_v
+
+
+DOT_FALLBACK_BYTES = 1 << 30  # dot_topk_excluding's materialised fallback keeps its score matrix under this
+
+
+def dot_topk_excluding(U, V, top_k, excl_rows, excl_indptr, excl_cols, idx_offset=0, max_rounds=2):
+    """dot_topk over the items outside each query's exclusion set
+    (hrec_dot_topk_excluding): (idx int64 [B, kk] (+ idx_offset), val f32
+    [B, kk], lens int32 [B]), kk = min(top_k, N); a list's entries past its
+    length are unspecified. Query b's set is excl_cols[excl_indptr[r] :
+    excl_indptr[r + 1]] with r = excl_rows[b] (int64 [B]; negative: empty);
+    columns int32, local item indices, ascending per row. Users go in chunks
+    of DOT_USER_CHUNK; an overflowed chunk is refined as in dot_topk (the
+    k-th best of the truncated ranking seeds the next round), and after
+    max_rounds the materialised chain answers it: hrec_dot_scores ->
+    hrec_mask_rows_f32 (NaN) -> hrec_topk_f32, in user sub-batches whose
+    score matrix stays under DOT_FALLBACK_BYTES."""
+    dk, bf = _dot_args(U, V)
+    B, N = U.shape[0], V.shape[0]
+    kk = min(int(top_k), int(N))
+    dev = U.device
+    if excl_rows.numel() != B:
+        raise HrecError("dot_topk_excluding: excl_rows must have one entry per query")
+    out_i = torch.empty((B, kk), dtype=torch.int64, device=dev)
+    out_v = torch.empty((B, kk), dtype=torch.float32, device=dev)
+    out_n = torch.zeros(B, dtype=torch.int32, device=dev)
+    if B == 0 or kk == 0:
+        return out_i, out_v, out_n
+    p_indptr, p_cols = _excl_args("dot_topk_excluding", excl_indptr, excl_cols)
+    for b0 in range(0, B, DOT_USER_CHUNK):
+        b1 = min(B, b0 + DOT_USER_CHUNK)
+        Ub, rows = U[b0:b1], excl_rows[b0:b1]
+        nb = b1 - b0
+        need = int(lib().hrec_dot_topk_excluding_workspace_bytes(nb, N, kk))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        oi, ov, on = out_i[b0:b1], out_v[b0:b1], out_n[b0:b1]
+        thr = None
+        for _ in range(max_rounds):
+            _check("hrec_dot_topk_excluding", lib().hrec_dot_topk_excluding(
+                _vp(Ub.data_ptr()), nb, _vp(V.data_ptr()), N, dk, bf, kk,
+                None if thr is None else _dev(thr, torch.float32, "thr"), int(idx_offset),
+                _dev(rows, torch.int64, "excl_rows"), p_indptr, p_cols,
+                _dev(oi, torch.int64, "out_idx"), _dev(ov, torch.float32, "out_val"),
+                _dev(on, torch.int32, "out_len"), _dev(flag, torch.int32, "overflow"), _dev(ws, torch.uint8, "ws"),
+                need, _stream()))
+            if int(flag.item()) == 0:
+                break
+            thr = ov[:, kk - 1].contiguous()
+        else:
+            del ws
+            sub = max(1, DOT_FALLBACK_BYTES // (4 * N))
+            for s in range(0, nb, sub):
+                e = min(s + sub, nb)
+                scores = dot_scores(Ub[s:e], V)
+                kept = mask_rows(scores, rows[s:e], excl_indptr, excl_cols)
+                ci, cv = topk(scores, kk)
+                oi[s:e] = ci + int(idx_offset)
+                ov[s:e] = cv
+                on[s:e] = kept.clamp_(max=kk)
+                del scores
+    return out_i, out_v, out_n
 
 
 def dot_filter(U, V, thr, thr_per=0, cap=8192):

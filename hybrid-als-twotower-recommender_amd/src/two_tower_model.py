@@ -7,6 +7,14 @@ kernels). Host-side feature assembly (_prepare_features, the MinMaxScaler on
 [price, average_review_rating]) is kept exactly, including the scaler refit
 on every _prepare_features call.
 
+Not in the reference (failures raise): recommend_for_users /
+recommend_for_all_users (top-n lists for many users in one device pass, with
+an optional seen-item exclusion), ranking_metrics / evaluate_ranking (Spark's
+five ranking metrics of those lists against a held-out frame) and candidates
+(the item tower's vectors of a frame, computed once) — hrec_dot_topk /
+hrec_dot_topk_excluding at widths 32 / 64 / 128 / 256, the materialised
+hrec_tt_score chain at any other width.
+
 Deviations from the committed reference (documented in DESIGN.md):
   * `if val_data:` on a DataFrame raises in the reference (D5); here
     val_data is tested with `is not None`, so EarlyStopping(patience=3,
@@ -26,7 +34,28 @@ from sklearn.model_selection import train_test_split  # noqa: F401  (reference i
 from sklearn.preprocessing import MinMaxScaler
 
 from . import _hrec
+from .als_model import ALSModel, _int_ids
 from .tt_engine import TABLES, DeviceTwoTower
+
+
+class TwoTowerCandidates:
+    """A candidate frame on the device (TwoTowerModel.candidates): item_ids
+    (numpy int64, frame order) and ids_dev (the same on the device), vectors
+    (f32 device [n, d], the item tower's outputs), and the stamp of the
+    weights they were built from: the engine object, its `iterations`, and
+    the fitted scaler's parameters (scale_, min_) the numeric inputs went
+    through."""
+
+    def __init__(self, item_ids, ids_dev, vectors, engine, iterations, scaler_stamp=None):
+        self.item_ids = item_ids
+        self.ids_dev = ids_dev
+        self.vectors = vectors
+        self.engine = engine
+        self.iterations = int(iterations)
+        self.scaler_stamp = scaler_stamp
+
+    def __len__(self):
+        return int(self.item_ids.size)
 
 
 class History:
@@ -301,6 +330,267 @@ class TwoTowerModel:
                 or not all(type(s) is pd.Series for s in ids)):
             return None
         return ids + [sub[c] for c in self._FAST_NUM_COLS]
+
+    # ------------------------------------- batch top-n lists / ranking metrics
+    # None of these has a counterpart in the reference: failures raise.
+    # Scoring route, by embedding_size d:
+    #   d in {32, 64, 128, 256}: the fused matrix-core top-k over f32 operands,
+    #     hrec_dot_topk (no exclusion) / hrec_dot_topk_excluding — its f32
+    #     scores are hrec_tt_score's fmaf chain in the same k order, i.e. the
+    #     bits predict_for_user gives;
+    #   any other d (the constructor default 50 among them): hrec_tt_score ->
+    #     hrec_mask_rows_f32 -> hrec_topk_f32 over materialised scores, in user
+    #     sub-batches of at most RECOMMEND_FALLBACK_BYTES — hrec_tt_score adds
+    #     those widths in the order k = 0 .. d-1, which the zero-padded
+    #     matrix-core operand would not reproduce.
+    RECOMMEND_MAX = 1024                 # largest list length (the library's top_k limit)
+    RECOMMEND_FALLBACK_BYTES = 1 << 30   # a materialised score matrix stays under this (per sub-batch)
+    EXCLUSION_HOST_PAIRS = 1 << 16       # exclusion lists up to this many pairs are built on the host
+    RANKING_HOST_ROWS = ALSModel.RANKING_HOST_ROWS
+    RANKING_METRIC_NAMES = ALSModel.RANKING_METRIC_NAMES
+
+    def candidates(self, item_features):
+        """The candidate frame on the device, for the methods below: its
+        itemId column (int64, frame order), the item tower's f32 vectors and a
+        stamp of the weights they come from. The item inputs are assembled as
+        predict_for_user assembles them (_ids, the fitted scaler's transform),
+        over the whole frame in one item_vectors call, so the vectors are bit
+        for bit those predict_for_user(u, item_features) scores with. Repeated
+        itemIds raise ValueError. Passing a TwoTowerCandidates checks its stamp
+        and returns it: RuntimeError after the weights moved on (a training
+        step) or the scaler was refitted to other parameters (_prepare_features
+        refits it on every call), since predict_for_user would then score
+        other vectors."""
+        if self.model is None:
+            raise RuntimeError("the two-tower model is not built or loaded")
+        if isinstance(item_features, TwoTowerCandidates):
+            if (item_features.engine is not self.model or item_features.iterations != self.model.iterations
+                    or item_features.scaler_stamp != self._scaler_stamp()):
+                raise RuntimeError("candidates: built from other weights or another scaler fit than the model holds "
+                                   "now; build them again")
+            return item_features
+        ids = _int_ids(item_features["itemId"], "itemId")
+        if np.unique(ids).size != ids.size:
+            raise ValueError("candidates: the frame repeats an itemId")
+        dev, sz = self.model.device, self.model.sizes
+        if ids.size == 0:
+            vec = torch.empty((0, int(self.embedding_size)), dtype=torch.float32, device=dev)
+        else:
+            num = _minmax_transform(self.scaler, item_features, ["price", "average_review_rating"])
+            vec = self.model.item_vectors(
+                torch.as_tensor(_ids(item_features["itemId"].values, sz["item_emb"], "item_id_in"), device=dev),
+                torch.as_tensor(_ids(item_features["manufacturer_id"].values, sz["man_emb"], "manufacturer_in"),
+                                device=dev),
+                torch.as_tensor(_ids(item_features["category_id"].values, sz["cat_emb"], "category_in"), device=dev),
+                torch.as_tensor(np.ascontiguousarray(np.asarray(num, dtype=np.float32).reshape(-1, 2)), device=dev))
+        return TwoTowerCandidates(ids, torch.as_tensor(ids, device=dev), vec, self.model, self.model.iterations,
+                                  self._scaler_stamp())
+
+    def _scaler_stamp(self):
+        """The fitted scaler's parameters as bytes (None before a fit)."""
+        sc = self.scaler
+        if not hasattr(sc, "scale_") or not hasattr(sc, "min_"):
+            return None
+        return (np.asarray(sc.scale_, np.float64).tobytes(), np.asarray(sc.min_, np.float64).tobytes())
+
+    @staticmethod
+    def _exclusion_csr(users, item_ids, excl_users, excl_items):
+        """The exclusion CSR of the (excl_users[p], excl_items[p]) pairs for
+        the queried `users` (int64, ascending, distinct) over a candidate
+        frame whose rows hold `item_ids` (int64, distinct, any order): numpy
+        (indptr int64 [len(users) + 1], cols int32). Row q is users[q]; the
+        columns are candidate FRAME ROW indices, ascending and distinct. Pairs
+        with a user outside `users` or an item outside the frame are dropped.
+        Pure numpy."""
+        users = np.asarray(users, np.int64).reshape(-1)
+        item_ids = np.asarray(item_ids, np.int64).reshape(-1)
+        eu = np.asarray(excl_users, np.int64).reshape(-1)
+        ei = np.asarray(excl_items, np.int64).reshape(-1)
+        if eu.size != ei.size:
+            raise ValueError("exclude: userId and itemId must have the same length")
+        n_rows, n_cols = users.size, item_ids.size
+        indptr = np.zeros(n_rows + 1, np.int64)
+        if n_rows == 0 or n_cols == 0 or eu.size == 0:
+            return indptr, np.zeros(0, np.int32)
+        order = np.argsort(item_ids, kind="stable")  # sorted position -> frame row
+        sorted_ids = item_ids[order]
+        pi = np.minimum(np.searchsorted(sorted_ids, ei), n_cols - 1)
+        pu = np.minimum(np.searchsorted(users, eu), n_rows - 1)
+        ok = (sorted_ids[pi] == ei) & (users[pu] == eu)
+        key = np.unique(pu[ok] * n_cols + order[pi[ok]])  # ascending: by row, then by frame row
+        np.cumsum(np.bincount(key // n_cols, minlength=n_rows), out=indptr[1:])
+        return indptr, (key % n_cols).astype(np.int32)
+
+    @staticmethod
+    def _exclusion_csr_device(users, item_ids, excl_users, excl_items, dev):
+        """_exclusion_csr on the device (one sort of 64-bit keys), as
+        DeviceALSFactors.exclusion builds large lists: device (indptr, cols)."""
+        users = torch.as_tensor(users, dtype=torch.int64, device=dev)
+        item_ids = torch.as_tensor(item_ids, dtype=torch.int64, device=dev)
+        eu = torch.as_tensor(excl_users, dtype=torch.int64, device=dev)
+        ei = torch.as_tensor(excl_items, dtype=torch.int64, device=dev)
+        n_rows, n_cols = users.numel(), item_ids.numel()
+        indptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
+        if n_rows == 0 or n_cols == 0 or eu.numel() == 0:
+            return indptr, torch.zeros(0, dtype=torch.int32, device=dev)
+        sorted_ids, order = torch.sort(item_ids, stable=True)
+        pi = torch.searchsorted(sorted_ids, ei).clamp_(max=n_cols - 1)
+        pu = torch.searchsorted(users, eu).clamp_(max=n_rows - 1)
+        ok = (sorted_ids[pi] == ei) & (users[pu] == eu)
+        key = torch.unique(pu[ok] * n_cols + order[pi[ok]])  # sorted
+        if key.numel():
+            torch.cumsum(torch.bincount(torch.div(key, n_cols, rounding_mode="floor"), minlength=n_rows), 0,
+                         out=indptr[1:])
+        return indptr, torch.remainder(key, n_cols).to(torch.int32)
+
+    def _exclusion(self, users, cand, exclude):
+        """The device exclusion CSR of an `exclude` frame (columns userId,
+        itemId) for the queried users over the candidates' frame rows."""
+        eu, ei = _int_ids(exclude["userId"], "userId"), _int_ids(exclude["itemId"], "itemId")
+        dev = self.model.device
+        if eu.size <= self.EXCLUSION_HOST_PAIRS:
+            indptr, cols = self._exclusion_csr(users, cand.item_ids, eu, ei)
+            return torch.as_tensor(indptr, device=dev), torch.as_tensor(cols, device=dev)
+        return self._exclusion_csr_device(users, cand.item_ids, eu, ei, dev)
+
+    def _query_users(self, users):
+        """The distinct user ids, ascending (int64); an id outside the user
+        table raises _ids's IndexError."""
+        if isinstance(users, pd.DataFrame):
+            users = users["userId"]
+        if self.model is None:
+            raise RuntimeError("the two-tower model is not built or loaded")
+        return np.unique(_ids(np.asarray(users).reshape(-1), self.model.sizes["user_emb"], "user_in").astype(np.int64))
+
+    def _recommend_device(self, users, cand, num, exclude=None):
+        """Top-`num` candidates for each of `users` (_query_users' array):
+        device (raw itemIds int64 [n, kk], scores f32 [n, kk], lens int32 [n]
+        or None when every list is full), kk = min(num, candidates). Past a
+        list's length: id 0, score NaN."""
+        num = int(num)
+        if not 1 <= num <= self.RECOMMEND_MAX:
+            raise ValueError(f"num_items must be in [1, {self.RECOMMEND_MAX}] (got {num})")
+        dev = self.model.device
+        n, N = int(users.size), int(cand.vectors.shape[0])
+        kk = min(num, N)
+        if n == 0 or kk == 0:
+            return (torch.zeros((n, kk), dtype=torch.int64, device=dev),
+                    torch.zeros((n, kk), dtype=torch.float32, device=dev),
+                    None if exclude is None else torch.zeros(n, dtype=torch.int32, device=dev))
+        excl = self._exclusion(users, cand, exclude) if exclude is not None else None
+        U = self.model.user_vectors(torch.as_tensor(users.astype(np.int32), device=dev))
+        V = cand.vectors
+        rows = torch.arange(n, dtype=torch.int64, device=dev)  # query q reads exclusion row q
+        lens = None
+        if int(self.embedding_size) in _hrec.DOT_DK:
+            if excl is None:
+                idx, val = _hrec.dot_topk(U, V, kk)
+            else:
+                idx, val, lens = _hrec.dot_topk_excluding(U, V, kk, rows, *excl)
+        else:
+            idx = torch.empty((n, kk), dtype=torch.int64, device=dev)
+            val = torch.empty((n, kk), dtype=torch.float32, device=dev)
+            lens = None if excl is None else torch.empty(n, dtype=torch.int32, device=dev)
+            sub = max(1, self.RECOMMEND_FALLBACK_BYTES // (4 * N))
+            for s in range(0, n, sub):
+                e = min(s + sub, n)
+                scores = _hrec.tt_score(U[s:e].contiguous(), V)
+                if excl is not None:
+                    lens[s:e] = _hrec.mask_rows(scores, rows[s:e], *excl).clamp_(max=kk)
+                idx[s:e], val[s:e] = _hrec.topk(scores, kk)
+                del scores
+        if lens is None:
+            return cand.ids_dev[idx], val, None
+        live = torch.arange(kk, device=dev).unsqueeze(0) < lens.unsqueeze(1)
+        ids = torch.where(live, cand.ids_dev[idx.clamp_(0, N - 1)], torch.zeros_like(idx))
+        return ids, torch.where(live, val, torch.full_like(val, float("nan"))), lens
+
+    def recommend_for_users(self, users, item_features, num_items, exclude=None):
+        """Top-n lists for many users in one device pass: a DataFrame with
+        `userId` (the distinct ids of `users`, ascending; a DataFrame with a
+        userId column or an array-like) and `recommendations`: the user's top
+        num_items (1 .. 1024) candidates of `item_features` (a frame, or
+        candidates()'s object) as (itemId, rating) tuples, best first. A rating
+        is the f32 predict_for_user gives that pair over the same frame; equal
+        ratings keep frame order (what Python's stable sorted(...,
+        reverse=True) gives predict_for_user's list). A user id outside [0,
+        num_users) raises IndexError.
+        exclude (optional): a DataFrame with userId and itemId columns,
+        typically the training frame. Its pairs never appear: each list is the
+        full ranking without them, cut to num_items, shorter only when fewer
+        entries remain; a user with everything excluded keeps its row with an
+        empty list. Pairs with a user outside the table or an item not in the
+        candidate frame, and repeated pairs, change nothing.
+        embedding_size 32 / 64 / 128 / 256 takes the fused matrix-core top-k
+        (hrec_dot_topk / hrec_dot_topk_excluding); any other width, the
+        default 50 included, the materialised hrec_tt_score chain (see the
+        note above)."""
+        cand = self.candidates(item_features)
+        users = self._query_users(users)
+        ids, val, lens = self._recommend_device(users, cand, num_items, exclude)
+        ids, val = ids.cpu().numpy().tolist(), val.cpu().numpy().tolist()
+        recs = [list(zip(i, s)) for i, s in zip(ids, val)]
+        if lens is not None:  # each list cut to its length
+            recs = [rec[:m] for rec, m in zip(recs, lens.cpu().numpy().tolist())]
+        return pd.DataFrame({"userId": users, "recommendations": recs})
+
+    def recommend_for_all_users(self, item_features, num_items, exclude=None):
+        """recommend_for_users for users 0 .. num_users - 1."""
+        return self.recommend_for_users(np.arange(int(self.num_users), dtype=np.int64), item_features, num_items,
+                                        exclude)
+
+    def ranking_metrics(self, data, item_features, k=10, label_col=None, min_rating=None, exclude=None):
+        """Spark's RankingMetrics (binary relevance) of the model's top-k
+        lists over `item_features` against `data` (columns userId, itemId):
+        ALSModel.RANKING_METRIC_NAMES' five metrics plus "count", with
+        ALSModel.ranking_metrics' semantics. A user's ground truth is the set
+        of its itemIds in `data` — with min_rating, of the rows whose
+        label_col (default average_review_rating) is >= min_rating; a user
+        left with no row does not appear. Items absent from the candidate
+        frame stay in the set: never hit, counted in its size. Each metric is
+        the mean over the `count` users (NaN when count is 0). exclude as in
+        recommend_for_users; each list is evaluated at its own length. A user
+        id outside the table raises IndexError. The lists go from the top-k
+        into hrec_ranking_metrics without leaving the device."""
+        k = int(k)
+        if not 1 <= k <= _hrec.RANK_MAX:
+            raise ValueError(f"k must be in [1, {_hrec.RANK_MAX}] (got {k})")
+        cand = self.candidates(item_features)
+        users, items = _int_ids(data["userId"], "userId"), _int_ids(data["itemId"], "itemId")
+        if min_rating is not None:
+            keep = np.asarray(data[label_col or "average_review_rating"], np.float64) >= float(min_rating)
+            users, items = users[keep], items[keep]
+        _ids(users, self.model.sizes["user_emb"], "user_in")  # range check (IndexError)
+        dev = self.model.device
+        build = ALSModel._label_csr_host if users.size <= self.RANKING_HOST_ROWS else ALSModel._label_csr_device
+        uniq, indptr, labels = build(users, items, dev)
+        n = int(uniq.numel())
+        res = {name: float("nan") for name in self.RANKING_METRIC_NAMES}
+        res["count"] = n
+        if n == 0:
+            return res
+        pred, _, pred_len = self._recommend_device(uniq.cpu().numpy(), cand, k, exclude)
+        sums, unsorted, _ = _hrec.ranking_metrics(pred, indptr, labels, k, pred_len=pred_len,
+                                                  pred_len_max=int(pred.shape[1]) if pred.numel() else 0)
+        s = torch.cat([sums, unsorted.to(torch.float64)]).tolist()  # one host read
+        if s[-1] != 0.0:
+            raise RuntimeError("ranking_metrics: a label row is not sorted ascending")
+        s = dict(zip(_hrec.RANK_SUMS, s))
+        if int(s["n_rows"]) != n:
+            raise RuntimeError(f"ranking_metrics: {int(s['n_rows'])} rows evaluated, {n} expected")
+        for name, slot in zip(self.RANKING_METRIC_NAMES, ("sum_ap", "sum_ap_k", "sum_precision", "sum_recall",
+                                                          "sum_ndcg")):
+            res[name] = s[slot] / n
+        return res
+
+    def evaluate_ranking(self, data, item_features, metric_name="meanAveragePrecision", k=10, label_col=None,
+                         min_rating=None, exclude=None):
+        """Spark's RankingEvaluator(metricName=metric_name, k=k).evaluate of
+        the model's lists for the users of `data` (a float)."""
+        if metric_name not in self.RANKING_METRIC_NAMES:
+            raise ValueError(f"metric_name must be one of {', '.join(self.RANKING_METRIC_NAMES)} "
+                             f"(got {metric_name!r})")
+        return float(self.ranking_metrics(data, item_features, k, label_col, min_rating, exclude)[metric_name])
 
     # --------------------------------------------------------- persistence
     def save_model(self, model_path="models/twotower.keras"):

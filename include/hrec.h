@@ -23,6 +23,9 @@
  *          (no reference line)                        -> hrec_ranking_metrics
  *   Python/sklearn fusion     src/hybrid_system.py:57-75,108 -> hrec_fuse_topk
  *   Keras  two-tower graph    src/two_tower_model.py:38-89 -> hrec_tt_*
+ *   Keras  Dot + sorted(...)[:k] for many users        -> hrec_dot_topk
+ *          the same minus a training frame's pairs
+ *          (no reference line)                        -> hrec_dot_topk_excluding
  *
  * Conventions (all functions):
  *   - every pointer is a DEVICE pointer owned by the caller, except where a
@@ -722,6 +725,40 @@ int hrec_dot_topk(const void* user_vec, int n_users, const void* item_vec, int64
                   int dtype, int top_k, const float* thr_in, int64_t idx_offset, int64_t* out_idx,
                   float* out_val, int* overflow, void* workspace, size_t workspace_bytes,
                   void* stream);
+/* hrec_dot_topk over the items a query has not seen: the same scores (the
+ * bits hrec_dot_scores gives each pair), the same stable ranking, with the
+ * items of the query's exclusion set deleted from it, cut to kk = min(top_k,
+ * n_items). Additive to ABI 7.
+ *
+ * The set of query b is excl_cols[excl_indptr[r] .. excl_indptr[r + 1]) with
+ * r = excl_rows[b] (a negative r: the empty set) — hrec_mask_rows_f32's
+ * convention. Columns are LOCAL item indices in [0, n_items), before
+ * idx_offset is added; ascending; duplicates count once; a column outside the
+ * range is ignored and never used as an index. out_len[b] (int32, device) =
+ * min(kk, n_items - distinct in-range excluded columns of b), computed from
+ * the exclusion row; the entries of out_idx / out_val at positions >=
+ * out_len[b] are unspecified.
+ * Catalogues hrec_dot_topk scores in full (n_items <= 16384, no thr_in): the
+ * excluded scores become NaN (ranked last) before the exact top-k. Otherwise
+ * the bound is the kk-th best of the strided sample's items that stay (the
+ * sample columns of excluded items are set to -inf first; a query with fewer
+ * than kk of them left gets -inf and admits every score), the three filter
+ * kernels run unchanged, and the excluded candidates leave the lists (NaN
+ * scores) before the final top-k. *overflow as hrec_dot_topk sets it: some
+ * query had more survivors than its list holds, excluded ones included.
+ * thr_in keeps its meaning (a NaN entry admits every score); after an
+ * overflowed round out_val[:, kk - 1] is again a valid higher bound — NaN,
+ * which admits everything, when fewer than kk non-excluded entries sat in the
+ * truncated list — so the refinement round of hrec_dot_topk carries over. A
+ * caller out of rounds falls back to hrec_dot_scores + hrec_mask_rows_f32
+ * (fill NaN) + hrec_topk_f32. Operands, limits and workspace size are
+ * hrec_dot_topk's. */
+size_t hrec_dot_topk_excluding_workspace_bytes(int n_users, int64_t n_items, int top_k);
+int hrec_dot_topk_excluding(const void* user_vec, int n_users, const void* item_vec, int64_t n_items,
+                            int dk, int dtype, int top_k, const float* thr_in, int64_t idx_offset,
+                            const int64_t* excl_rows, const int64_t* excl_indptr, const int32_t* excl_cols,
+                            int64_t* out_idx, float* out_val, int32_t* out_len, int* overflow,
+                            void* workspace, size_t workspace_bytes, void* stream);
 /* The survivor filter of hrec_dot_topk / the pruned hybrid alone: append
  * (score, j) of every item j with <U[b], V[j]> >= thr[b * thr_stride + (thr_per
  * ? j / thr_per : 0)] to user b's list (cand_val / cand_idx [n_users, cap]; a
