@@ -601,6 +601,65 @@ def ranking_metrics(pred, label_indptr, labels, k, pred_len=None, pred_len_max=N
     return sums, unsorted, per_row
 
 
+def _excl_args(name, excl_indptr, excl_cols):
+    """The exclusion CSR's two pointers (an empty column list: a stand-in entry, never read)."""
+    if excl_cols.numel() == 0:
+        excl_cols = torch.zeros(1, dtype=torch.int32, device=excl_indptr.device)
+    return _dev(excl_indptr, torch.int64, f"{name}: excl_indptr"), _dev(excl_cols, torch.int32, f"{name}: excl_cols")
+
+
+def _als_topk(user_factors, user_rows, item_factors_t, n_items, k, top_k, pruned=None, excl=None,
+              check_overflow=False, overflow_out=None, workspace=None, out=None):
+    """The body of the four als_score_topk* wrappers: entry hrec_als_score_topk
+    + "_pruned" with pruned = (item_factors, items_bf16) + "_excluding" with
+    excl = (excl_indptr, excl_cols). Checks the shapes and `out`, allocates
+    what the caller did not pass, calls the entry; check_overflow reads the
+    flag and answers a set one from the full score matrix (the pruned entries
+    resolve top_k <= 8 on the device: no read there)."""
+    entry = "hrec_als_score_topk" + ("_pruned" if pruned else "") + ("_excluding" if excl else "")
+    name = entry[5:]
+    kp = user_factors.shape[1]
+    B = user_rows.numel()
+    kk = min(int(top_k), int(n_items))
+    dev = user_factors.device
+    if pruned and (pruned[0].stride(1) != 1 or pruned[0].shape[0] < n_items):
+        raise HrecError(f"{name}: item_factors must be row-major with >= n_items rows")
+    if excl and excl[0].numel() != user_factors.shape[0] + 1:
+        raise HrecError(f"{name}: excl_indptr must have one entry per factor row + 1")
+    if out is None:
+        out = (torch.empty((B, kk), dtype=torch.int64, device=dev),
+               torch.empty((B, kk), dtype=torch.float32, device=dev))
+        if excl:
+            out += (torch.empty(B, dtype=torch.int32, device=dev),)
+    elif (tuple(out[0].shape) != (B, kk) or tuple(out[1].shape) != (B, kk) or check_overflow
+          or (excl and out[2].numel() != B)):
+        raise HrecError(f"{name}: out must be two [B, kk] tensors"
+                        + (" and one [B]" if excl else ", with check_overflow=False"))
+    # zeroed by the library on the stream
+    flag = overflow_out if overflow_out is not None else torch.empty(1, dtype=torch.int32, device=dev)
+    query = getattr(lib(), entry + "_workspace_bytes")
+    need = int(query(B, n_items, kk, int(k)) if pruned else query(B, n_items, kk))
+    ws = workspace if workspace is not None and workspace.numel() >= need else \
+        torch.empty(need, dtype=torch.uint8, device=dev)
+    args = [_dev(user_factors, torch.float32, "user_factors"), _dev(user_rows, torch.int64, "user_rows"), B,
+            _dev(item_factors_t, torch.float32, "item_factors_t"), item_factors_t.shape[1]]
+    if pruned:
+        args += [_dev(pruned[0], torch.float32, "item_factors"), pruned[0].stride(0),
+                 _dev(pruned[1], torch.uint8, "items_bf16")]
+    args += [n_items, int(k), kp, kk]
+    if excl:
+        args += _excl_args(name, *excl)
+    args += [_dev(out[0], torch.int64, "out_idx"), _dev(out[1], torch.float32, "out_val")]
+    if excl:
+        args.append(_dev(out[2], torch.int32, "out_len"))
+    args += [_dev(flag, torch.int32, "overflow"), _dev(ws, torch.uint8, "ws"), ws.numel(), _stream()]
+    _check(entry, getattr(lib(), entry)(*args))
+    if check_overflow and (kk > 8 or not pruned) and int(flag.item()) != 0:
+        scores = als_score(user_factors, user_rows, item_factors_t, None, n_items, k)
+        return topk(scores, kk)
+    return out
+
+
 def als_score_topk(user_factors, user_rows, item_factors_t, n_items, k, top_k, check_overflow=True,
                    overflow_out=None):
     """Top-k of the JVM-exact ALS scores over items [0, n_items) for each
@@ -608,32 +667,8 @@ def als_score_topk(user_factors, user_rows, item_factors_t, n_items, k, top_k, c
     full score matrix + top-k when a user's survivor list overflowed.
     overflow_out (device int32 [1], optional) receives the library's overflow
     flag (with check_overflow=False the caller resolves it later)."""
-    kp = user_factors.shape[1]
-    B = user_rows.numel()
-    kk = min(int(top_k), int(n_items))
-    dev = user_factors.device
-    out_i = torch.empty((B, kk), dtype=torch.int64, device=dev)
-    out_v = torch.empty((B, kk), dtype=torch.float32, device=dev)
-    # zeroed by the library on the stream
-    flag = overflow_out if overflow_out is not None else torch.empty(1, dtype=torch.int32, device=dev)
-    need = int(lib().hrec_als_score_topk_workspace_bytes(B, n_items, kk))
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    _check("hrec_als_score_topk", lib().hrec_als_score_topk(
-        _dev(user_factors, torch.float32, "user_factors"), _dev(user_rows, torch.int64, "user_rows"), B,
-        _dev(item_factors_t, torch.float32, "item_factors_t"), item_factors_t.shape[1], n_items, k, kp, kk,
-        _dev(out_i, torch.int64, "out_idx"), _dev(out_v, torch.float32, "out_val"),
-        _dev(flag, torch.int32, "overflow"), _dev(ws, torch.uint8, "ws"), need, _stream()))
-    if check_overflow and int(flag.item()) != 0:
-        scores = als_score(user_factors, user_rows, item_factors_t, None, n_items, k)
-        return topk(scores, kk)
-    return out_i, out_v
-
-
-def _excl_args(name, excl_indptr, excl_cols):
-    """The exclusion CSR's two pointers (an empty column list: a stand-in entry, never read)."""
-    if excl_cols.numel() == 0:
-        excl_cols = torch.zeros(1, dtype=torch.int32, device=excl_indptr.device)
-    return _dev(excl_indptr, torch.int64, f"{name}: excl_indptr"), _dev(excl_cols, torch.int32, f"{name}: excl_cols")
+    return _als_topk(user_factors, user_rows, item_factors_t, n_items, k, top_k, check_overflow=check_overflow,
+                     overflow_out=overflow_out)
 
 
 def als_score_topk_excluding(user_factors, user_rows, item_factors_t, n_items, k, top_k, excl_indptr, excl_cols,
@@ -646,32 +681,8 @@ def als_score_topk_excluding(user_factors, user_rows, item_factors_t, n_items, k
     is the caller's to resolve: a set flag means als_score + mask_rows (NaN) +
     topk. workspace (uint8 device, optional) is reused when large enough; out
     (optional): the contiguous ([B, kk], [B, kk], [B]) tensors to write."""
-    kp = user_factors.shape[1]
-    B = user_rows.numel()
-    kk = min(int(top_k), int(n_items))
-    dev = user_factors.device
-    if excl_indptr.numel() != user_factors.shape[0] + 1:
-        raise HrecError("als_score_topk_excluding: excl_indptr must have one entry per factor row + 1")
-    if out is not None:
-        out_i, out_v, out_n = out
-        if tuple(out_i.shape) != (B, kk) or tuple(out_v.shape) != (B, kk) or out_n.numel() != B:
-            raise HrecError("als_score_topk_excluding: out must be two [B, kk] tensors and one [B]")
-    else:
-        out_i = torch.empty((B, kk), dtype=torch.int64, device=dev)
-        out_v = torch.empty((B, kk), dtype=torch.float32, device=dev)
-        out_n = torch.empty(B, dtype=torch.int32, device=dev)
-    flag = overflow_out if overflow_out is not None else torch.empty(1, dtype=torch.int32, device=dev)
-    need = int(lib().hrec_als_score_topk_excluding_workspace_bytes(B, n_items, kk))
-    ws = workspace if workspace is not None and workspace.numel() >= need else \
-        torch.empty(need, dtype=torch.uint8, device=dev)
-    _check("hrec_als_score_topk_excluding", lib().hrec_als_score_topk_excluding(
-        _dev(user_factors, torch.float32, "user_factors"), _dev(user_rows, torch.int64, "user_rows"), B,
-        _dev(item_factors_t, torch.float32, "item_factors_t"), item_factors_t.shape[1], n_items, int(k), kp, kk,
-        *_excl_args("als_score_topk_excluding", excl_indptr, excl_cols),
-        _dev(out_i, torch.int64, "out_idx"), _dev(out_v, torch.float32, "out_val"),
-        _dev(out_n, torch.int32, "out_len"), _dev(flag, torch.int32, "overflow"), _dev(ws, torch.uint8, "ws"),
-        ws.numel(), _stream()))
-    return out_i, out_v, out_n
+    return _als_topk(user_factors, user_rows, item_factors_t, n_items, k, top_k, excl=(excl_indptr, excl_cols),
+                     overflow_out=overflow_out, workspace=workspace, out=out)
 
 
 def mask_rows(vals, row_ids, excl_indptr, excl_cols, fill=float("nan")):
@@ -716,34 +727,8 @@ def als_score_topk_pruned(user_factors, user_rows, item_factors_t, item_factors,
     + top-k as als_score_topk does (check_overflow). out (optional): the
     contiguous (int64 [B, kk], f32 [B, kk]) tensors to write, e.g. the row
     slices of a larger result (with check_overflow=False)."""
-    kp = user_factors.shape[1]
-    B = user_rows.numel()
-    kk = min(int(top_k), int(n_items))
-    dev = user_factors.device
-    if item_factors.stride(1) != 1 or item_factors.shape[0] < n_items:
-        raise HrecError("als_score_topk_pruned: item_factors must be row-major with >= n_items rows")
-    if out is not None:
-        out_i, out_v = out
-        if tuple(out_i.shape) != (B, kk) or tuple(out_v.shape) != (B, kk) or check_overflow:
-            raise HrecError("als_score_topk_pruned: out must be two [B, kk] tensors, with check_overflow=False")
-    else:
-        out_i = torch.empty((B, kk), dtype=torch.int64, device=dev)
-        out_v = torch.empty((B, kk), dtype=torch.float32, device=dev)
-    flag = overflow_out if overflow_out is not None else torch.empty(1, dtype=torch.int32, device=dev)
-    need = int(lib().hrec_als_score_topk_pruned_workspace_bytes(B, n_items, kk, int(k)))
-    ws = workspace if workspace is not None and workspace.numel() >= need else \
-        torch.empty(need, dtype=torch.uint8, device=dev)
-    _check("hrec_als_score_topk_pruned", lib().hrec_als_score_topk_pruned(
-        _dev(user_factors, torch.float32, "user_factors"), _dev(user_rows, torch.int64, "user_rows"), B,
-        _dev(item_factors_t, torch.float32, "item_factors_t"), item_factors_t.shape[1],
-        _dev(item_factors, torch.float32, "item_factors"), item_factors.stride(0),
-        _dev(items_bf16, torch.uint8, "items_bf16"), n_items, int(k), kp, kk,
-        _dev(out_i, torch.int64, "out_idx"), _dev(out_v, torch.float32, "out_val"),
-        _dev(flag, torch.int32, "overflow"), _dev(ws, torch.uint8, "ws"), ws.numel(), _stream()))
-    if check_overflow and kk > 8 and int(flag.item()) != 0:
-        scores = als_score(user_factors, user_rows, item_factors_t, None, n_items, k)
-        return topk(scores, kk)
-    return out_i, out_v
+    return _als_topk(user_factors, user_rows, item_factors_t, n_items, k, top_k, pruned=(item_factors, items_bf16),
+                     check_overflow=check_overflow, overflow_out=overflow_out, workspace=workspace, out=out)
 
 
 def als_score_topk_pruned_excluding(user_factors, user_rows, item_factors_t, item_factors, items_bf16, n_items, k,
@@ -757,36 +742,8 @@ def als_score_topk_pruned_excluding(user_factors, user_rows, item_factors_t, ite
     means the answer is incomplete and als_score_topk_excluding answers the
     call. workspace (uint8 device, optional) is reused when large enough; out
     (optional): the contiguous ([B, kk], [B, kk], [B]) tensors to write."""
-    kp = user_factors.shape[1]
-    B = user_rows.numel()
-    kk = min(int(top_k), int(n_items))
-    dev = user_factors.device
-    if item_factors.stride(1) != 1 or item_factors.shape[0] < n_items:
-        raise HrecError("als_score_topk_pruned_excluding: item_factors must be row-major with >= n_items rows")
-    if excl_indptr.numel() != user_factors.shape[0] + 1:
-        raise HrecError("als_score_topk_pruned_excluding: excl_indptr must have one entry per factor row + 1")
-    if out is not None:
-        out_i, out_v, out_n = out
-        if tuple(out_i.shape) != (B, kk) or tuple(out_v.shape) != (B, kk) or out_n.numel() != B:
-            raise HrecError("als_score_topk_pruned_excluding: out must be two [B, kk] tensors and one [B]")
-    else:
-        out_i = torch.empty((B, kk), dtype=torch.int64, device=dev)
-        out_v = torch.empty((B, kk), dtype=torch.float32, device=dev)
-        out_n = torch.empty(B, dtype=torch.int32, device=dev)
-    flag = overflow_out if overflow_out is not None else torch.empty(1, dtype=torch.int32, device=dev)
-    need = int(lib().hrec_als_score_topk_pruned_excluding_workspace_bytes(B, n_items, kk, int(k)))
-    ws = workspace if workspace is not None and workspace.numel() >= need else \
-        torch.empty(need, dtype=torch.uint8, device=dev)
-    _check("hrec_als_score_topk_pruned_excluding", lib().hrec_als_score_topk_pruned_excluding(
-        _dev(user_factors, torch.float32, "user_factors"), _dev(user_rows, torch.int64, "user_rows"), B,
-        _dev(item_factors_t, torch.float32, "item_factors_t"), item_factors_t.shape[1],
-        _dev(item_factors, torch.float32, "item_factors"), item_factors.stride(0),
-        _dev(items_bf16, torch.uint8, "items_bf16"), n_items, int(k), kp, kk,
-        *_excl_args("als_score_topk_pruned_excluding", excl_indptr, excl_cols),
-        _dev(out_i, torch.int64, "out_idx"), _dev(out_v, torch.float32, "out_val"),
-        _dev(out_n, torch.int32, "out_len"), _dev(flag, torch.int32, "overflow"), _dev(ws, torch.uint8, "ws"),
-        ws.numel(), _stream()))
-    return out_i, out_v, out_n
+    return _als_topk(user_factors, user_rows, item_factors_t, n_items, k, top_k, pruned=(item_factors, items_bf16),
+                     excl=(excl_indptr, excl_cols), overflow_out=overflow_out, workspace=workspace, out=out)
 
 
 def als_topk_pruned_counts(ws, B, n_items, top_k, k):
@@ -820,6 +777,26 @@ def topk(vals, top_k):
                            _dev(out_i, torch.int64, "out_idx"), _dev(out_v, vals.dtype, "out_val"),
                            _dev(ws, torch.uint8, "ws"), ws_bytes, _stream()))
     return out_i, out_v
+
+
+def topk_materialised(score, lo, hi, n_cols, kk, max_bytes, out_i, out_v, lens=None, excl=None, idx_offset=0):
+    """The last resort of every ranked-list path: rows [lo, hi) of out_i /
+    out_v (and lens) from materialised scores. score(s, e) gives the f32
+    [e - s, n_cols] scores of rows s .. e; they go through hrec_topk_f32 in
+    sub-batches whose score matrix stays under max_bytes. excl (optional):
+    (row_ids, excl_indptr, excl_cols) — row r's excluded columns are NaN-ed
+    first (mask_rows with row_ids[r]) and lens[r] = min(kk, columns kept).
+    idx_offset is added to the indices."""
+    sub = max(1, max_bytes // (4 * n_cols))
+    for s in range(lo, hi, sub):
+        e = min(s + sub, hi)
+        scores = score(s, e)
+        if excl is not None:
+            lens[s:e] = mask_rows(scores, excl[0][s:e], excl[1], excl[2]).clamp_(max=kk)
+        idx, val = topk(scores, kk)
+        out_i[s:e] = idx + int(idx_offset) if idx_offset else idx
+        out_v[s:e] = val
+        del scores
 
 
 # ----------------------------------------------------------------- fusion
@@ -993,37 +970,59 @@ def dot_topk(U, V, top_k, idx_offset=0, max_rounds=2):
     survivor list overflows, the k-th best of the survivors (a valid, higher
     lower bound) seeds another round; after max_rounds the exact chunked path
     (scores + top-k per chunk + keyed merge) answers."""
+    return _dot_topk(U, V, top_k, idx_offset, max_rounds)[:2]
+
+
+def _dot_topk(U, V, top_k, idx_offset, max_rounds, excl=None):
+    """dot_topk's and, with excl = (excl_rows, excl_indptr, excl_cols),
+    dot_topk_excluding's loop over user chunks and refinement rounds:
+    (idx, val, lens or None)."""
+    name = "hrec_dot_topk" + ("_excluding" if excl else "")
     dk, bf = _dot_args(U, V)
     B, N = U.shape[0], V.shape[0]
     kk = min(int(top_k), int(N))
     dev = U.device
+    if excl and excl[0].numel() != B:
+        raise HrecError("dot_topk_excluding: excl_rows must have one entry per query")
     out_i = torch.empty((B, kk), dtype=torch.int64, device=dev)
     out_v = torch.empty((B, kk), dtype=torch.float32, device=dev)
+    out_n = torch.zeros(B, dtype=torch.int32, device=dev) if excl else None
     if B == 0 or kk == 0:
-        return out_i, out_v
+        return out_i, out_v, out_n
+    p_excl = _excl_args("dot_topk_excluding", excl[1], excl[2]) if excl else None
+    entry, query = getattr(lib(), name), getattr(lib(), name + "_workspace_bytes")
     for b0 in range(0, B, DOT_USER_CHUNK):
         b1 = min(B, b0 + DOT_USER_CHUNK)
         Ub = U[b0:b1]
         nb = b1 - b0
-        need = int(lib().hrec_dot_topk_workspace_bytes(nb, N, kk))
+        need = int(query(nb, N, kk))
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         flag = torch.zeros(1, dtype=torch.int32, device=dev)
         oi, ov = out_i[b0:b1], out_v[b0:b1]
+        p_in, p_out = (), (_dev(oi, torch.int64, "out_idx"), _dev(ov, torch.float32, "out_val"))
+        if excl:
+            rows, on = excl[0][b0:b1], out_n[b0:b1]
+            p_in = (_dev(rows, torch.int64, "excl_rows"), *p_excl)
+            p_out += (_dev(on, torch.int32, "out_len"),)
         thr = None
         for _ in range(max_rounds):
-            _check("hrec_dot_topk", lib().hrec_dot_topk(
+            _check(name, entry(
                 _vp(Ub.data_ptr()), nb, _vp(V.data_ptr()), N, dk, bf, kk,
                 None if thr is None else _dev(thr, torch.float32, "thr"), int(idx_offset),
-                _dev(oi, torch.int64, "out_idx"), _dev(ov, torch.float32, "out_val"),
-                _dev(flag, torch.int32, "overflow"), _dev(ws, torch.uint8, "ws"), need, _stream()))
+                *p_in, *p_out, _dev(flag, torch.int32, "overflow"), _dev(ws, torch.uint8, "ws"), need, _stream()))
             if int(flag.item()) == 0:
                 break
             thr = ov[:, kk - 1].contiguous()
         else:
-            ci, cv = _dot_topk_chunked(Ub, V, kk, idx_offset)
-            oi.copy_(ci)
-            ov.copy_(cv)
-    return out_i, out_v
+            if excl:
+                del ws
+                topk_materialised(lambda s, e: dot_scores(Ub[s:e], V), 0, nb, N, kk, DOT_FALLBACK_BYTES, oi, ov, on,
+                                  (rows, excl[1], excl[2]), idx_offset)
+            else:
+                ci, cv = _dot_topk_chunked(Ub, V, kk, idx_offset)
+                oi.copy_(ci)
+                ov.copy_(cv)
+    return out_i, out_v, out_n
 
 
 DOT_FALLBACK_BYTES = 1 << 30  # dot_topk_excluding's materialised fallback keeps its score matrix under this
@@ -1041,51 +1040,7 @@ def dot_topk_excluding(U, V, top_k, excl_rows, excl_indptr, excl_cols, idx_offse
     max_rounds the materialised chain answers it: hrec_dot_scores ->
     hrec_mask_rows_f32 (NaN) -> hrec_topk_f32, in user sub-batches whose
     score matrix stays under DOT_FALLBACK_BYTES."""
-    dk, bf = _dot_args(U, V)
-    B, N = U.shape[0], V.shape[0]
-    kk = min(int(top_k), int(N))
-    dev = U.device
-    if excl_rows.numel() != B:
-        raise HrecError("dot_topk_excluding: excl_rows must have one entry per query")
-    out_i = torch.empty((B, kk), dtype=torch.int64, device=dev)
-    out_v = torch.empty((B, kk), dtype=torch.float32, device=dev)
-    out_n = torch.zeros(B, dtype=torch.int32, device=dev)
-    if B == 0 or kk == 0:
-        return out_i, out_v, out_n
-    p_indptr, p_cols = _excl_args("dot_topk_excluding", excl_indptr, excl_cols)
-    for b0 in range(0, B, DOT_USER_CHUNK):
-        b1 = min(B, b0 + DOT_USER_CHUNK)
-        Ub, rows = U[b0:b1], excl_rows[b0:b1]
-        nb = b1 - b0
-        need = int(lib().hrec_dot_topk_excluding_workspace_bytes(nb, N, kk))
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        oi, ov, on = out_i[b0:b1], out_v[b0:b1], out_n[b0:b1]
-        thr = None
-        for _ in range(max_rounds):
-            _check("hrec_dot_topk_excluding", lib().hrec_dot_topk_excluding(
-                _vp(Ub.data_ptr()), nb, _vp(V.data_ptr()), N, dk, bf, kk,
-                None if thr is None else _dev(thr, torch.float32, "thr"), int(idx_offset),
-                _dev(rows, torch.int64, "excl_rows"), p_indptr, p_cols,
-                _dev(oi, torch.int64, "out_idx"), _dev(ov, torch.float32, "out_val"),
-                _dev(on, torch.int32, "out_len"), _dev(flag, torch.int32, "overflow"), _dev(ws, torch.uint8, "ws"),
-                need, _stream()))
-            if int(flag.item()) == 0:
-                break
-            thr = ov[:, kk - 1].contiguous()
-        else:
-            del ws
-            sub = max(1, DOT_FALLBACK_BYTES // (4 * N))
-            for s in range(0, nb, sub):
-                e = min(s + sub, nb)
-                scores = dot_scores(Ub[s:e], V)
-                kept = mask_rows(scores, rows[s:e], excl_indptr, excl_cols)
-                ci, cv = topk(scores, kk)
-                oi[s:e] = ci + int(idx_offset)
-                ov[s:e] = cv
-                on[s:e] = kept.clamp_(max=kk)
-                del scores
-    return out_i, out_v, out_n
+    return _dot_topk(U, V, top_k, idx_offset, max_rounds, (excl_rows, excl_indptr, excl_cols))
 
 
 def dot_filter(U, V, thr, thr_per=0, cap=8192):

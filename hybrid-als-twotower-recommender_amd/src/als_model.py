@@ -58,7 +58,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _hrec
+from . import _hrec, ranked_lists
 from .als_engine import DeviceALS, padded_k, process_group
 from .als_ingest import check_same_frame, frame_fingerprint, sharded_ingest
 from .data_preprocessing import get_item_features
@@ -90,7 +90,7 @@ class DeviceALSFactors:
         self.V = V                               # [n_items, kp] f32 device
         self.k = int(k)
         self.Vt = _hrec.transpose(V) if V.shape[0] else V.t().contiguous()
-        self._ids_dev = {}  # "user" / "item" -> the sorted ids on the device (_lookup_device)
+        self._ids_dev = {}  # "user" / "item" -> the sorted ids on the device (_ids_device)
         self._rec_ops = {}  # "user" / "item" -> recommend()'s operands (_recommend_operands)
 
     @staticmethod
@@ -106,12 +106,8 @@ class DeviceALSFactors:
     def _lookup_device(self, keys, side="item"):
         """_lookup for long id lists: the same binary search on the device
         over a cached copy of the sorted item (or user) ids."""
-        dev = self.U.device
-        if side not in self._ids_dev:
-            ids_h = self.item_ids if side == "item" else self.user_ids
-            self._ids_dev[side] = torch.as_tensor(np.asarray(ids_h, np.int64), device=dev)
-        ids = self._ids_dev[side]
-        k = torch.as_tensor(keys, device=dev)
+        ids = self._ids_device(side)
+        k = torch.as_tensor(keys, device=ids.device)
         if ids.numel() == 0:
             return torch.full_like(k, -1)
         pos = torch.searchsorted(ids, k).clamp_(max=ids.numel() - 1)
@@ -187,22 +183,12 @@ class DeviceALSFactors:
 
     EXCLUSION_HOST_PAIRS = 1 << 16  # exclusion lists up to this many pairs are built on the host
 
-    @classmethod
-    def _exclusion_host(cls, side, known_users, known_items, user_ids, item_ids):
-        """exclusion() on the host: numpy (indptr int64, cols int32) from the
-        model's sorted ids and the pairs."""
-        u = cls._lookup(known_users, np.asarray(user_ids, np.int64).reshape(-1))
-        i = cls._lookup(known_items, np.asarray(item_ids, np.int64).reshape(-1))
-        if u.size != i.size:
-            raise ValueError("user_ids and item_ids must have the same length")
-        ok = (u >= 0) & (i >= 0)
-        r, c = (u[ok], i[ok]) if side == "user" else (i[ok], u[ok])
-        n_u, n_i = len(known_users), len(known_items)
-        n_rows, n_cols = (n_u, n_i) if side == "user" else (n_i, n_u)
-        key = np.unique(r * max(n_cols, 1) + c)  # ascending: by row, then by column
-        indptr = np.zeros(n_rows + 1, np.int64)
-        np.cumsum(np.bincount(key // max(n_cols, 1), minlength=n_rows), out=indptr[1:])
-        return indptr, (key % max(n_cols, 1)).astype(np.int32)
+    def _ids_device(self, side):
+        """The sorted user (or item) ids on the device, cached."""
+        if side not in self._ids_dev:
+            ids_h = self.item_ids if side == "item" else self.user_ids
+            self._ids_dev[side] = torch.as_tensor(np.asarray(ids_h, np.int64), device=self.U.device)
+        return self._ids_dev[side]
 
     def exclusion(self, side, user_ids, item_ids):
         """The exclusion CSR recommend(side, ..., exclude=) takes, from the
@@ -215,89 +201,13 @@ class DeviceALSFactors:
         above; the ids may be numpy arrays or device tensors."""
         if side not in ("user", "item"):
             raise ValueError(f"side must be 'user' or 'item' (got {side!r})")
-        dev = self.U.device
-        on_dev = isinstance(user_ids, torch.Tensor)
-        n_pairs = int(user_ids.numel() if on_dev else np.asarray(user_ids).size)
-        n_u, n_i = len(self.user_ids), len(self.item_ids)
-        n_rows, n_cols = (n_u, n_i) if side == "user" else (n_i, n_u)
-        if not on_dev and n_pairs <= self.EXCLUSION_HOST_PAIRS:
-            indptr, cols = self._exclusion_host(side, self.user_ids, self.item_ids, user_ids, item_ids)
-            return torch.as_tensor(indptr, device=dev), torch.as_tensor(cols, device=dev)
-        u = self._lookup_device(user_ids if on_dev else np.asarray(user_ids, np.int64).reshape(-1), "user")
-        i = self._lookup_device(item_ids if isinstance(item_ids, torch.Tensor)
-                                else np.asarray(item_ids, np.int64).reshape(-1), "item")
-        if u.numel() != i.numel():
-            raise ValueError("user_ids and item_ids must have the same length")
-        r, c = (u, i) if side == "user" else (i, u)
-        key = r * max(n_cols, 1) + c
-        key = torch.unique(key[(r >= 0) & (c >= 0)])  # sorted
-        del u, i, r, c
-        indptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
-        if key.numel():
-            torch.cumsum(torch.bincount(torch.div(key, max(n_cols, 1), rounding_mode="floor"), minlength=n_rows), 0,
-                         out=indptr[1:])
-        return indptr, torch.remainder(key, max(n_cols, 1)).to(torch.int32)
-
-    def _recommend_excluding(self, side, rows, num, exclude):
-        """recommend() under an exclusion: (ids, scores, lens). Three levels,
-        each answering only the batches the one before flagged: the bf16-pruned
-        entry (hrec_als_score_topk_pruned_excluding), the exact chain over
-        every pair (hrec_als_score_topk_excluding), the materialised scores
-        (hrec_als_score + hrec_mask_rows_f32 + hrec_topk) in sub-batches. One
-        flag per batch and level; one host read after the last batch of the
-        first level, a second only if that one found a flag."""
-        num = int(num)
-        if not 1 <= num <= self.RECOMMEND_MAX:
-            raise ValueError(f"num must be in [1, {self.RECOMMEND_MAX}] (got {num})")
-        Q, F, Ft, bf, ids = self._recommend_operands(side)
-        dev = Q.device
-        indptr, cols = exclude
-        if indptr.numel() != Q.shape[0] + 1 or indptr.dtype != torch.int64 or cols.dtype != torch.int32:
-            raise ValueError(f"recommend: exclude must be exclusion('{side}', ...)'s (indptr int64 "
-                             f"[{Q.shape[0] + 1}], cols int32)")
-        rows = torch.as_tensor(rows, dtype=torch.int64, device=dev).reshape(-1).contiguous()
-        n, n_other = rows.numel(), int(F.shape[0])
-        kk = min(num, n_other)
-        out_i = torch.zeros((n, kk), dtype=torch.int64, device=dev)
-        out_v = torch.empty((n, kk), dtype=torch.float32, device=dev)
-        lens = torch.zeros(n, dtype=torch.int32, device=dev)
-        if n == 0 or kk == 0:
-            return out_i, out_v, lens
-        if bool(((rows < 0) | (rows >= Q.shape[0])).any().item()):
-            raise ValueError(f"recommend: a {side} row is outside [0, {Q.shape[0]})")
-        B = int(self.RECOMMEND_BATCH)
-        starts = range(0, n, B)
-        flags = torch.zeros(len(starts), dtype=torch.int32, device=dev)
-        # the pruned query covers the exact entry's need: one workspace for both levels
-        need = int(_hrec.lib().hrec_als_score_topk_pruned_excluding_workspace_bytes(min(B, n), n_other, kk, self.k))
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        for b, s in enumerate(starts):
-            _hrec.als_score_topk_pruned_excluding(Q, rows[s: s + B], Ft, F, bf, n_other, self.k, kk, indptr, cols,
-                                                  overflow_out=flags[b: b + 1], workspace=ws,
-                                                  out=(out_i[s: s + B], out_v[s: s + B], lens[s: s + B]))
-        # one host read for all batches; a flagged batch is incomplete at every kk
-        redo = torch.nonzero(flags).reshape(-1).tolist()
-        flags.zero_()
-        for b in redo:  # the exact chain over every pair of that batch
-            s = starts[b]
-            _hrec.als_score_topk_excluding(Q, rows[s: s + B], Ft, n_other, self.k, kk, indptr, cols,
-                                           overflow_out=flags[b: b + 1], workspace=ws,
-                                           out=(out_i[s: s + B], out_v[s: s + B], lens[s: s + B]))
-        del ws
-        sub = max(1, self.RECOMMEND_FALLBACK_BYTES // (4 * n_other))
-        for b in (torch.nonzero(flags).reshape(-1).tolist() if redo else ()):
-            lo, hi = starts[b], min(starts[b] + B, n)
-            for s in range(lo, hi, sub):
-                e = min(s + sub, hi)
-                scores = _hrec.als_score(Q, rows[s:e], Ft, None, n_other, self.k)
-                kept = _hrec.mask_rows(scores, rows[s:e], indptr, cols)
-                out_i[s:e], out_v[s:e] = _hrec.topk(scores, kk)
-                lens[s:e] = kept.clamp_(max=kk)
-                del scores
-        # past a list's length: id 0, score NaN (what the library left there is unspecified)
-        live = torch.arange(kk, device=dev).unsqueeze(0) < lens.unsqueeze(1)
-        out_ids = torch.where(live, ids[out_i.clamp_(0, n_other - 1)], torch.zeros_like(out_i))
-        return out_ids, torch.where(live, out_v, torch.full_like(out_v, float("nan"))), lens
+        sides = ("user", "item") if side == "user" else ("item", "user")  # (rows, columns)
+        known = {"user": self.user_ids, "item": self.item_ids}
+        pairs = {"user": user_ids, "item": item_ids}
+        return ranked_lists.exclusion_csr(
+            *(known[s] for s in sides), *(pairs[s] for s in sides), self.U.device, self.EXCLUSION_HOST_PAIRS,
+            cols_sorted=True, device_keys=lambda: tuple(self._ids_device(s) for s in sides),
+            what="user_ids and item_ids")
 
     def recommend(self, side, rows, num, exclude=None):
         """Top-`num` of the other side for each of `rows` (int64 row indices
@@ -316,48 +226,68 @@ class DeviceALSFactors:
         stable ranking with the row's excluded entries deleted, cut to num;
         returns (ids, scores, lens int32 [n]) with lens = min(kk, size of the
         other side - the row's excluded entries), and id 0 / score NaN past a
-        list's length. Those batches go through
-        hrec_als_score_topk_pruned_excluding (the bf16 bound over the sample's
-        items that stay, the exact chain for the pairs it keeps); a flagged
-        batch, at every kk, through hrec_als_score_topk_excluding (the exact
-        chain over every pair), and one flagged there too through
-        hrec_als_score + hrec_mask_rows_f32 + hrec_topk."""
-        if exclude is not None:
-            return self._recommend_excluding(side, rows, num, exclude)
-        num = int(num)
-        if not 1 <= num <= self.RECOMMEND_MAX:
-            raise ValueError(f"num must be in [1, {self.RECOMMEND_MAX}] (got {num})")
+        list's length. Three levels, each answering only the batches the one
+        before flagged: hrec_als_score_topk_pruned_excluding (the bf16 bound
+        over the sample's items that stay, the exact chain for the pairs it
+        keeps); at every kk hrec_als_score_topk_excluding (the exact chain
+        over every pair); hrec_als_score + hrec_mask_rows_f32 + hrec_topk.
+        One flag per batch and level; one host read after the last batch of
+        the first level, a second only if that one found a flag."""
+        num = ranked_lists.check_num(num, self.RECOMMEND_MAX)
         Q, F, Ft, bf, ids = self._recommend_operands(side)
         dev = Q.device
+        excl = exclude is not None
+        if excl:
+            indptr, cols = exclude
+            if indptr.numel() != Q.shape[0] + 1 or indptr.dtype != torch.int64 or cols.dtype != torch.int32:
+                raise ValueError(f"recommend: exclude must be exclusion('{side}', ...)'s (indptr int64 "
+                                 f"[{Q.shape[0] + 1}], cols int32)")
         rows = torch.as_tensor(rows, dtype=torch.int64, device=dev).reshape(-1).contiguous()
         n, n_other = rows.numel(), int(F.shape[0])
         kk = min(num, n_other)
-        out_i = torch.empty((n, kk), dtype=torch.int64, device=dev)
+        out_i = (torch.zeros if excl else torch.empty)((n, kk), dtype=torch.int64, device=dev)
         out_v = torch.empty((n, kk), dtype=torch.float32, device=dev)
+        lens = torch.zeros(n, dtype=torch.int32, device=dev) if excl else None
+        outs = (out_i, out_v, lens) if excl else (out_i, out_v)
         if n == 0 or kk == 0:
-            return out_i, out_v
+            return outs
         if bool(((rows < 0) | (rows >= Q.shape[0])).any().item()):
             raise ValueError(f"recommend: a {side} row is outside [0, {Q.shape[0]})")
         B = int(self.RECOMMEND_BATCH)
         starts = range(0, n, B)
         flags = torch.zeros(len(starts), dtype=torch.int32, device=dev)
-        need = int(_hrec.lib().hrec_als_score_topk_pruned_workspace_bytes(min(B, n), n_other, kk, self.k))
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        for b, s in enumerate(starts):
-            _hrec.als_score_topk_pruned(Q, rows[s: s + B], Ft, F, bf, n_other, self.k, kk, check_overflow=False,
-                                        overflow_out=flags[b: b + 1], workspace=ws,
-                                        out=(out_i[s: s + B], out_v[s: s + B]))
+        # with an exclusion the pruned query covers the exact entry's need: one workspace for both levels
+        lib = _hrec.lib()
+        query = (lib.hrec_als_score_topk_pruned_excluding_workspace_bytes if excl
+                 else lib.hrec_als_score_topk_pruned_workspace_bytes)
+        ws = torch.empty(int(query(min(B, n), n_other, kk, self.k)), dtype=torch.uint8, device=dev)
+
+        def batch(entry, b, *operands, **kw):
+            sl = slice(starts[b], starts[b] + B)
+            out = (out_i[sl], out_v[sl], lens[sl]) if excl else (out_i[sl], out_v[sl])
+            entry(Q, rows[sl], Ft, *operands, overflow_out=flags[b: b + 1], workspace=ws, out=out, **kw)
+
+        for b in range(len(starts)):
+            if excl:
+                batch(_hrec.als_score_topk_pruned_excluding, b, F, bf, n_other, self.k, kk, indptr, cols)
+            else:
+                batch(_hrec.als_score_topk_pruned, b, F, bf, n_other, self.k, kk, check_overflow=False)
+        # one host read for all batches; a flagged batch is incomplete (without an exclusion only for kk > 8:
+        # below, the library resolved it on the device)
+        redo = torch.nonzero(flags).reshape(-1).tolist() if excl or kk > 8 else ()
+        if excl:
+            flags.zero_()
+            for b in redo:  # the exact chain over every pair of that batch
+                batch(_hrec.als_score_topk_excluding, b, n_other, self.k, kk, indptr, cols)
+            redo = torch.nonzero(flags).reshape(-1).tolist() if redo else ()
         del ws
-        if kk > 8:  # one host read for all batches; a flagged batch is incomplete
-            sub = max(1, self.RECOMMEND_FALLBACK_BYTES // (4 * n_other))
-            for b in torch.nonzero(flags).reshape(-1).tolist():
-                lo, hi = starts[b], min(starts[b] + B, n)
-                for s in range(lo, hi, sub):
-                    e = min(s + sub, hi)
-                    scores = _hrec.als_score(Q, rows[s:e], Ft, None, n_other, self.k)
-                    out_i[s:e], out_v[s:e] = _hrec.topk(scores, kk)
-                    del scores
-        return ids[out_i], out_v
+        for b in redo:  # the materialised scores
+            _hrec.topk_materialised(lambda s, e: _hrec.als_score(Q, rows[s:e], Ft, None, n_other, self.k),
+                                    starts[b], min(starts[b] + B, n), n_other, kk, self.RECOMMEND_FALLBACK_BYTES,
+                                    out_i, out_v, lens, (rows, indptr, cols) if excl else None)
+        if not excl:
+            return ids[out_i], out_v
+        return (*ranked_lists.pad_lists(ids, out_i, out_v, lens, n_other), lens)
 
     # Spark 3.5 ALSModel directory layout (MLWriter): metadata/part-00000 is
     # one JSON line with the model params and "rank"; userFactors/ and
@@ -920,8 +850,7 @@ class ALSModel:
     def evaluate(self, data, metric_name="rmse", label_col="average_review_rating"):
         """Spark's RegressionEvaluator(metricName=metric_name).evaluate of
         transform(data): one of rmse, mse, mae, r2, var (a float)."""
-        if metric_name not in self.METRIC_NAMES:
-            raise ValueError(f"metric_name must be one of {', '.join(self.METRIC_NAMES)} (got {metric_name!r})")
+        ranked_lists.check_metric_name(metric_name, self.METRIC_NAMES)
         return float(self.regression_metrics(data, label_col)[metric_name])
 
     # ------------------------------------------------ recommendForAll / Subset
@@ -957,11 +886,7 @@ class ALSModel:
             (rec_ids, scores), lens = model.recommend(side, rows, num), None
         else:
             rec_ids, scores, lens = model.recommend(side, rows, num, exclude=self._exclusion(side, exclude))
-        rec_ids, scores = rec_ids.cpu().numpy().tolist(), scores.cpu().numpy().tolist()
-        recs = [list(zip(i, s)) for i, s in zip(rec_ids, scores)]
-        if lens is not None:  # each list cut to its length
-            recs = [rec[:m] for rec, m in zip(recs, lens.cpu().numpy().tolist())]
-        return pd.DataFrame({col: ids[rows], "recommendations": recs})
+        return ranked_lists.lists_frame(col, ids[rows], rec_ids, scores, lens)
 
     def recommend_for_all_users(self, num_items, exclude=None):
         """Spark's recommendForAllUsers: a DataFrame with one row per user
@@ -1002,28 +927,6 @@ class ALSModel:
                             "ndcgAtK")
     RANKING_HOST_ROWS = 1 << 16  # frames up to this many rows: the label CSR is built on the host
 
-    @staticmethod
-    def _label_csr_host(users, items, dev):
-        """(distinct users, indptr, labels) of the (user, item) rows, int64
-        device tensors: users ascending, a user's items ascending (duplicates
-        stay; the kernel counts them once)."""
-        order = np.lexsort((items, users))
-        u, labels = users[order], items[order]
-        first = np.flatnonzero(np.r_[True, u[1:] != u[:-1]]) if len(u) else np.zeros(0, np.int64)
-        indptr = np.r_[first, len(u)].astype(np.int64)
-        return tuple(torch.as_tensor(np.ascontiguousarray(a, np.int64), device=dev) for a in (u[first], indptr, labels))
-
-    @staticmethod
-    def _label_csr_device(users, items, dev):
-        """_label_csr_host with the sorts on the device (two stable sorts)."""
-        u, it = torch.as_tensor(users, device=dev), torch.as_tensor(items, device=dev)
-        it, order = torch.sort(it, stable=True)
-        u, order = torch.sort(u[order], stable=True)
-        uniq, counts = torch.unique_consecutive(u, return_counts=True)
-        indptr = torch.zeros(uniq.numel() + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(counts, 0, out=indptr[1:])
-        return uniq, indptr, it[order].contiguous()
-
     def ranking_metrics(self, data, k=10, label_col=None, min_rating=None, exclude=None):
         """Spark's RankingMetrics (binary relevance) of the model's top-k item
         lists against `data` (columns userId, itemId): {"meanAveragePrecision",
@@ -1043,9 +946,7 @@ class ALSModel:
         ranked without its pairs (recommend_for_all_users' exclude), each
         evaluated at its own length. An item of `data` that is also excluded
         can never be hit and still counts in its user's set size."""
-        k = int(k)
-        if not 1 <= k <= _hrec.RANK_MAX:
-            raise ValueError(f"k must be in [1, {_hrec.RANK_MAX}] (got {k})")
+        k = ranked_lists.check_num(k, _hrec.RANK_MAX, "k")
         users, items = self._pair_ids(data)
         if min_rating is not None:
             keep = np.asarray(data[label_col or "average_review_rating"], np.float64) >= float(min_rating)
@@ -1059,8 +960,7 @@ class ALSModel:
                 known = model._lookup(model.user_ids, users) >= 0
             dropped = int(np.unique(users[~known]).size)
             users, items = users[known], items[known]
-        build = self._label_csr_host if users.size <= self.RANKING_HOST_ROWS else self._label_csr_device
-        uniq, indptr, labels = build(users, items, dev)
+        uniq, indptr, labels = ranked_lists.label_csr(users, items, dev, self.RANKING_HOST_ROWS)
         n = int(uniq.numel())
         res = {name: float("nan") for name in self.RANKING_METRIC_NAMES}
         res.update(count=n, dropped=dropped)
@@ -1087,17 +987,7 @@ class ALSModel:
             pred[known, : top.shape[1]] = top
             pred_len = torch.zeros(n, dtype=torch.int32, device=dev)
             pred_len[known] = int(top.shape[1]) if top_len is None else top_len
-        sums, unsorted, _ = _hrec.ranking_metrics(pred, indptr, labels, k, pred_len=pred_len,
-                                                  pred_len_max=int(pred.shape[1]) if pred.numel() else 0)
-        s = torch.cat([sums, unsorted.to(torch.float64)]).tolist()  # one host read
-        if s[-1] != 0.0:
-            raise RuntimeError("ranking_metrics: a label row is not sorted ascending")
-        s = dict(zip(_hrec.RANK_SUMS, s))
-        if int(s["n_rows"]) != n:
-            raise RuntimeError(f"ranking_metrics: {int(s['n_rows'])} rows evaluated, {n} expected")
-        for name, slot in zip(self.RANKING_METRIC_NAMES, ("sum_ap", "sum_ap_k", "sum_precision", "sum_recall",
-                                                          "sum_ndcg")):
-            res[name] = s[slot] / n
+        res.update(ranked_lists.ranking_means(pred, pred_len, indptr, labels, k, n, self.RANKING_METRIC_NAMES))
         return res
 
     def evaluate_ranking(self, data, metric_name="meanAveragePrecision", k=10, label_col=None, min_rating=None,
@@ -1105,9 +995,7 @@ class ALSModel:
         """Spark's RankingEvaluator(metricName=metric_name, k=k).evaluate of
         the model's lists for the users of `data` (a float); exclude as in
         ranking_metrics."""
-        if metric_name not in self.RANKING_METRIC_NAMES:
-            raise ValueError(f"metric_name must be one of {', '.join(self.RANKING_METRIC_NAMES)} "
-                             f"(got {metric_name!r})")
+        ranked_lists.check_metric_name(metric_name, self.RANKING_METRIC_NAMES)
         return float(self.ranking_metrics(data, k, label_col, min_rating, exclude)[metric_name])
 
     # ----------------------------------------------------------- persistence

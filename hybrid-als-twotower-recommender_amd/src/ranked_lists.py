@@ -1,0 +1,158 @@
+"""What the ALS and the two-tower model share around their ranked lists:
+the exclusion CSR of seen pairs, the label CSR and the tail of the ranking
+metrics, list finishing (padding, the DataFrame of tuples) and the argument
+checks. Plain functions over numpy arrays and device tensors; the models keep
+their own operands, thresholds (passed in, read at call time) and scoring
+routes. The materialised top-k of the last resort is _hrec.topk_materialised.
+"""
+import numpy as np
+import torch
+
+from . import _hrec
+
+
+def check_num(num, limit, name="num"):
+    """int(num), in [1, limit]."""
+    num = int(num)
+    if not 1 <= num <= limit:
+        raise ValueError(f"{name} must be in [1, {limit}] (got {num})")
+    return num
+
+
+def check_metric_name(metric_name, names):
+    if metric_name not in names:
+        raise ValueError(f"metric_name must be one of {', '.join(names)} (got {metric_name!r})")
+
+
+# ------------------------------------------------------------ exclusion CSR
+# (row_keys, col_keys, excl_rows, excl_cols) -> (indptr int64 [len(row_keys) +
+# 1], cols int32): row q holds the positions in col_keys of the ids paired
+# with row_keys[q], ascending and distinct. row_keys: int64, ascending,
+# distinct. col_keys: int64, distinct, in any order (cols_sorted: ascending,
+# which saves the sort). Pairs with a key outside either list are dropped.
+def exclusion_csr_host(row_keys, col_keys, excl_rows, excl_cols, cols_sorted=False, what="excl_rows and excl_cols"):
+    """Pure numpy."""
+    row_keys, col_keys, er, ec = (np.asarray(a, np.int64).reshape(-1)
+                                  for a in (row_keys, col_keys, excl_rows, excl_cols))
+    if er.size != ec.size:
+        raise ValueError(f"{what} must have the same length")
+    n_rows, n_cols = row_keys.size, col_keys.size
+    indptr = np.zeros(n_rows + 1, np.int64)
+    if n_rows == 0 or n_cols == 0 or er.size == 0:
+        return indptr, np.zeros(0, np.int32)
+    order = None if cols_sorted else np.argsort(col_keys, kind="stable")  # sorted position -> position in col_keys
+    sorted_cols = col_keys if cols_sorted else col_keys[order]
+    pc = np.minimum(np.searchsorted(sorted_cols, ec), n_cols - 1)
+    pr = np.minimum(np.searchsorted(row_keys, er), n_rows - 1)
+    ok = (sorted_cols[pc] == ec) & (row_keys[pr] == er)
+    key = np.unique(pr[ok] * n_cols + (pc[ok] if cols_sorted else order[pc[ok]]))  # ascending: by row, then by column
+    np.cumsum(np.bincount(key // n_cols, minlength=n_rows), out=indptr[1:])
+    return indptr, (key % n_cols).astype(np.int32)
+
+
+def exclusion_csr_device(row_keys, col_keys, excl_rows, excl_cols, dev, cols_sorted=False,
+                         what="excl_rows and excl_cols"):
+    """exclusion_csr_host on the device (one sort of 64-bit keys, and one of
+    col_keys unless cols_sorted); any of the four may already be a device
+    tensor."""
+    row_keys, col_keys, er, ec = (torch.as_tensor(a, dtype=torch.int64, device=dev).reshape(-1)
+                                  for a in (row_keys, col_keys, excl_rows, excl_cols))
+    if er.numel() != ec.numel():
+        raise ValueError(f"{what} must have the same length")
+    n_rows, n_cols = row_keys.numel(), col_keys.numel()
+    indptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
+    if n_rows == 0 or n_cols == 0 or er.numel() == 0:
+        return indptr, torch.zeros(0, dtype=torch.int32, device=dev)
+    sorted_cols, order = (col_keys, None) if cols_sorted else torch.sort(col_keys, stable=True)
+    pc = torch.searchsorted(sorted_cols, ec).clamp_(max=n_cols - 1)
+    pr = torch.searchsorted(row_keys, er).clamp_(max=n_rows - 1)
+    ok = (sorted_cols[pc] == ec) & (row_keys[pr] == er)
+    key = torch.unique(pr[ok] * n_cols + (pc[ok] if cols_sorted else order[pc[ok]]))  # sorted
+    del pc, pr, ok
+    if key.numel():
+        torch.cumsum(torch.bincount(torch.div(key, n_cols, rounding_mode="floor"), minlength=n_rows), 0,
+                     out=indptr[1:])
+    return indptr, torch.remainder(key, n_cols).to(torch.int32)
+
+
+def exclusion_csr(row_keys, col_keys, excl_rows, excl_cols, dev, host_pairs, cols_sorted=False, device_keys=None,
+                  what="excl_rows and excl_cols"):
+    """The device (indptr, cols): built on the host up to host_pairs pairs,
+    on the device above or when the pairs are device tensors already.
+    device_keys (optional): the (row_keys, col_keys) copies a caller keeps on
+    the device."""
+    on_dev = isinstance(excl_rows, torch.Tensor) or isinstance(excl_cols, torch.Tensor)
+    if not on_dev and np.asarray(excl_rows).size <= host_pairs:
+        indptr, cols = exclusion_csr_host(row_keys, col_keys, excl_rows, excl_cols, cols_sorted, what)
+        return torch.as_tensor(indptr, device=dev), torch.as_tensor(cols, device=dev)
+    if device_keys is not None:
+        row_keys, col_keys = device_keys()
+    return exclusion_csr_device(row_keys, col_keys, excl_rows, excl_cols, dev, cols_sorted, what)
+
+
+# ---------------------------------------------------------------- label CSR
+def label_csr_host(users, items, dev):
+    """(distinct users, indptr, labels) of the (user, item) rows, int64
+    device tensors: users ascending, a user's items ascending (duplicates
+    stay; the kernel counts them once)."""
+    order = np.lexsort((items, users))
+    u, labels = users[order], items[order]
+    first = np.flatnonzero(np.r_[True, u[1:] != u[:-1]]) if len(u) else np.zeros(0, np.int64)
+    indptr = np.r_[first, len(u)].astype(np.int64)
+    return tuple(torch.as_tensor(np.ascontiguousarray(a, np.int64), device=dev) for a in (u[first], indptr, labels))
+
+
+def label_csr_device(users, items, dev):
+    """label_csr_host with the sorts on the device (two stable sorts)."""
+    u, it = torch.as_tensor(users, device=dev), torch.as_tensor(items, device=dev)
+    it, order = torch.sort(it, stable=True)
+    u, order = torch.sort(u[order], stable=True)
+    uniq, counts = torch.unique_consecutive(u, return_counts=True)
+    indptr = torch.zeros(uniq.numel() + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=indptr[1:])
+    return uniq, indptr, it[order].contiguous()
+
+
+def label_csr(users, items, dev, host_rows):
+    """On the host for frames up to host_rows rows, on the device above."""
+    return (label_csr_host if users.size <= host_rows else label_csr_device)(users, items, dev)
+
+
+# -------------------------------------------------------------- metric tail
+def ranking_means(pred, pred_len, indptr, labels, k, n, names):
+    """{name: mean over the n label rows} of Spark's five ranking metrics
+    (names in the order MAP, MAP@k, precision@k, recall@k, NDCG@k) for the
+    device lists pred (lens pred_len, None: all full) against the label CSR:
+    hrec_ranking_metrics and one host read."""
+    sums, unsorted, _ = _hrec.ranking_metrics(pred, indptr, labels, k, pred_len=pred_len,
+                                              pred_len_max=int(pred.shape[1]) if pred.numel() else 0)
+    s = torch.cat([sums, unsorted.to(torch.float64)]).tolist()  # one host read
+    if s[-1] != 0.0:
+        raise RuntimeError("ranking_metrics: a label row is not sorted ascending")
+    s = dict(zip(_hrec.RANK_SUMS, s))
+    if int(s["n_rows"]) != n:
+        raise RuntimeError(f"ranking_metrics: {int(s['n_rows'])} rows evaluated, {n} expected")
+    return {name: s[slot] / n
+            for name, slot in zip(names, ("sum_ap", "sum_ap_k", "sum_precision", "sum_recall", "sum_ndcg"))}
+
+
+# ----------------------------------------------------------- list finishing
+def pad_lists(id_table, idx, val, lens, n_cols):
+    """(raw ids, scores) of the lists idx / val with id 0 and score NaN past
+    each list's length (what the library left there is unspecified)."""
+    kk = idx.shape[1]
+    live = torch.arange(kk, device=idx.device).unsqueeze(0) < lens.unsqueeze(1)
+    ids = torch.where(live, id_table[idx.clamp_(0, n_cols - 1)], torch.zeros_like(idx))
+    return ids, torch.where(live, val, torch.full_like(val, float("nan")))
+
+
+def lists_frame(key_col, keys, ids, val, lens=None):
+    """The DataFrame (key_col, recommendations): per key its list of (id,
+    rating) tuples from the device lists ids / val, cut to lens when given."""
+    import pandas as pd
+
+    ids, val = ids.cpu().numpy().tolist(), val.cpu().numpy().tolist()
+    recs = [list(zip(i, s)) for i, s in zip(ids, val)]
+    if lens is not None:  # each list cut to its length
+        recs = [rec[:m] for rec, m in zip(recs, lens.cpu().numpy().tolist())]
+    return pd.DataFrame({key_col: keys, "recommendations": recs})

@@ -33,8 +33,8 @@ import torch
 from sklearn.model_selection import train_test_split  # noqa: F401  (reference import surface)
 from sklearn.preprocessing import MinMaxScaler
 
-from . import _hrec
-from .als_model import ALSModel, _int_ids
+from . import _hrec, ranked_lists
+from .als_model import _int_ids
 from .tt_engine import TABLES, DeviceTwoTower
 
 
@@ -346,8 +346,9 @@ class TwoTowerModel:
     RECOMMEND_MAX = 1024                 # largest list length (the library's top_k limit)
     RECOMMEND_FALLBACK_BYTES = 1 << 30   # a materialised score matrix stays under this (per sub-batch)
     EXCLUSION_HOST_PAIRS = 1 << 16       # exclusion lists up to this many pairs are built on the host
-    RANKING_HOST_ROWS = ALSModel.RANKING_HOST_ROWS
-    RANKING_METRIC_NAMES = ALSModel.RANKING_METRIC_NAMES
+    RANKING_HOST_ROWS = 1 << 16          # frames up to this many rows: the label CSR is built on the host
+    RANKING_METRIC_NAMES = ("meanAveragePrecision", "meanAveragePrecisionAtK", "precisionAtK", "recallAtK",
+                            "ndcgAtK")
 
     def candidates(self, item_features):
         """The candidate frame on the device, for the methods below: its
@@ -393,65 +394,15 @@ class TwoTowerModel:
             return None
         return (np.asarray(sc.scale_, np.float64).tobytes(), np.asarray(sc.min_, np.float64).tobytes())
 
-    @staticmethod
-    def _exclusion_csr(users, item_ids, excl_users, excl_items):
-        """The exclusion CSR of the (excl_users[p], excl_items[p]) pairs for
-        the queried `users` (int64, ascending, distinct) over a candidate
-        frame whose rows hold `item_ids` (int64, distinct, any order): numpy
-        (indptr int64 [len(users) + 1], cols int32). Row q is users[q]; the
-        columns are candidate FRAME ROW indices, ascending and distinct. Pairs
-        with a user outside `users` or an item outside the frame are dropped.
-        Pure numpy."""
-        users = np.asarray(users, np.int64).reshape(-1)
-        item_ids = np.asarray(item_ids, np.int64).reshape(-1)
-        eu = np.asarray(excl_users, np.int64).reshape(-1)
-        ei = np.asarray(excl_items, np.int64).reshape(-1)
-        if eu.size != ei.size:
-            raise ValueError("exclude: userId and itemId must have the same length")
-        n_rows, n_cols = users.size, item_ids.size
-        indptr = np.zeros(n_rows + 1, np.int64)
-        if n_rows == 0 or n_cols == 0 or eu.size == 0:
-            return indptr, np.zeros(0, np.int32)
-        order = np.argsort(item_ids, kind="stable")  # sorted position -> frame row
-        sorted_ids = item_ids[order]
-        pi = np.minimum(np.searchsorted(sorted_ids, ei), n_cols - 1)
-        pu = np.minimum(np.searchsorted(users, eu), n_rows - 1)
-        ok = (sorted_ids[pi] == ei) & (users[pu] == eu)
-        key = np.unique(pu[ok] * n_cols + order[pi[ok]])  # ascending: by row, then by frame row
-        np.cumsum(np.bincount(key // n_cols, minlength=n_rows), out=indptr[1:])
-        return indptr, (key % n_cols).astype(np.int32)
-
-    @staticmethod
-    def _exclusion_csr_device(users, item_ids, excl_users, excl_items, dev):
-        """_exclusion_csr on the device (one sort of 64-bit keys), as
-        DeviceALSFactors.exclusion builds large lists: device (indptr, cols)."""
-        users = torch.as_tensor(users, dtype=torch.int64, device=dev)
-        item_ids = torch.as_tensor(item_ids, dtype=torch.int64, device=dev)
-        eu = torch.as_tensor(excl_users, dtype=torch.int64, device=dev)
-        ei = torch.as_tensor(excl_items, dtype=torch.int64, device=dev)
-        n_rows, n_cols = users.numel(), item_ids.numel()
-        indptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
-        if n_rows == 0 or n_cols == 0 or eu.numel() == 0:
-            return indptr, torch.zeros(0, dtype=torch.int32, device=dev)
-        sorted_ids, order = torch.sort(item_ids, stable=True)
-        pi = torch.searchsorted(sorted_ids, ei).clamp_(max=n_cols - 1)
-        pu = torch.searchsorted(users, eu).clamp_(max=n_rows - 1)
-        ok = (sorted_ids[pi] == ei) & (users[pu] == eu)
-        key = torch.unique(pu[ok] * n_cols + order[pi[ok]])  # sorted
-        if key.numel():
-            torch.cumsum(torch.bincount(torch.div(key, n_cols, rounding_mode="floor"), minlength=n_rows), 0,
-                         out=indptr[1:])
-        return indptr, torch.remainder(key, n_cols).to(torch.int32)
-
     def _exclusion(self, users, cand, exclude):
         """The device exclusion CSR of an `exclude` frame (columns userId,
-        itemId) for the queried users over the candidates' frame rows."""
+        itemId): row q is the queried users[q] (ascending, distinct), the
+        columns are candidate FRAME ROW indices (the frame holds its itemIds
+        in any order). Pairs with a user outside `users` or an item outside
+        the frame are dropped."""
         eu, ei = _int_ids(exclude["userId"], "userId"), _int_ids(exclude["itemId"], "itemId")
-        dev = self.model.device
-        if eu.size <= self.EXCLUSION_HOST_PAIRS:
-            indptr, cols = self._exclusion_csr(users, cand.item_ids, eu, ei)
-            return torch.as_tensor(indptr, device=dev), torch.as_tensor(cols, device=dev)
-        return self._exclusion_csr_device(users, cand.item_ids, eu, ei, dev)
+        return ranked_lists.exclusion_csr(users, cand.item_ids, eu, ei, self.model.device, self.EXCLUSION_HOST_PAIRS,
+                                          what="exclude: userId and itemId")
 
     def _query_users(self, users):
         """The distinct user ids, ascending (int64); an id outside the user
@@ -467,9 +418,7 @@ class TwoTowerModel:
         device (raw itemIds int64 [n, kk], scores f32 [n, kk], lens int32 [n]
         or None when every list is full), kk = min(num, candidates). Past a
         list's length: id 0, score NaN."""
-        num = int(num)
-        if not 1 <= num <= self.RECOMMEND_MAX:
-            raise ValueError(f"num_items must be in [1, {self.RECOMMEND_MAX}] (got {num})")
+        num = ranked_lists.check_num(num, self.RECOMMEND_MAX, "num_items")
         dev = self.model.device
         n, N = int(users.size), int(cand.vectors.shape[0])
         kk = min(num, N)
@@ -491,19 +440,12 @@ class TwoTowerModel:
             idx = torch.empty((n, kk), dtype=torch.int64, device=dev)
             val = torch.empty((n, kk), dtype=torch.float32, device=dev)
             lens = None if excl is None else torch.empty(n, dtype=torch.int32, device=dev)
-            sub = max(1, self.RECOMMEND_FALLBACK_BYTES // (4 * N))
-            for s in range(0, n, sub):
-                e = min(s + sub, n)
-                scores = _hrec.tt_score(U[s:e].contiguous(), V)
-                if excl is not None:
-                    lens[s:e] = _hrec.mask_rows(scores, rows[s:e], *excl).clamp_(max=kk)
-                idx[s:e], val[s:e] = _hrec.topk(scores, kk)
-                del scores
+            _hrec.topk_materialised(lambda s, e: _hrec.tt_score(U[s:e].contiguous(), V), 0, n, N, kk,
+                                    self.RECOMMEND_FALLBACK_BYTES, idx, val, lens,
+                                    None if excl is None else (rows, *excl))
         if lens is None:
             return cand.ids_dev[idx], val, None
-        live = torch.arange(kk, device=dev).unsqueeze(0) < lens.unsqueeze(1)
-        ids = torch.where(live, cand.ids_dev[idx.clamp_(0, N - 1)], torch.zeros_like(idx))
-        return ids, torch.where(live, val, torch.full_like(val, float("nan"))), lens
+        return (*ranked_lists.pad_lists(cand.ids_dev, idx, val, lens, N), lens)
 
     def recommend_for_users(self, users, item_features, num_items, exclude=None):
         """Top-n lists for many users in one device pass: a DataFrame with
@@ -528,11 +470,7 @@ class TwoTowerModel:
         cand = self.candidates(item_features)
         users = self._query_users(users)
         ids, val, lens = self._recommend_device(users, cand, num_items, exclude)
-        ids, val = ids.cpu().numpy().tolist(), val.cpu().numpy().tolist()
-        recs = [list(zip(i, s)) for i, s in zip(ids, val)]
-        if lens is not None:  # each list cut to its length
-            recs = [rec[:m] for rec, m in zip(recs, lens.cpu().numpy().tolist())]
-        return pd.DataFrame({"userId": users, "recommendations": recs})
+        return ranked_lists.lists_frame("userId", users, ids, val, lens)
 
     def recommend_for_all_users(self, item_features, num_items, exclude=None):
         """recommend_for_users for users 0 .. num_users - 1."""
@@ -552,44 +490,28 @@ class TwoTowerModel:
         recommend_for_users; each list is evaluated at its own length. A user
         id outside the table raises IndexError. The lists go from the top-k
         into hrec_ranking_metrics without leaving the device."""
-        k = int(k)
-        if not 1 <= k <= _hrec.RANK_MAX:
-            raise ValueError(f"k must be in [1, {_hrec.RANK_MAX}] (got {k})")
+        k = ranked_lists.check_num(k, _hrec.RANK_MAX, "k")
         cand = self.candidates(item_features)
         users, items = _int_ids(data["userId"], "userId"), _int_ids(data["itemId"], "itemId")
         if min_rating is not None:
             keep = np.asarray(data[label_col or "average_review_rating"], np.float64) >= float(min_rating)
             users, items = users[keep], items[keep]
         _ids(users, self.model.sizes["user_emb"], "user_in")  # range check (IndexError)
-        dev = self.model.device
-        build = ALSModel._label_csr_host if users.size <= self.RANKING_HOST_ROWS else ALSModel._label_csr_device
-        uniq, indptr, labels = build(users, items, dev)
+        uniq, indptr, labels = ranked_lists.label_csr(users, items, self.model.device, self.RANKING_HOST_ROWS)
         n = int(uniq.numel())
         res = {name: float("nan") for name in self.RANKING_METRIC_NAMES}
         res["count"] = n
         if n == 0:
             return res
         pred, _, pred_len = self._recommend_device(uniq.cpu().numpy(), cand, k, exclude)
-        sums, unsorted, _ = _hrec.ranking_metrics(pred, indptr, labels, k, pred_len=pred_len,
-                                                  pred_len_max=int(pred.shape[1]) if pred.numel() else 0)
-        s = torch.cat([sums, unsorted.to(torch.float64)]).tolist()  # one host read
-        if s[-1] != 0.0:
-            raise RuntimeError("ranking_metrics: a label row is not sorted ascending")
-        s = dict(zip(_hrec.RANK_SUMS, s))
-        if int(s["n_rows"]) != n:
-            raise RuntimeError(f"ranking_metrics: {int(s['n_rows'])} rows evaluated, {n} expected")
-        for name, slot in zip(self.RANKING_METRIC_NAMES, ("sum_ap", "sum_ap_k", "sum_precision", "sum_recall",
-                                                          "sum_ndcg")):
-            res[name] = s[slot] / n
+        res.update(ranked_lists.ranking_means(pred, pred_len, indptr, labels, k, n, self.RANKING_METRIC_NAMES))
         return res
 
     def evaluate_ranking(self, data, item_features, metric_name="meanAveragePrecision", k=10, label_col=None,
                          min_rating=None, exclude=None):
         """Spark's RankingEvaluator(metricName=metric_name, k=k).evaluate of
         the model's lists for the users of `data` (a float)."""
-        if metric_name not in self.RANKING_METRIC_NAMES:
-            raise ValueError(f"metric_name must be one of {', '.join(self.RANKING_METRIC_NAMES)} "
-                             f"(got {metric_name!r})")
+        ranked_lists.check_metric_name(metric_name, self.RANKING_METRIC_NAMES)
         return float(self.ranking_metrics(data, item_features, k, label_col, min_rating, exclude)[metric_name])
 
     # --------------------------------------------------------- persistence

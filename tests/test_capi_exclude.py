@@ -1,7 +1,7 @@
 """CPU: the seen-item exclusion entries of the C-ABI (hrec_als_score_topk_excluding,
 its workspace query, hrec_mask_rows_f32) are exported and bound, check their
-arguments before any device work, and the host exclusion builder
-(DeviceALSFactors._exclusion_host) equals a numpy restatement."""
+arguments before any device work. (The host exclusion builder:
+tests/test_exclusion_host.py.)"""
 import ctypes
 
 import numpy as np
@@ -103,44 +103,3 @@ def test_workspace_query(lib):
                 assert need >= base(n_users, n_items, top_k) > 0
                 assert need >= prev
                 prev = need
-
-
-def _restated(side, known_users, known_items, users, items):
-    """The exclusion CSR by sets: per known row the sorted distinct known columns."""
-    urow = {int(u): r for r, u in enumerate(known_users)}
-    irow = {int(i): r for r, i in enumerate(known_items)}
-    n_rows = len(known_users) if side == "user" else len(known_items)
-    sets = [set() for _ in range(n_rows)]
-    for u, i in zip(users.tolist(), items.tolist()):
-        if u in urow and i in irow:
-            r, c = (urow[u], irow[i]) if side == "user" else (irow[i], urow[u])
-            sets[r].add(c)
-    indptr = np.cumsum([0] + [len(s) for s in sets]).astype(np.int64)
-    cols = np.array([c for s in sets for c in sorted(s)], np.int32)
-    return indptr, cols
-
-
-@pytest.mark.parametrize("side", ["user", "item"])
-def test_host_exclusion_builder(side):
-    from src.als_model import DeviceALSFactors
-
-    known_users = -50 + 3 * np.arange(37, dtype=np.int64)
-    known_items = -40 + 7 * np.arange(29, dtype=np.int64)
-    rng = np.random.default_rng(11)
-    users = np.r_[rng.choice(known_users, 400), [-49, 10 ** 6, int(known_users[3])]]  # two unknown users
-    items = np.r_[rng.choice(known_items, 400), [int(known_items[0]), -39, 5]]         # two unknown items
-    again = rng.integers(0, len(users), 60)                                             # duplicates
-    users, items = np.r_[users, users[again]], np.r_[items, items[again]]
-    perm = rng.permutation(len(users))                                                  # unsorted
-    users, items = users[perm], items[perm]
-    indptr, cols = DeviceALSFactors._exclusion_host(side, known_users, known_items, users, items)
-    e_indptr, e_cols = _restated(side, known_users, known_items, users, items)
-    assert indptr.dtype == np.int64 and cols.dtype == np.int32
-    assert np.array_equal(indptr, e_indptr) and np.array_equal(cols, e_cols)
-    assert 0 < len(cols) < 400  # duplicates went, something stayed
-    # nothing known, and nothing at all: an empty CSR over every row
-    for u, i in ((np.array([10 ** 6]), np.array([5])), (np.zeros(0, np.int64), np.zeros(0, np.int64))):
-        indptr, cols = DeviceALSFactors._exclusion_host(side, known_users, known_items, u, i)
-        assert len(indptr) == (37 if side == "user" else 29) + 1 and not indptr.any() and len(cols) == 0
-    with pytest.raises(ValueError):
-        DeviceALSFactors._exclusion_host(side, known_users, known_items, users, items[:-1])
