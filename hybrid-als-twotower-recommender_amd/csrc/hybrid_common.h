@@ -54,6 +54,25 @@ __device__ __forceinline__ double hp_fuse(const HpScale& s, float a, float t, do
   return w0 * an + w1 * (double)tn;
 }
 
+// The same with genuine f64 ALS extremes and scores (hrec_hybrid_lists: the
+// cold-start fallback vector is f64): hrec_fuse_topk's coefficients, and
+// hp_scale's bit for bit when amin / amax are widened f32 values.
+__device__ __forceinline__ HpScale hp_scale64(double amin, double amax, float tmin, float tmax) {
+#pragma clang fp contract(off)
+  HpScale s;
+  s.ascale = 1.0 / mm_range(amax - amin);
+  s.amin_ = 0.0 - amin * s.ascale;
+  s.tscale = 1.0f / mm_range(tmax - tmin);
+  s.tmin_ = 0.0f - tmin * s.tscale;
+  return s;
+}
+__device__ __forceinline__ double hp_fuse64(const HpScale& s, double a, float t, double w0, double w1) {
+#pragma clang fp contract(off)
+  const double an = a * s.ascale + s.amin_;
+  const float tn = t * s.tscale + s.tmin_;
+  return w0 * an + w1 * (double)tn;
+}
+
 // Order of every top-k: larger value first; equal values -> smaller index
 // first (a stable descending sort of the input order). NaN sorts last.
 template <typename T>

@@ -90,6 +90,9 @@ _SIGNATURES = {
     "hrec_fuse_rows_topk": (_c_i32, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i32, _c_i32, _c_i64, _vp, _vp,
                                      _vp, _c_sz, _vp]),
     "hrec_topk_f64_keyed": (_c_i32, [_vp, _vp, _c_i64, _c_i64, _c_i32, _vp, _vp, _vp, _c_sz, _vp]),
+    "hrec_hybrid_lists_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i32, _c_i32]),
+    "hrec_hybrid_lists": (_c_i32, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _c_i32, _c_i32, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
     "hrec_fuse_workspace_bytes": (_c_sz, [_c_i64, _c_i32]),
     "hrec_fuse_topk": (_c_i32, [_vp, _vp, _c_i32, _c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp,
                                 _c_sz, _vp]),
@@ -1507,6 +1510,63 @@ def topk_keyed(vals, keys, top_k):
         _dev(out_i, torch.int64, "out_idx"), _dev(out_v, torch.float64, "out_val"), _dev(ws, torch.uint8, "ws"),
         need, _stream()))
     return out_i, out_v
+
+
+# ----------------------------------------------------- hybrid ranked lists
+HYBRID_LISTS_SAMPLE = 4096  # HREC_HYBRID_LISTS_SAMPLE: columns whose kk-th best key bounds a row (mode 0)
+HYBRID_LISTS_CAP = 4096     # HREC_HYBRID_LISTS_CAP: entries of a row's list (mode 0)
+
+
+def hybrid_lists(als, tt, top_k, als_wins, fallback=None, excl=None, mode=0, want_minmax=False):
+    """hrec_hybrid_lists over the f32 device score matrices als / tt [n_rows,
+    n] (unit column stride, one shared row stride >= n): per row the stable
+    descending ranking of hrec_fuse_topk's fused scores without the row's
+    excluded columns, cut to kk = min(top_k, n). fallback (f64 [n] device,
+    optional) replaces NaN ALS entries per column; excl (optional) =
+    (excl_rows int64 [n_rows], excl_indptr int64, excl_cols int32), the CSR
+    of dot_topk_excluding. mode 0: bounded (a set overflow flag means some
+    row's list was cut: repeat with mode 1); mode 1: full. Returns (idx int64
+    [n_rows, kk], val f64 [n_rows, kk], lens int32 [n_rows], overflow int32
+    [1][, minmax f64 [n_rows, 4]]) as device tensors; entries past a row's
+    length are unspecified."""
+    name = "hybrid_lists"
+    for t, what in ((als, "als"), (tt, "tt")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
+            raise HrecError(f"{name}: {what} must be a 2-D f32 device tensor")
+    n_rows, n = als.shape
+    if tuple(tt.shape) != (n_rows, n):
+        raise HrecError(f"{name}: als and tt must have the same shape")
+    if n_rows > 1:
+        ld = int(als.stride(0))
+        if als.stride(1) != 1 or tt.stride(1) != 1 or int(tt.stride(0)) != ld or ld < n:
+            raise HrecError(f"{name}: als and tt need unit column stride and one row stride >= n")
+    else:
+        als, tt, ld = als.contiguous(), tt.contiguous(), n
+    if fallback is not None and fallback.numel() != n:
+        raise HrecError(f"{name}: fallback must hold one value per column")
+    dev = als.device
+    kk = min(int(top_k), n)
+    idx = torch.empty((n_rows, kk), dtype=torch.int64, device=dev)
+    val = torch.empty((n_rows, kk), dtype=torch.float64, device=dev)
+    lens = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+    minmax = torch.empty((n_rows, 4), dtype=torch.float64, device=dev) if want_minmax else None
+    if excl is not None:
+        if excl[0].numel() != n_rows:
+            raise HrecError(f"{name}: excl_rows must hold one entry per row")
+        excl_args = (_dev(excl[0], torch.int64, f"{name}: excl_rows"), *_excl_args(name, excl[1], excl[2]))
+    else:
+        excl_args = (None, None, None)
+    need = int(lib().hrec_hybrid_lists_workspace_bytes(n_rows, n, int(top_k), int(mode)))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    _check("hrec_hybrid_lists", lib().hrec_hybrid_lists(
+        _vp(als.data_ptr()), _vp(tt.data_ptr()), n_rows, n, ld, _dev(fallback, torch.float64, "fallback"),
+        int(bool(als_wins)), int(top_k), int(mode), *excl_args, _dev(idx, torch.int64, "out_idx"),
+        _dev(val, torch.float64, "out_val"), _dev(lens, torch.int32, "out_len"),
+        _dev(minmax, torch.float64, "out_minmax"), _dev(overflow, torch.int32, "overflow"),
+        _dev(ws, torch.uint8, "ws"), need, _stream()))
+    res = (idx, val, lens, overflow)
+    return res + (minmax,) if want_minmax else res
 
 
 # ------------------------------------------------------- multi-GPU (C-ABI)

@@ -9,6 +9,13 @@ pinned numpy, requirements.txt:5), and a stable descending top-k that keeps
 Python's sorted(..., reverse=True) tie order. The item order of the fused
 list is the iteration order of set(als).union(set(tt)) (:61), built on the
 host exactly as the reference builds it.
+
+Not in the reference (failures raise): recommend_for_users /
+recommend_for_all_users (the fused model's top-n lists for many users in one
+device pass, with an optional seen-item exclusion) and ranking_metrics /
+evaluate_ranking (Spark's five ranking metrics of those lists against a
+held-out frame) — hrec_hybrid_lists over both models' batched scores. Equal
+fused scores keep candidate-frame order there, not the set order above.
 """
 import itertools
 import os
@@ -19,8 +26,8 @@ import pandas as pd
 import torch
 from sklearn.preprocessing import MinMaxScaler
 
-from . import _hrec
-from .als_model import ALSModel
+from . import _hrec, ranked_lists
+from .als_model import ALSModel, _int_ids
 from .evaluation import compute_f1_score
 from .two_tower_model import TwoTowerModel
 
@@ -283,6 +290,162 @@ class HybridRecommendationSystem:
         _set_fitted(self.als_scaler, m[0], m[1], n, np.float64)
         _set_fitted(self.twotower_scaler, m[2], m[3], n, np.float32)
         return [(item(int(i)), np.float64(s)) for i, s in zip(idx_h[:k], sc_h[:k])]
+
+    # ------------------------------------- batch top-n lists / ranking metrics
+    # None of these has a counterpart in the reference: failures raise. The
+    # third member of the family ALSModel.recommend_for_* / TwoTowerModel.
+    # recommend_for_users started, over the same ranked_lists helpers.
+    RECOMMEND_MAX = 1024               # largest list length (the library's top_k limit)
+    RECOMMEND_SCORE_BYTES = 1 << 30    # a sub-batch's two score matrices (mode 1: its key matrix) stay under this
+    RECOMMEND_ROWS = 65535             # rows of one hrec_hybrid_lists call
+    RANKING_HOST_ROWS = TwoTowerModel.RANKING_HOST_ROWS
+    RANKING_METRIC_NAMES = TwoTowerModel.RANKING_METRIC_NAMES
+
+    def _require_models(self):
+        if not self.models_loaded:
+            raise ValueError("Models not loaded. Call load_models() first.")
+
+    def _als_fallback(self, users, keys):
+        """The f64 device vector that stands in for NaN transform results
+        (ALSModel._cold_scores: what _predictions substitutes per item), or
+        None when the ALS model knows every queried user and every candidate.
+        Unknown ids without that vector raise ValueError."""
+        m = self.als_model.model
+        if m is None:
+            raise RuntimeError("the ALS model is not trained or loaded")
+        cold_users = int((m._lookup(m.user_ids, users) < 0).sum())
+        cold_items = int((m._lookup(m.item_ids, keys) < 0).sum())
+        if not cold_users and not cold_items:
+            return None
+        fb = self.als_model._cold_scores(keys)
+        if fb is None:
+            raise ValueError(f"{cold_users} queried user(s) and {cold_items} candidate item(s) are unknown to the ALS "
+                             "model and its cold-start fallback vector is not available (item_features missing, "
+                             "non-finite or outside hrec_cold_fallback); the per-call similarity search is not "
+                             "part of the batched lists")
+        return fb
+
+    def _recommend_device(self, users, cand, num, exclude=None):
+        """Top-`num` fused candidates for each of `users` (TwoTowerModel.
+        _query_users' array): device (raw itemIds int64 [n, kk], fused scores
+        f64 [n, kk], lens int32 [n] or None when every list is full), kk =
+        min(num, candidates). Past a list's length: id 0, score NaN. Users go
+        through hrec_hybrid_lists in sub-batches (mode 0); the sub-batches
+        whose overflow flag is set — read back once, after the last one — are
+        redone in mode 1."""
+        num = ranked_lists.check_num(num, self.RECOMMEND_MAX, "num_items")
+        tt, als = self.twotower_model, self.als_model
+        dev = tt.model.device
+        n, N = int(users.size), len(cand)
+        kk = min(num, N)
+        if n == 0 or kk == 0:
+            return (torch.zeros((n, kk), dtype=torch.int64, device=dev),
+                    torch.zeros((n, kk), dtype=torch.float64, device=dev),
+                    None if exclude is None else torch.zeros(n, dtype=torch.int32, device=dev))
+        excl = tt._exclusion(users, cand, exclude) if exclude is not None else None
+        keys = cand.item_ids
+        fallback = self._als_fallback(users, keys)
+        als_wins = self.als_f1_score > self.twotower_f1_score
+        rows = torch.arange(n, dtype=torch.int64, device=dev)  # query q reads exclusion row q
+        idx = torch.empty((n, kk), dtype=torch.int64, device=dev)
+        val = torch.empty((n, kk), dtype=torch.float64, device=dev)
+        lens = torch.empty(n, dtype=torch.int32, device=dev)
+
+        def run(s, e, mode):
+            a = als.model.score(users[s:e], keys)  # transform's f32, NaN where an id is unknown
+            U = tt.model.user_vectors(torch.as_tensor(users[s:e].astype(np.int32), device=dev))
+            t = _hrec.tt_score(U, cand.vectors)    # the bits predict_for_user gives
+            i, v, m, over = _hrec.hybrid_lists(a, t, kk, als_wins, fallback=fallback,
+                                               excl=None if excl is None else (rows[s:e], *excl), mode=mode)
+            idx[s:e], val[s:e], lens[s:e] = i, v, m
+            return over
+
+        sub = max(1, min(self.RECOMMEND_ROWS, self.RECOMMEND_SCORE_BYTES // (8 * N)))
+        spans = [(s, min(s + sub, n)) for s in range(0, n, sub)]
+        flagged = torch.cat([run(s, e, 0) for s, e in spans]).tolist()  # one host read
+        sub1 = max(1, min(self.RECOMMEND_ROWS, self.RECOMMEND_SCORE_BYTES // (16 * N)))
+        for (s, e), over in zip(spans, flagged):
+            if over:
+                for s1 in range(s, e, sub1):
+                    run(s1, min(s1 + sub1, e), 1)
+        ids, val = ranked_lists.pad_lists(cand.ids_dev, idx, val, lens, N)
+        return ids, val, (None if exclude is None else lens)
+
+    def recommend_for_users(self, users, item_features, num_items, exclude=None):
+        """Top-n lists of the fused model for many users in one device pass:
+        a DataFrame with `userId` (the distinct ids of `users`, ascending; a
+        DataFrame with a userId column or an array-like) and `recommendations`:
+        the user's top num_items (1 .. 1024) candidates of `item_features` (a
+        frame, or TwoTowerModel.candidates()'s object) as (itemId, score)
+        tuples, best first. A score is bit for bit the np.float64 that
+        adaptive_fusion(als_model.predict_for_user(u, ids), twotower_model.
+        predict_for_user(u, frame)) gives that pair over the same frame, with
+        the weights als_f1_score / twotower_f1_score choose at call time. The
+        ALS score of a pair is transform's f32; where that is NaN (a user or
+        an item the ALS model does not know) it is the item's cold-start
+        value, ALSModel._cold_scores — when that vector is not available and
+        some queried user or candidate is unknown, ValueError. A user id
+        outside the two-tower user table raises IndexError.
+        exclude (optional): a DataFrame with userId and itemId columns,
+        typically the training frame. Both scalers are fitted over ALL
+        candidates, excluded ones included (the left-anti join comes after
+        the ranking and does not re-scale): each list is the full ranking
+        without the excluded pairs, cut to num_items, shorter only when fewer
+        entries remain; a user with everything excluded keeps its row with an
+        empty list.
+        Ties: equal fused scores keep candidate-frame order. The reference
+        (and get_hybrid_recommendations) orders them by the iteration order
+        of a Python set; the lists do not reproduce that.
+        Non-finite scores: a row follows hrec_fuse_topk's arithmetic — NaN is
+        ignored by the scalers and a NaN fused score ranks last, in frame
+        order; the ValueError the per-user path raises for infinite scores is
+        not reproduced. One GPU; models not loaded raise ValueError."""
+        self._require_models()
+        cand = self.twotower_model.candidates(item_features)
+        users = self.twotower_model._query_users(users)
+        ids, val, lens = self._recommend_device(users, cand, num_items, exclude)
+        return ranked_lists.lists_frame("userId", users, ids, val, lens)
+
+    def recommend_for_all_users(self, item_features, num_items, exclude=None):
+        """recommend_for_users for every user of the two-tower user table."""
+        self._require_models()
+        return self.recommend_for_users(np.arange(int(self.twotower_model.num_users), dtype=np.int64), item_features,
+                                        num_items, exclude)
+
+    def ranking_metrics(self, data, item_features, k=10, label_col=None, min_rating=None, exclude=None):
+        """Spark's RankingMetrics (binary relevance) of the fused model's top-k
+        lists over `item_features` against `data` (columns userId, itemId):
+        the five RANKING_METRIC_NAMES plus "count", with TwoTowerModel.
+        ranking_metrics' semantics (ground truth = the user's itemIds in
+        `data`, of the rows with label_col >= min_rating when given; each
+        metric the mean over the `count` users, NaN when count is 0; each list
+        evaluated at its own length). exclude as in recommend_for_users. The
+        lists go from hrec_hybrid_lists into hrec_ranking_metrics without
+        leaving the device."""
+        self._require_models()
+        k = ranked_lists.check_num(k, _hrec.RANK_MAX, "k")
+        tt = self.twotower_model
+        cand = tt.candidates(item_features)
+        users, items = _int_ids(data["userId"], "userId"), _int_ids(data["itemId"], "itemId")
+        if min_rating is not None:
+            keep = np.asarray(data[label_col or "average_review_rating"], np.float64) >= float(min_rating)
+            users, items = users[keep], items[keep]
+        uniq, indptr, labels = ranked_lists.label_csr(users, items, tt.model.device, self.RANKING_HOST_ROWS)
+        n = int(uniq.numel())
+        res = {name: float("nan") for name in self.RANKING_METRIC_NAMES}
+        res["count"] = n
+        if n == 0:
+            return res
+        pred, _, pred_len = self._recommend_device(tt._query_users(uniq.cpu().numpy()), cand, k, exclude)
+        res.update(ranked_lists.ranking_means(pred, pred_len, indptr, labels, k, n, self.RANKING_METRIC_NAMES))
+        return res
+
+    def evaluate_ranking(self, data, item_features, metric_name="meanAveragePrecision", k=10, label_col=None,
+                         min_rating=None, exclude=None):
+        """Spark's RankingEvaluator(metricName=metric_name, k=k).evaluate of
+        the fused model's lists for the users of `data` (a float)."""
+        ranked_lists.check_metric_name(metric_name, self.RANKING_METRIC_NAMES)
+        return float(self.ranking_metrics(data, item_features, k, label_col, min_rating, exclude)[metric_name])
 
     def cleanup(self):
         if self.als_model:

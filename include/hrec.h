@@ -22,6 +22,8 @@
  *   Spark  RankingEvaluator / RankingMetrics
  *          (no reference line)                        -> hrec_ranking_metrics
  *   Python/sklearn fusion     src/hybrid_system.py:57-75,108 -> hrec_fuse_topk
+ *          the same for many users, minus seen pairs
+ *          (no reference line)                        -> hrec_hybrid_lists
  *   Keras  two-tower graph    src/two_tower_model.py:38-89 -> hrec_tt_*
  *   Keras  Dot + sorted(...)[:k] for many users        -> hrec_dot_topk
  *          the same minus a training frame's pairs
@@ -531,6 +533,39 @@ int hrec_fuse_rows_topk(const float* als, const float* tt, int64_t n_rows, int64
 int hrec_topk_f64_keyed(const double* vals, const int64_t* keys, int64_t n_rows, int64_t n,
                         int top_k, int64_t* out_idx, double* out_val, void* workspace,
                         size_t workspace_bytes, void* stream);
+
+/* Hybrid ranked lists (additive to ABI 7): for each row r of the f32 score
+ * matrices als / tt [n_rows, ld] (ld >= n, n_rows < 65536), the stable
+ * descending ranking that hrec_fuse_topk(a_r, tt_r as f32, n, als_wins,
+ * top_k = n) gives, with the row's excluded columns deleted, cut to kk =
+ * min(top_k, n) (top_k in [1, 1024]): the same indices, out_val bits and
+ * out_minmax[r] ([n_rows][4], or NULL). a_rj = als_fallback[j] where
+ * als[r][j] is NaN and als_fallback ([n] f64, or NULL) is given, else
+ * (double)als[r][j]. Both scalers see every column, excluded ones included;
+ * equal fused scores keep column order; NaN fused scores rank last.
+ * Exclusion (hrec_mask_rows_f32's convention): row r's set is
+ * excl_cols[excl_indptr[q] .. excl_indptr[q + 1]) with q = excl_rows[r] (q <
+ * 0: empty), ascending, duplicates counting once, a column outside [0, n)
+ * ignored and never used as an index; all three NULL: nothing excluded.
+ * out_len[r] = min(kk, n - distinct in-range excluded columns); entries at
+ * positions >= out_len[r] are unspecified; an excluded column never appears
+ * before out_len[r].
+ * mode 0 (bounded): each row's first HREC_HYBRID_LISTS_SAMPLE columns give a
+ * lower bound of its kk-th key; the columns reaching it go to a list of
+ * HREC_HYBRID_LISTS_CAP entries. *overflow = 1 when some row had more: the
+ * answer is then incomplete (rows that fit are still right) and the caller
+ * repeats the call with mode 1. n <= HREC_HYBRID_LISTS_SAMPLE never
+ * overflows. mode 1 (full): every fused key is written to the workspace and
+ * ranked; always complete, *overflow = 0; >= 16 * n_rows * n bytes. */
+#define HREC_HYBRID_LISTS_SAMPLE 4096
+#define HREC_HYBRID_LISTS_CAP 4096
+size_t hrec_hybrid_lists_workspace_bytes(int64_t n_rows, int64_t n, int top_k, int mode);
+int hrec_hybrid_lists(const float* als, const float* tt, int64_t n_rows, int64_t n, int64_t ld,
+                      const double* als_fallback, int als_wins, int top_k, int mode,
+                      const int64_t* excl_rows, const int64_t* excl_indptr,
+                      const int32_t* excl_cols, int64_t* out_idx, double* out_val,
+                      int32_t* out_len, double* out_minmax, int* overflow, void* workspace,
+                      size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------ cold-start sim --
  * ALSModel._find_similar_items (src/als_model.py:93-104): out[q*n_items+j] =
