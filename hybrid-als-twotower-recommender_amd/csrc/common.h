@@ -19,6 +19,12 @@ int check_launch(const char* what);
 
 constexpr int kWave = 64;
 
+// The lanes below this one that are set in a __ballot mask: a lane's rank
+// among the lanes that voted yes.
+__device__ __forceinline__ int lanes_below(uint64_t mask) {
+  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
 // Leading dimensions of factor matrices: 16/32/64 (one wave per row in the
 // half-sweep) and 96/128/192/256 (one workgroup per row, csrc/als_wide.hip).
 inline bool hrec_factor_ld_ok(int kp) {
@@ -174,6 +180,26 @@ int dot_filter_run(const void* U, int B, const void* V, int64_t n_items, int dk,
 int dot_scores_run(const void* U, int B, const void* V, int64_t n_items, int dk, int bf16, float* out, int64_t ldo,
                    hipStream_t s, int ub_cap = 0);
 int count_overflow(const int* cn, int n_users, int cap, int* flag, hipStream_t s);
+// csrc/exclusion.hip: the exclusion CSR of a call (csrc/exclusion.h has the
+// convention; on: an *_excluding entry point) and its two launches.
+struct Excl {
+  bool on;
+  const int64_t* rows;  // row ids (ALS: the factor rows of the call)
+  const int64_t* indptr;
+  const int32_t* cols;
+  int32_t* out_len;
+};
+// vals[i][c / step] = fill for every column c in [0, n) of row i's set with
+// c % step == 0 and c / step < S (vals: [n_rows][row_stride >= S], column s
+// holding item s * step; null: lengths only); kept_out[i] (optional) =
+// min(len_cap, n - distinct columns in [0, n)).
+int excl_mask_run(float* vals, int64_t n_rows, int64_t row_stride, int64_t S, int64_t step, int64_t n,
+                  const Excl& x, float fill, int64_t len_cap, int32_t* kept_out, hipStream_t s);
+// cand_v[b][e] = NaN for every candidate e < min(cand_n[b], cap) whose item
+// cand_i[b][e] is in query b's set; out_len[b] (optional) = min(kk, candidates
+// that stay).
+int excl_drop_run(const Excl& x, int n_users, float* cand_v, const int64_t* cand_i, const int* cand_n, int cap,
+                  int kk, int32_t* out_len, hipStream_t s);
 // csrc/dot_gemv.hip: the few-user (B <= 4, f32) streaming scoring kernel, same
 // contract and same score bits as the matrix-core launch of csrc/dot_topk.hip
 // (FILTER: the per-user survivor filter, thr_per == 0).

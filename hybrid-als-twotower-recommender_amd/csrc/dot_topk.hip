@@ -264,86 +264,6 @@ __global__ void dot_offset_kernel(int64_t* __restrict__ idx, int64_t n, int64_t 
   if (i < n && idx[i] >= 0) idx[i] += off;
 }
 
-// ------------------------------------------------- exclusion (seen items)
-// hrec_dot_topk_excluding's two kernels. The exclusion set of query b is
-// excl_cols[excl_indptr[r] .. excl_indptr[r + 1]) with r = excl_rows[b] (r < 0:
-// empty), columns = local item indices, ascending, duplicates allowed
-// (hrec_mask_rows_f32's convention).
-//
-// Masking, strided: vals is [n_rows][S], column s holding item s * step (the
-// sample of hrec_dot_topk; step 1 and S = n_items: the full score matrix). One
-// wave per query, lanes striding the segment: an excluded item c in [0,
-// n_items) with c % step == 0 and c / step < S gets vals[b][c / step] = fill;
-// any other column touches nothing (a column outside [0, n_items) is never
-// used as an index), and the walk stops at the first stride that meets a
-// column >= n_items. vals may be null (lengths only). out_len[b] = min(kk,
-// n_items - distinct columns in [0, n_items)); a column counts where it
-// differs from its left neighbour.
-__global__ __launch_bounds__(256) void dot_mask_excluded_kernel(float* __restrict__ vals, int n_rows, int64_t S,
-                                                                int64_t step, int64_t n_items,
-                                                                const int64_t* __restrict__ excl_rows,
-                                                                const int64_t* __restrict__ excl_indptr,
-                                                                const int32_t* __restrict__ excl_cols, float fill,
-                                                                int kk, int32_t* __restrict__ out_len) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= n_rows) return;  // wave-uniform
-  const int64_t r = excl_rows[row];
-  const int64_t lo = r >= 0 ? excl_indptr[r] : 0, hi = r >= 0 ? excl_indptr[r + 1] : 0;
-  int64_t distinct = 0;
-  for (int64_t p0 = lo; p0 < hi; p0 += 64) {  // wave-uniform trip count
-    const int64_t p = p0 + lane;
-    bool counted = false, past = false;
-    if (p < hi) {
-      const int64_t c = excl_cols[p];
-      past = c >= n_items;
-      if (c >= 0 && !past) {
-        const int64_t sc = c / step;
-        if (vals && sc * step == c && sc < S) vals[(int64_t)row * S + sc] = fill;  // duplicates store the same value
-        counted = p == lo || (int64_t)excl_cols[p - 1] != c;
-      }
-    }
-    distinct += __popcll(__ballot(counted));
-    if (__ballot(past)) break;
-  }
-  if (lane == 0) {
-    const int64_t kept = n_items - distinct;
-    out_len[row] = (int32_t)(kept < kk ? kept : kk);
-  }
-}
-
-// The filter's candidates without the excluded items: one block per query, a
-// thread per candidate, a binary search of the query's ascending segment; an
-// excluded candidate's score becomes NaN (ranked last by the stable top-k).
-// The lists hold local item indices here (idx_offset is added to the ranked
-// result afterwards), which is what the columns are; the (-inf, INT64_MAX - 1)
-// fillers of an overflowed list match no column. A list past the cap is read
-// up to the cap.
-__global__ __launch_bounds__(256) void dot_drop_excluded_kernel(const int64_t* __restrict__ excl_rows,
-                                                                const int64_t* __restrict__ excl_indptr,
-                                                                const int32_t* __restrict__ excl_cols,
-                                                                float* __restrict__ cand_v,
-                                                                const int64_t* __restrict__ cand_i,
-                                                                const int* __restrict__ cand_n, int cap) {
-  const int b = blockIdx.x;
-  const int64_t r = excl_rows[b];
-  if (r < 0) return;  // block-uniform
-  const int64_t lo = excl_indptr[r], hi = excl_indptr[r + 1];
-  if (lo >= hi) return;
-  const int n = cand_n[b] < cap ? cand_n[b] : cap;
-  const float qnan = __builtin_nanf("");
-  for (int e = threadIdx.x; e < n; e += blockDim.x) {
-    const int64_t j = cand_i[(int64_t)b * cap + e];
-    int64_t a = lo, z = hi;  // the first position with a column >= j
-    while (a < z) {
-      const int64_t mid = a + ((z - a) >> 1);
-      if ((int64_t)excl_cols[mid] < j) a = mid + 1;
-      else z = mid;
-    }
-    if (a < hi && (int64_t)excl_cols[a] == j) cand_v[(int64_t)b * cap + e] = qnan;
-  }
-}
-
 // f32 -> bf16 bit patterns (bf16_rne).
 __global__ void f32_to_bf16_kernel(const float* __restrict__ in, int64_t n, uint16_t* __restrict__ out) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
@@ -974,27 +894,12 @@ extern "C" size_t hrec_dot_topk_workspace_bytes(int n_users, int64_t n_items, in
   return dot_layout(nullptr, n_users > 0 ? n_users : 0, n_items, kk).total;
 }
 
-// The exclusion of a call (on: hrec_dot_topk_excluding).
-struct DotExcl {
-  bool on;
-  const int64_t* rows;
-  const int64_t* indptr;
-  const int32_t* cols;
-  int32_t* out_len;
-};
-
-static int dot_mask_run(float* vals, int n_users, int64_t S, int64_t step, int64_t n_items, const DotExcl& x,
-                        float fill, int kk, hipStream_t s) {
-  hipLaunchKernelGGL(dot_mask_excluded_kernel, dim3((unsigned)((n_users + 3) / 4)), dim3(256), 0, s, vals, n_users, S,
-                     step, n_items, x.rows, x.indptr, x.cols, fill, kk, x.out_len);
-  return check_launch("dot_mask_excluded_kernel");
-}
-
 // hrec_dot_topk and hrec_dot_topk_excluding (x.on): the same launches, the
-// exclusion's kernels between them.
+// exclusion's kernels (csrc/exclusion.hip; columns = local item indices)
+// between them.
 static int dot_topk_run(const char* fn, const void* user_vec, int n_users, const void* item_vec, int64_t n_items,
                         int dk, int dtype, int top_k, const float* thr_in, int64_t idx_offset, int64_t* out_idx,
-                        float* out_val, int* overflow, void* workspace, size_t workspace_bytes, const DotExcl& x,
+                        float* out_val, int* overflow, void* workspace, size_t workspace_bytes, const Excl& x,
                         void* stream) {
   int rc = dot_check(user_vec, n_users, item_vec, n_items, dk, dtype, fn);
   if (rc) return rc;
@@ -1015,7 +920,7 @@ static int dot_topk_run(const char* fn, const void* user_vec, int n_users, const
                            nullptr, nullptr, 0, s);
     if (rc) return rc;
     if (x.on) {  // excluded scores -> NaN: ranked after every score that stays
-      rc = dot_mask_run(w.samp, n_users, n_items, 1, n_items, x, __builtin_nanf(""), kk, s);
+      rc = excl_mask_run(w.samp, n_users, n_items, n_items, 1, n_items, x, __builtin_nanf(""), kk, x.out_len, s);
       if (rc) return rc;
     }
     rc = topk_rows<float>(w.samp, n_users, n_items, n_items, kk, out_idx, out_val, w.tws, (size_t)1 << 62, s);
@@ -1031,7 +936,7 @@ static int dot_topk_run(const char* fn, const void* user_vec, int n_users, const
         // the bound is over the sample's items that stay: the sample columns of
         // excluded items -> -inf (a query with fewer than kk left gets -inf and
         // admits every score); also writes out_len
-        rc = dot_mask_run(w.samp, n_users, S, step, n_items, x, -INFINITY, kk, s);
+        rc = excl_mask_run(w.samp, n_users, S, S, step, n_items, x, -INFINITY, kk, x.out_len, s);
         if (rc) return rc;
       }
       rc = topk_rows<float>(w.samp, n_users, S, S, kk, w.si, w.sv, w.tws, (size_t)1 << 62, s);
@@ -1039,7 +944,7 @@ static int dot_topk_run(const char* fn, const void* user_vec, int n_users, const
       thr = w.sv + (kk - 1);
       thr_stride = kk;
     } else if (x.on) {  // a caller's bound: the lengths alone
-      rc = dot_mask_run(nullptr, n_users, 0, 1, n_items, x, 0.f, kk, s);
+      rc = excl_mask_run(nullptr, n_users, 0, 0, 1, n_items, x, 0.f, kk, x.out_len, s);
       if (rc) return rc;
     }
     // 2) fused score + survivor filter over every item
@@ -1052,9 +957,7 @@ static int dot_topk_run(const char* fn, const void* user_vec, int n_users, const
     rc = check_launch("dot_overflow_kernel");
     if (rc) return rc;
     if (x.on) {  // the filter also kept excluded items that reach the bound
-      hipLaunchKernelGGL(dot_drop_excluded_kernel, dim3((unsigned)n_users), dim3(256), 0, s, x.rows, x.indptr, x.cols,
-                         w.cv, w.ci, w.cn, (int)cap);
-      rc = check_launch("dot_drop_excluded_kernel");
+      rc = excl_drop_run(x, n_users, w.cv, w.ci, w.cn, (int)cap, kk, nullptr, s);
       if (rc) return rc;
     }
     // 3) exact stable top-k of the survivors (item index breaks ties)
@@ -1068,7 +971,7 @@ extern "C" int hrec_dot_topk(const void* user_vec, int n_users, const void* item
                              int dtype, int top_k, const float* thr_in, int64_t idx_offset, int64_t* out_idx,
                              float* out_val, int* overflow, void* workspace, size_t workspace_bytes, void* stream) {
   return dot_topk_run("dot_topk", user_vec, n_users, item_vec, n_items, dk, dtype, top_k, thr_in, idx_offset, out_idx,
-                      out_val, overflow, workspace, workspace_bytes, DotExcl{}, stream);
+                      out_val, overflow, workspace, workspace_bytes, Excl{}, stream);
 }
 
 // The exclusion lives in the caller's buffers: the workspace is hrec_dot_topk's.
@@ -1083,5 +986,5 @@ extern "C" int hrec_dot_topk_excluding(const void* user_vec, int n_users, const 
                                        int* overflow, void* workspace, size_t workspace_bytes, void* stream) {
   return dot_topk_run("dot_topk_excluding", user_vec, n_users, item_vec, n_items, dk, dtype, top_k, thr_in,
                       idx_offset, out_idx, out_val, overflow, workspace, workspace_bytes,
-                      DotExcl{true, excl_rows, excl_indptr, excl_cols, out_len}, stream);
+                      Excl{true, excl_rows, excl_indptr, excl_cols, out_len}, stream);
 }

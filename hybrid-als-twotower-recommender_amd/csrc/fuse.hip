@@ -297,7 +297,7 @@ __device__ __forceinline__ void fuse_segment_one(
       overflow = true;
       break;
     }
-    const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    const int below = lanes_below(m);
     const int slot = c ? nc + below : 64 + lane;  // branch-free append
     ck[slot] = key[e];
     ce[slot] = e * 64 + lane;
@@ -417,7 +417,7 @@ __global__ __launch_bounds__(256) void fuse_filter_kernel(
     const bool c = e * 64 + lane < nvalid && key >= tk;
     const uint64_t m = __ballot(c);
     if (m == 0) continue;  // wave-uniform
-    const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    const int below = lanes_below(m);
     const int slot = nc + below;
     if (c && slot < kFuseSlots) {
       ck_sh[wv][slot] = key;

@@ -13,6 +13,7 @@
 //   3. mode 1: hl_pass_kernel<1> writes every fused value and its column (-1
 //      where excluded) and topk_rows ranks the whole rows.
 // Keys are hp_order_key's: 0 = excluded / empty, 1 = NaN, numbers above.
+#include "exclusion.h"
 #include "hybrid_common.h"
 
 namespace hrec {
@@ -38,19 +39,6 @@ __device__ __forceinline__ double hl_als(float a, const double* __restrict__ fb,
 
 // hp_order_key of a live (non-excluded) column
 __device__ __forceinline__ uint64_t hl_key(double fused) { return hp_order_key(fused, 0); }
-
-// The row's exclusion segment [lo, hi) of excl_cols (empty without a CSR or
-// for a negative row id).
-__device__ __forceinline__ void hl_excl_range(const int64_t* __restrict__ excl_rows,
-                                              const int64_t* __restrict__ excl_indptr, int64_t r, int64_t& lo,
-                                              int64_t& hi) {
-  lo = hi = 0;
-  if (!excl_rows) return;
-  const int64_t q = excl_rows[r];
-  if (q < 0) return;
-  lo = excl_indptr[q];
-  hi = excl_indptr[q + 1];
-}
 
 // One 1024-thread block per row: ALS min / max in f64 after the substitution,
 // two-tower min / max in f32 (NaN ignored; hrec_fuse_topk's fmin / fmax from
@@ -90,14 +78,10 @@ __global__ __launch_bounds__(1024) void hl_extremes_kernel(
     j0 = n4 << 2;
   }
   for (int64_t j = j0 + threadIdx.x; j < n; j += 1024) take(ar[j], tr[j], j);
-  // distinct in-range excluded columns (a column counts where it differs from its left neighbour)
-  int64_t lo, hi;
-  hl_excl_range(excl_rows, excl_indptr, r, lo, hi);
+  // distinct in-range excluded columns
+  const ExclSeg x = excl_segment(excl_rows, excl_indptr, r);
   int dist = 0;
-  for (int64_t p = lo + threadIdx.x; p < hi; p += 1024) {
-    const int64_t c = excl_cols[p];
-    dist += (c >= 0 && c < n && (p == lo || (int64_t)excl_cols[p - 1] != c)) ? 1 : 0;
-  }
+  for (int64_t p = x.lo + threadIdx.x; p < x.hi; p += 1024) dist += excl_counts(excl_cols, x.lo, p, n) ? 1 : 0;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     amin = fmin(amin, __shfl_xor(amin, off, kWave));
@@ -152,9 +136,8 @@ __global__ __launch_bounds__(kHlBoundBlock) void hl_bound_kernel(
   for (int q = tid; q < kHlSample / 32; q += kHlBoundBlock) bm[q] = 0;
   if (tid < 64) cn[tid] = 0;
   __syncthreads();
-  int64_t lo, hi;
-  hl_excl_range(excl_rows, excl_indptr, r, lo, hi);
-  for (int64_t p = lo + tid; p < hi; p += kHlBoundBlock) {
+  const ExclSeg x = excl_segment(excl_rows, excl_indptr, r);
+  for (int64_t p = x.lo + tid; p < x.hi; p += kHlBoundBlock) {
     const int64_t c = excl_cols[p];
     if (c >= kHlSample) break;  // ascending: nothing of the sample follows
     if (c >= 0) atomicOr(&bm[c >> 5], 1u << (c & 31));
@@ -208,25 +191,13 @@ __global__ __launch_bounds__(256) void hl_pass_kernel(
   uint32_t* bm = bm_sh[wv];
   if (lane < kHlSeg / 32) bm[lane] = 0;
   hl_wave_sync();
-  int64_t lo, hi;
-  hl_excl_range(excl_rows, excl_indptr, r, lo, hi);
-  if (lo < hi) {
-    int64_t a = lo, z = hi;  // the first position with a column >= seg0 (negative columns fall before it)
-    while (a < z) {
-      const int64_t mid = a + ((z - a) >> 1);
-      if ((int64_t)excl_cols[mid] < seg0) a = mid + 1;
-      else z = mid;
-    }
-    for (int64_t p0 = a; p0 < hi; p0 += 64) {  // wave-uniform trip count
-      const int64_t p = p0 + lane;
-      bool in = false;
-      if (p < hi) {
-        const int64_t c = (int64_t)excl_cols[p] - seg0;
-        in = c >= 0 && c < nvalid;  // columns past the segment (or past n) end the walk unused
-        if (in) atomicOr(&bm[c >> 5], 1u << (c & 31));
-      }
-      if (__ballot(!in)) break;
-    }
+  const ExclSeg x = excl_segment(excl_rows, excl_indptr, r);
+  if (x.lo < x.hi) {
+    // from the first column >= seg0; columns past the segment (or past n) end the walk unused
+    excl_wave_walk(excl_cols, x.lo, excl_lower_bound(excl_cols, x.lo, x.hi, seg0), x.hi, seg0 + nvalid, lane,
+                   [&](int64_t c) {  // c >= seg0 always, when the columns ascend
+                     if (c >= seg0) atomicOr(&bm[(c - seg0) >> 5], 1u << ((c - seg0) & 31));
+                   });
   }
   hl_wave_sync();
   const HpScale sc = coef[r];
@@ -267,8 +238,7 @@ __global__ __launch_bounds__(256) void hl_pass_kernel(
       int base = 0;
       if (lane == 0) base = atomicAdd(&cnt[r], __popcll(m));
       base = __builtin_amdgcn_readfirstlane(base);
-      const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-      const int64_t slot = (int64_t)base + below;
+      const int64_t slot = (int64_t)base + lanes_below(m);
       if (c && slot < L) {
         out_v[r * L + slot] = fused;
         out_i[r * L + slot] = j;

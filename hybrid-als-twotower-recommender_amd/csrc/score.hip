@@ -1,6 +1,7 @@
 // K2: ALS scoring (Spark ALSModel.transform, JVM-exact f32 chain) and its
 // fused top-k; K2p: the pruned ALS top-k. The generic stable top-k is
 // csrc/topk.hip, the hybrid fusion (K9) csrc/fuse.hip.
+#include "exclusion.h"
 #include "hybrid_common.h"
 
 namespace hrec {
@@ -205,8 +206,7 @@ __global__ __launch_bounds__(256) void als_score_fast_kernel(
         }
         base = __shfl(base, leader, kWave);
         if (pass) {
-          const int pos = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                                                __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+          const int pos = base + lanes_below(m);
           if (pos < cap) {
             cand_v[(int64_t)(b0 + b) * cap + pos] = sv[e];
             cand_i[(int64_t)(b0 + b) * cap + pos] = sj[e];
@@ -249,90 +249,6 @@ __global__ __launch_bounds__(256) void sample_threshold_kernel(const float* __re
     thr[row] = t;
     if (zero_cnt) zero_cnt[row] = 0;
   }
-}
-
-// ------------------------------------------------- exclusion (seen items)
-// The exclusion set of row i is excl_cols[excl_indptr[r] .. excl_indptr[r + 1])
-// with r = row_ids[i] (r < 0: empty), columns ascending, duplicates allowed.
-// One wave per row, lanes striding the segment: vals[i][c] = fill for every
-// column c in [0, n) of the set (a column outside is skipped, never used as
-// an index), and the walk stops at the first stride that meets a column
-// >= n (ascending: nothing in range follows). kept_out (optional): min(len_cap,
-// n - distinct columns in [0, n)); a column counts where it differs from its
-// left neighbour.
-__global__ __launch_bounds__(256) void mask_rows_kernel(float* __restrict__ vals, int64_t n_rows, int64_t n,
-                                                        int64_t row_stride, const int64_t* __restrict__ row_ids,
-                                                        const int64_t* __restrict__ excl_indptr,
-                                                        const int32_t* __restrict__ excl_cols, float fill,
-                                                        int64_t len_cap, int32_t* __restrict__ kept_out) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= n_rows) return;  // wave-uniform
-  const int64_t r = row_ids[row];
-  const int64_t lo = r >= 0 ? excl_indptr[r] : 0, hi = r >= 0 ? excl_indptr[r + 1] : 0;
-  float* __restrict__ rv = vals + row * row_stride;
-  int64_t distinct = 0;
-  for (int64_t p0 = lo; p0 < hi; p0 += 64) {  // wave-uniform trip count
-    const int64_t p = p0 + lane;
-    bool counted = false, past = false;
-    if (p < hi) {
-      const int64_t c = excl_cols[p];
-      past = c >= n;
-      if (c >= 0 && !past) {
-        rv[c] = fill;  // duplicates store the same value
-        counted = p == lo || (int64_t)excl_cols[p - 1] != c;
-      }
-    }
-    distinct += __popcll(__ballot(counted));
-    if (__ballot(past)) break;
-  }
-  if (lane == 0 && kept_out) {
-    const int64_t kept = n - distinct;
-    kept_out[row] = (int32_t)(kept < len_cap ? kept : len_cap);
-  }
-}
-
-// The filter's candidates without the excluded items: one block per query, a
-// thread per candidate, a binary search of the query's ascending segment; an
-// excluded candidate's score becomes NaN (better() ranks NaN last, so the
-// top-k over the list passes it only after every candidate that stays).
-// out_len[b] = min(kk, candidates that stay), counted by ballots into an LDS
-// integer. A list past the cap (the filter raised *overflow) is read up to
-// the cap.
-__global__ __launch_bounds__(256) void drop_excluded_kernel(const int64_t* __restrict__ user_rows,
-                                                            const int64_t* __restrict__ excl_indptr,
-                                                            const int32_t* __restrict__ excl_cols,
-                                                            float* __restrict__ cand_v,
-                                                            const int64_t* __restrict__ cand_i,
-                                                            const int* __restrict__ cand_n, int cap, int kk,
-                                                            int32_t* __restrict__ out_len) {
-  __shared__ int s_kept;
-  const int b = blockIdx.x;
-  if (threadIdx.x == 0) s_kept = 0;
-  __syncthreads();
-  const int64_t r = user_rows[b];
-  const int64_t lo = r >= 0 ? excl_indptr[r] : 0, hi = r >= 0 ? excl_indptr[r + 1] : 0;
-  const int n = cand_n[b] < cap ? cand_n[b] : cap;
-  const float qnan = __builtin_nanf("");
-  for (int e0 = 0; e0 < n; e0 += blockDim.x) {  // block-uniform trip count: the ballots see whole waves
-    const int e = e0 + threadIdx.x;
-    bool keep = false;
-    if (e < n) {
-      const int64_t j = cand_i[(int64_t)b * cap + e];
-      int64_t a = lo, z = hi;  // the first position with a column >= j
-      while (a < z) {
-        const int64_t mid = a + ((z - a) >> 1);
-        if ((int64_t)excl_cols[mid] < j) a = mid + 1;
-        else z = mid;
-      }
-      keep = !(a < hi && (int64_t)excl_cols[a] == j);
-      if (!keep) cand_v[(int64_t)b * cap + e] = qnan;
-    }
-    const uint64_t m = __ballot(keep);
-    if (m && (threadIdx.x & 63) == 0) atomicAdd(&s_kept, __popcll(m));  // LDS, integer
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) out_len[b] = s_kept < kk ? s_kept : kk;
 }
 
 }  // namespace hrec
@@ -414,27 +330,13 @@ extern "C" size_t hrec_als_score_topk_workspace_bytes(int n_users, int64_t n_ite
   return score_layout(nullptr, n_users > 0 ? n_users : 0, n_items > 0 ? n_items : 0, score_kk(n_items, top_k)).total;
 }
 
-// The exclusion of a call (on: hrec_als_score_topk_excluding).
-struct ScoreExcl {
-  bool on;
-  const int64_t* indptr;
-  const int32_t* cols;
-  int32_t* out_len;
-};
-
-static int mask_rows_run(float* vals, int64_t n_rows, int64_t n, int64_t row_stride, const int64_t* row_ids,
-                         const ScoreExcl& x, float fill, int64_t len_cap, int32_t* kept_out, hipStream_t s) {
-  hipLaunchKernelGGL(mask_rows_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, s, vals, n_rows, n,
-                     row_stride, row_ids, x.indptr, x.cols, fill, len_cap, kept_out);
-  return check_launch("mask_rows_kernel");
-}
-
-// hrec_als_score_topk and hrec_als_score_topk_excluding (x.indptr set): the
-// same launches, the exclusion's two kernels between them.
+// hrec_als_score_topk and hrec_als_score_topk_excluding (x.on; x.rows are the
+// call's user_rows): the same launches, the exclusion's two kernels
+// (csrc/exclusion.hip) between them.
 static int score_topk_run(const char* fn, const float* user_factors, const int64_t* user_rows, int n_users,
                           const float* item_factors_t, int64_t ld_items, int64_t n_items, int k, int kp, int top_k,
                           int64_t* out_idx, float* out_val, int* overflow, void* workspace, size_t workspace_bytes,
-                          const ScoreExcl& x, void* stream) {
+                          const Excl& x, void* stream) {
   const bool excl = x.on;
   HREC_REQUIRE(hrec_factor_ld_ok(kp), "%s: kp must be 16, 32, 64, 96, 128, 192 or 256", fn);
   HREC_REQUIRE(k >= 1 && k <= kp, "%s: need 1 <= k <= kp", fn);
@@ -462,7 +364,7 @@ static int score_topk_run(const char* fn, const float* user_factors, const int64
     int rc = check_launch("als_score_fast_kernel");
     if (rc) return rc;
     if (excl) {  // excluded scores -> NaN: ranked after every score that stays
-      rc = mask_rows_run(w.samp, n_users, n_items, n_items, user_rows, x, __builtin_nanf(""), kk, x.out_len, s);
+      rc = excl_mask_run(w.samp, n_users, n_items, n_items, 1, n_items, x, __builtin_nanf(""), kk, x.out_len, s);
       if (rc) return rc;
     }
     return topk_rows<float>(w.samp, n_users, n_items, n_items, kk, out_idx, out_val, w.tws, (size_t)1 << 62, s);
@@ -478,7 +380,7 @@ static int score_topk_run(const char* fn, const float* user_factors, const int64
   if (excl) {
     // the bound is over the sample's items that stay: excluded ones -> -inf (a
     // query with fewer than kk left gets -inf and keeps every item)
-    rc = mask_rows_run(w.samp, n_users, S, S, user_rows, x, -__builtin_inff(), 0, nullptr, s);
+    rc = excl_mask_run(w.samp, n_users, S, S, 1, S, x, -__builtin_inff(), 0, nullptr, s);
     if (rc) return rc;
   }
   const float* thr = w.sv + (kk - 1);
@@ -504,9 +406,7 @@ static int score_topk_run(const char* fn, const float* user_factors, const int64
   rc = check_launch("als_score_fast_kernel(filter)");
   if (rc) return rc;
   if (excl) {  // the filter also kept excluded items that reach the bound
-    hipLaunchKernelGGL(drop_excluded_kernel, dim3((unsigned)n_users), blk, 0, s, user_rows, x.indptr, x.cols, w.cv,
-                       w.ci, w.cn, kCap, kk, x.out_len);
-    rc = check_launch("drop_excluded_kernel");
+    rc = excl_drop_run(x, n_users, w.cv, w.ci, w.cn, kCap, kk, x.out_len, s);
     if (rc) return rc;
   }
   // 3) exact stable top-k over the candidates (original item index breaks ties)
@@ -518,7 +418,7 @@ extern "C" int hrec_als_score_topk(const float* user_factors, const int64_t* use
                                    int top_k, int64_t* out_idx, float* out_val, int* overflow, void* workspace,
                                    size_t workspace_bytes, void* stream) {
   return score_topk_run("als_score_topk", user_factors, user_rows, n_users, item_factors_t, ld_items, n_items, k, kp,
-                        top_k, out_idx, out_val, overflow, workspace, workspace_bytes, ScoreExcl{}, stream);
+                        top_k, out_idx, out_val, overflow, workspace, workspace_bytes, Excl{}, stream);
 }
 
 // The exclusion lives in the caller's buffers: the workspace is the fused path's.
@@ -533,18 +433,7 @@ extern "C" int hrec_als_score_topk_excluding(const float* user_factors, const in
                                              void* workspace, size_t workspace_bytes, void* stream) {
   return score_topk_run("als_score_topk_excluding", user_factors, user_rows, n_users, item_factors_t, ld_items,
                         n_items, k, kp, top_k, out_idx, out_val, overflow, workspace, workspace_bytes,
-                        ScoreExcl{true, excl_indptr, excl_cols, out_len}, stream);
-}
-
-extern "C" int hrec_mask_rows_f32(float* vals, int64_t n_rows, int64_t n, int64_t row_stride, const int64_t* row_ids,
-                                  const int64_t* excl_indptr, const int32_t* excl_cols, float fill,
-                                  int32_t* kept_out, void* stream) {
-  HREC_REQUIRE(n_rows >= 0 && n >= 0 && row_stride >= n, "mask_rows_f32: bad shape");
-  HREC_REQUIRE(n < ((int64_t)1 << 31) && n_rows < ((int64_t)1 << 31), "mask_rows_f32: n and n_rows must be < 2^31");
-  if (n_rows == 0) return HREC_OK;
-  HREC_REQUIRE((vals || n == 0) && row_ids && excl_indptr && excl_cols && kept_out, "mask_rows_f32: null pointer");
-  return mask_rows_run(vals, n_rows, n, row_stride, row_ids, ScoreExcl{true, excl_indptr, excl_cols, nullptr}, fill,
-                       INT64_MAX, kept_out, as_stream(stream));
+                        Excl{true, user_rows, excl_indptr, excl_cols, out_len}, stream);
 }
 
 // ---------------------------------------------------- K2p: pruned ALS top-k
@@ -784,8 +673,7 @@ __global__ __launch_bounds__(256) void als_rescore_kernel(const float* __restric
     }
     base = __shfl(base, leader, kWave);
     if (pass) {
-      const int pos = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                                            __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+      const int pos = base + lanes_below(m);
       if (pos < cap) {
         cand_v[(int64_t)b * cap + pos] = acc;
         cand_i[(int64_t)b * cap + pos] = j;
@@ -996,7 +884,7 @@ __global__ __launch_bounds__(256) void als_bound_filter_kernel(const uint16_t* _
 // candidates (the bench's diagnostics; > cap raises *overflow).
 // EXCL (hrec_als_score_topk_pruned_excluding): a candidate whose chain reaches
 // tau_b is looked up in the query's ascending exclusion segment (the binary
-// search of drop_excluded_kernel) and, when found, never enters the LDS list;
+// search of excl_drop_kernel) and, when found, never enters the LDS list;
 // the ones that stay are counted by ballots (the loop's trip count is rounded
 // up to whole blocks so the ballots see whole waves) into s_n, an LDS integer,
 // which also reserves their slots: cand_n[b] and the overflow tests are then
@@ -1035,11 +923,7 @@ __global__ __launch_bounds__(256) void als_rescore_topk_kernel(const float* __re
     const float t = tau[b];
     const int kr = (k + 3) & ~3;
     const bool vec = (ldv & 3) == 0 && ((uintptr_t)V & 15) == 0;
-    int64_t xlo = 0, xhi = 0;
-    if constexpr (EXCL) {
-      xlo = excl_indptr[r];
-      xhi = excl_indptr[r + 1];
-    }
+    const ExclSeg xs = excl_segment(EXCL ? excl_indptr : nullptr, r);
     // EXCL: a block-uniform trip count, so the ballots below see whole waves
     const int e_end = EXCL ? (int)((n + blockDim.x - 1) / blockDim.x * blockDim.x) : n;
     for (int e = threadIdx.x; e < e_end; e += blockDim.x) {
@@ -1064,23 +948,14 @@ __global__ __launch_bounds__(256) void als_rescore_topk_kernel(const float* __re
         pass = acc >= t;
       }
       if constexpr (EXCL) {
-        if (pass) {
-          int64_t a = xlo, z = xhi;  // the first position with a column >= j
-          while (a < z) {
-            const int64_t mid = a + ((z - a) >> 1);
-            if ((int64_t)excl_cols[mid] < j) a = mid + 1;
-            else z = mid;
-          }
-          pass = !(a < xhi && (int64_t)excl_cols[a] == j);
-        }
+        pass = pass && !excl_contains(excl_cols, xs.lo, xs.hi, j);
         const uint64_t keep = __ballot(pass);
         if (keep) {
           int base = 0;
           const int leader = __builtin_ctzll(keep);
           if (lane == leader) base = atomicAdd(&s_n, __popcll(keep));  // LDS, integer
           base = __shfl(base, leader, kWave);
-          const int p = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(keep >> 32),
-                                                              __builtin_amdgcn_mbcnt_lo((uint32_t)keep, 0u));
+          const int p = base + lanes_below(keep);
           if (pass && p < kL) {
             s_v[p] = acc;
             s_j[p] = (int)j;
@@ -1392,7 +1267,7 @@ extern "C" size_t hrec_als_score_topk_pruned_excluding_workspace_bytes(int n_use
 //   kk such sample items gets t_b = -inf, which pr_bounds turns into the
 //   overflow flag: the caller falls back. The filter also keeps excluded items
 //   that reach the bound; they leave after the exact chain (kk > 8:
-//   drop_excluded_kernel, NaN scores ranked last; kk <= 8: inside the fused
+//   excl_drop_kernel, NaN scores ranked last; kk <= 8: inside the fused
 //   rescore-and-rank kernel). als_rescore_kernel's "fewer than kk candidates"
 //   test counts before the drop and stays right: with a finite bound at least
 //   kk non-excluded items reach tau_b. Nothing is resolved on the device here:
@@ -1401,7 +1276,7 @@ static int score_topk_pruned_run(const char* fn, const float* user_factors, cons
                                  const float* item_factors_t, int64_t ld_items, const float* item_factors,
                                  int64_t ld_v, const void* items_bf16, int64_t n_items, int k, int kp, int top_k,
                                  int64_t* out_idx, float* out_val, int* overflow, void* workspace,
-                                 size_t workspace_bytes, const ScoreExcl& x, void* stream) {
+                                 size_t workspace_bytes, const Excl& x, void* stream) {
   const bool excl = x.on;
   HREC_REQUIRE(hrec_factor_ld_ok(kp), "%s: kp must be 16, 32, 64, 96, 128, 192 or 256", fn);
   HREC_REQUIRE(k >= 1 && k <= kp, "%s: need 1 <= k <= kp", fn);
@@ -1468,7 +1343,7 @@ static int score_topk_pruned_run(const char* fn, const float* user_factors, cons
     rc = dot_scores_run(w.uop, n_users, items_bf16, S, dk, 1, w.samp, S, s, kPruneSampleUB);
     if (rc) return rc;
     if (excl) {  // the bound is over the sample's items that stay: excluded ones -> -inf
-      rc = mask_rows_run(w.samp, n_users, S, S, user_rows, x, -__builtin_inff(), 0, nullptr, s);
+      rc = excl_mask_run(w.samp, n_users, S, S, 1, S, x, -__builtin_inff(), 0, nullptr, s);
       if (rc) return rc;
     }
     const float* thr = w.sv + (kk - 1);
@@ -1522,9 +1397,7 @@ static int score_topk_pruned_run(const char* fn, const float* user_factors, cons
   rc = check_launch("als_rescore_kernel");
   if (rc) return rc;
   if (excl) {  // the filter also kept excluded items that reach the bound
-    hipLaunchKernelGGL(drop_excluded_kernel, dim3((unsigned)n_users), dim3(256), 0, s, user_rows, x.indptr, x.cols,
-                       w.cv, w.ci, w.cn, kCap, kk, x.out_len);
-    rc = check_launch("drop_excluded_kernel");
+    rc = excl_drop_run(x, n_users, w.cv, w.ci, w.cn, kCap, kk, x.out_len, s);
     if (rc) return rc;
   }
   // 4) the same exact stable top-k over the candidates
@@ -1538,7 +1411,7 @@ extern "C" int hrec_als_score_topk_pruned(const float* user_factors, const int64
                                           void* workspace, size_t workspace_bytes, void* stream) {
   return score_topk_pruned_run("als_score_topk_pruned", user_factors, user_rows, n_users, item_factors_t, ld_items,
                                item_factors, ld_v, items_bf16, n_items, k, kp, top_k, out_idx, out_val, overflow,
-                               workspace, workspace_bytes, ScoreExcl{}, stream);
+                               workspace, workspace_bytes, Excl{}, stream);
 }
 
 extern "C" int hrec_als_score_topk_pruned_excluding(const float* user_factors, const int64_t* user_rows, int n_users,
@@ -1550,6 +1423,6 @@ extern "C" int hrec_als_score_topk_pruned_excluding(const float* user_factors, c
                                                     void* workspace, size_t workspace_bytes, void* stream) {
   return score_topk_pruned_run("als_score_topk_pruned_excluding", user_factors, user_rows, n_users, item_factors_t,
                                ld_items, item_factors, ld_v, items_bf16, n_items, k, kp, top_k, out_idx, out_val,
-                               overflow, workspace, workspace_bytes, ScoreExcl{true, excl_indptr, excl_cols, out_len},
-                               stream);
+                               overflow, workspace, workspace_bytes,
+                               Excl{true, user_rows, excl_indptr, excl_cols, out_len}, stream);
 }

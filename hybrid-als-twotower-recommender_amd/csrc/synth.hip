@@ -47,8 +47,7 @@ __global__ __launch_bounds__(256) void synth_fill_kernel(uint64_t seed, uint64_t
     }
     const uint64_t mask = __ballot(hit);
     if (hit) {
-      const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                                       __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+      const int below = lanes_below(mask);
       indices[pos + below] = (int32_t)c;
       values[pos + below] = (float)(pair_hash(seed2, u, i) % (uint64_t)n_levels);
     }

@@ -59,6 +59,7 @@ import numpy as np
 import torch
 
 from . import _hrec, ranked_lists
+from .ranked_lists import int_ids as _int_ids
 from .als_engine import DeviceALS, padded_k, process_group
 from .als_ingest import check_same_frame, frame_fingerprint, sharded_ingest
 from .data_preprocessing import get_item_features
@@ -360,20 +361,6 @@ class _PyInts:
 
     def __iter__(self):
         return iter(self.vals.tolist())
-
-
-def _int_ids(col, name):
-    a = np.asarray(col)
-    if a.dtype.kind == "f":
-        if not np.all(np.isfinite(a)) or not np.all(a == np.floor(a)):
-            raise ValueError(f"{name} must hold integer ids (Spark casts them to Int)")
-        a = a.astype(np.int64)
-    if a.dtype.kind not in "iu":
-        raise ValueError(f"{name} must hold integer ids, got dtype {a.dtype}")
-    a = a.astype(np.int64)
-    if a.size and (a.min() < -(2 ** 31) or a.max() >= 2 ** 31):
-        raise ValueError(f"{name} ids must fit a 32-bit Int (Spark ALS)")
-    return a
 
 
 def build_csr(rows, cols, vals, n_rows, n_cols, alias=False, rows_in_order=None, indptr=None):

@@ -27,7 +27,7 @@ import torch
 from sklearn.preprocessing import MinMaxScaler
 
 from . import _hrec, ranked_lists
-from .als_model import ALSModel, _int_ids
+from .als_model import ALSModel
 from .evaluation import compute_f1_score
 from .two_tower_model import TwoTowerModel
 
@@ -339,9 +339,7 @@ class HybridRecommendationSystem:
         n, N = int(users.size), len(cand)
         kk = min(num, N)
         if n == 0 or kk == 0:
-            return (torch.zeros((n, kk), dtype=torch.int64, device=dev),
-                    torch.zeros((n, kk), dtype=torch.float64, device=dev),
-                    None if exclude is None else torch.zeros(n, dtype=torch.int32, device=dev))
+            return ranked_lists.empty_lists(n, kk, torch.float64, dev, exclude is not None)
         excl = tt._exclusion(users, cand, exclude) if exclude is not None else None
         keys = cand.item_ids
         fallback = self._als_fallback(users, keys)
@@ -423,22 +421,11 @@ class HybridRecommendationSystem:
         lists go from hrec_hybrid_lists into hrec_ranking_metrics without
         leaving the device."""
         self._require_models()
-        k = ranked_lists.check_num(k, _hrec.RANK_MAX, "k")
         tt = self.twotower_model
         cand = tt.candidates(item_features)
-        users, items = _int_ids(data["userId"], "userId"), _int_ids(data["itemId"], "itemId")
-        if min_rating is not None:
-            keep = np.asarray(data[label_col or "average_review_rating"], np.float64) >= float(min_rating)
-            users, items = users[keep], items[keep]
-        uniq, indptr, labels = ranked_lists.label_csr(users, items, tt.model.device, self.RANKING_HOST_ROWS)
-        n = int(uniq.numel())
-        res = {name: float("nan") for name in self.RANKING_METRIC_NAMES}
-        res["count"] = n
-        if n == 0:
-            return res
-        pred, _, pred_len = self._recommend_device(tt._query_users(uniq.cpu().numpy()), cand, k, exclude)
-        res.update(ranked_lists.ranking_means(pred, pred_len, indptr, labels, k, n, self.RANKING_METRIC_NAMES))
-        return res
+        return ranked_lists.ranking_metrics(
+            data, k, label_col, min_rating, tt.model.device, self.RANKING_HOST_ROWS, self.RANKING_METRIC_NAMES,
+            lambda users, k: self._recommend_device(tt._query_users(users), cand, k, exclude)[::2])
 
     def evaluate_ranking(self, data, item_features, metric_name="meanAveragePrecision", k=10, label_col=None,
                          min_rating=None, exclude=None):

@@ -1,7 +1,7 @@
-"""What the ALS and the two-tower model share around their ranked lists:
-the exclusion CSR of seen pairs, the label CSR and the tail of the ranking
-metrics, list finishing (padding, the DataFrame of tuples) and the argument
-checks. Plain functions over numpy arrays and device tensors; the models keep
+"""What the ALS, the two-tower and the hybrid model share around their ranked
+lists: the exclusion CSR of seen pairs, the label CSR, the ranking metrics of
+a frame (ranking_metrics: the two-tower and hybrid body) and their tail, list
+finishing (padding, the DataFrame of tuples) and the argument checks. Plain functions over numpy arrays and device tensors; the models keep
 their own operands, thresholds (passed in, read at call time) and scoring
 routes. The materialised top-k of the last resort is _hrec.topk_materialised.
 """
@@ -17,6 +17,20 @@ def check_num(num, limit, name="num"):
     if not 1 <= num <= limit:
         raise ValueError(f"{name} must be in [1, {limit}] (got {num})")
     return num
+
+
+def int_ids(col, name):
+    a = np.asarray(col)
+    if a.dtype.kind == "f":
+        if not np.all(np.isfinite(a)) or not np.all(a == np.floor(a)):
+            raise ValueError(f"{name} must hold integer ids (Spark casts them to Int)")
+        a = a.astype(np.int64)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"{name} must hold integer ids, got dtype {a.dtype}")
+    a = a.astype(np.int64)
+    if a.size and (a.min() < -(2 ** 31) or a.max() >= 2 ** 31):
+        raise ValueError(f"{name} ids must fit a 32-bit Int (Spark ALS)")
+    return a
 
 
 def check_metric_name(metric_name, names):
@@ -136,7 +150,31 @@ def ranking_means(pred, pred_len, indptr, labels, k, n, names):
             for name, slot in zip(names, ("sum_ap", "sum_ap_k", "sum_precision", "sum_recall", "sum_ndcg"))}
 
 
+def ranking_metrics(data, k, label_col, min_rating, dev, host_rows, names, lists):
+    """{name: mean, "count": n} over the frame `data` (userId, itemId; with
+    min_rating, the rows whose label_col is >= it): the label CSR, the device
+    lists(users, k) -> (pred, pred_len) of its n distinct users (ascending),
+    ranking_means. n == 0: NaN metrics, `lists` is not called."""
+    k = check_num(k, _hrec.RANK_MAX, "k")
+    users, items = int_ids(data["userId"], "userId"), int_ids(data["itemId"], "itemId")
+    if min_rating is not None:
+        keep = np.asarray(data[label_col or "average_review_rating"], np.float64) >= float(min_rating)
+        users, items = users[keep], items[keep]
+    uniq, indptr, labels = label_csr(users, items, dev, host_rows)
+    n = int(uniq.numel())
+    res = dict({name: float("nan") for name in names}, count=n)
+    if n:
+        res.update(ranking_means(*lists(uniq.cpu().numpy(), k), indptr, labels, k, n, names))
+    return res
+
+
 # ----------------------------------------------------------- list finishing
+def empty_lists(n, kk, dtype, dev, with_lens):
+    """The (ids, scores, lens) of n lists of kk entries when either is 0."""
+    return (torch.zeros((n, kk), dtype=torch.int64, device=dev), torch.zeros((n, kk), dtype=dtype, device=dev),
+            torch.zeros(n, dtype=torch.int32, device=dev) if with_lens else None)
+
+
 def pad_lists(id_table, idx, val, lens, n_cols):
     """(raw ids, scores) of the lists idx / val with id 0 and score NaN past
     each list's length (what the library left there is unspecified)."""

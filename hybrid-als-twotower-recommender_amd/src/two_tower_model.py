@@ -423,9 +423,7 @@ class TwoTowerModel:
         n, N = int(users.size), int(cand.vectors.shape[0])
         kk = min(num, N)
         if n == 0 or kk == 0:
-            return (torch.zeros((n, kk), dtype=torch.int64, device=dev),
-                    torch.zeros((n, kk), dtype=torch.float32, device=dev),
-                    None if exclude is None else torch.zeros(n, dtype=torch.int32, device=dev))
+            return ranked_lists.empty_lists(n, kk, torch.float32, dev, exclude is not None)
         excl = self._exclusion(users, cand, exclude) if exclude is not None else None
         U = self.model.user_vectors(torch.as_tensor(users.astype(np.int32), device=dev))
         V = cand.vectors
@@ -490,22 +488,10 @@ class TwoTowerModel:
         recommend_for_users; each list is evaluated at its own length. A user
         id outside the table raises IndexError. The lists go from the top-k
         into hrec_ranking_metrics without leaving the device."""
-        k = ranked_lists.check_num(k, _hrec.RANK_MAX, "k")
         cand = self.candidates(item_features)
-        users, items = _int_ids(data["userId"], "userId"), _int_ids(data["itemId"], "itemId")
-        if min_rating is not None:
-            keep = np.asarray(data[label_col or "average_review_rating"], np.float64) >= float(min_rating)
-            users, items = users[keep], items[keep]
-        _ids(users, self.model.sizes["user_emb"], "user_in")  # range check (IndexError)
-        uniq, indptr, labels = ranked_lists.label_csr(users, items, self.model.device, self.RANKING_HOST_ROWS)
-        n = int(uniq.numel())
-        res = {name: float("nan") for name in self.RANKING_METRIC_NAMES}
-        res["count"] = n
-        if n == 0:
-            return res
-        pred, _, pred_len = self._recommend_device(uniq.cpu().numpy(), cand, k, exclude)
-        res.update(ranked_lists.ranking_means(pred, pred_len, indptr, labels, k, n, self.RANKING_METRIC_NAMES))
-        return res
+        return ranked_lists.ranking_metrics(
+            data, k, label_col, min_rating, self.model.device, self.RANKING_HOST_ROWS, self.RANKING_METRIC_NAMES,
+            lambda users, k: self._recommend_device(self._query_users(users), cand, k, exclude)[::2])  # IndexError
 
     def evaluate_ranking(self, data, item_features, metric_name="meanAveragePrecision", k=10, label_col=None,
                          min_rating=None, exclude=None):

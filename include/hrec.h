@@ -401,7 +401,8 @@ int hrec_als_score_topk_excluding(const float* user_factors, const int64_t* user
  * vals[i * row_stride + c] = fill for every column c in [0, n) of the
  * exclusion set of factor row row_ids[i] (a negative row id: the empty set);
  * kept_out[i] (int32) = n - distinct in-range excluded columns. n and n_rows
- * below 2^31, row_stride >= n. Additive to ABI 7. */
+ * below 2^31, row_stride >= n. Additive to ABI 7. Every *_excluding entry
+ * reads its CSR by this convention (device side: csrc/exclusion.h). */
 int hrec_mask_rows_f32(float* vals, int64_t n_rows, int64_t n, int64_t row_stride, const int64_t* row_ids,
                        const int64_t* excl_indptr, const int32_t* excl_cols, float fill,
                        int32_t* kept_out, void* stream);
