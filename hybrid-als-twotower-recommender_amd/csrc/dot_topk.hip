@@ -27,6 +27,7 @@
 
 #include <type_traits>
 
+#include "cascade.h"
 #include "hybrid_common.h"
 
 namespace hrec {
@@ -860,43 +861,18 @@ extern "C" int hrec_dot_filter(const void* user_vec, int n_users, const void* it
                         cand_idx, cand_n, as_stream(stream));
 }
 
-// Workspace of hrec_dot_topk, in carve order.
-struct DotWs {
-  float* samp;  // [B][S] sample scores
-  char* tws;    // sample top-k workspace
-  float* sv;    // [B][kk] sample top-k values / indices
-  int64_t* si;
-  float* cv;    // [B][cap] candidates
-  int64_t* ci;
-  int* cn;      // [B] counters
-  char* fws;    // final top-k workspace
-  size_t total;
-};
-static DotWs dot_layout(void* base, int B, int64_t n_items, int kk) {
-  DotWs w{};
-  Carver c(base);
-  const int64_t S = dot_sample(n_items, kk), cap = dot_cap(kk);
-  w.samp = (float*)c.take((size_t)B * S * 4);
-  w.tws = c.take(topk_ws_bytes(B, S, kk, 4));
-  w.sv = (float*)c.take((size_t)B * kk * 4);
-  w.si = (int64_t*)c.take((size_t)B * kk * 8);
-  w.cv = (float*)c.take((size_t)B * cap * 4);
-  w.ci = (int64_t*)c.take((size_t)B * cap * 8);
-  w.cn = (int*)c.take((size_t)B * 4);
-  w.fws = c.take(topk_ws_bytes(B, cap, kk, 4));
-  w.total = c.total();
-  return w;
-}
-
+// Workspace of hrec_dot_topk: the cascade's buffers alone (counters of exactly B ints, no tail).
 extern "C" size_t hrec_dot_topk_workspace_bytes(int n_users, int64_t n_items, int top_k) {
   const int kk = (int)(top_k < n_items ? top_k : n_items);
   if (kk <= 0) return 256;
-  return dot_layout(nullptr, n_users > 0 ? n_users : 0, n_items, kk).total;
+  Carver c(nullptr);
+  cascade_carve(c, n_users > 0 ? n_users : 0, dot_sample(n_items, kk), dot_cap(kk), kk, 0);
+  return c.total();
 }
 
 // hrec_dot_topk and hrec_dot_topk_excluding (x.on): the same launches, the
-// exclusion's kernels (csrc/exclusion.hip; columns = local item indices)
-// between them.
+// exclusion's kernels (csrc/exclusion.hip; columns = local item indices) inside
+// the cascade's steps (csrc/cascade.hip: why the bound stays sound under one).
 static int dot_topk_run(const char* fn, const void* user_vec, int n_users, const void* item_vec, int64_t n_items,
                         int dk, int dtype, int top_k, const float* thr_in, int64_t idx_offset, int64_t* out_idx,
                         float* out_val, int* overflow, void* workspace, size_t workspace_bytes, const Excl& x,
@@ -913,17 +889,14 @@ static int dot_topk_run(const char* fn, const void* user_vec, int n_users, const
   hipStream_t s = as_stream(stream);
   const int kk = (int)(top_k < n_items ? top_k : n_items);
   const int64_t S = dot_sample(n_items, kk), cap = dot_cap(kk);
-  const DotWs w = dot_layout(workspace, n_users, n_items, kk);
+  Carver carver(workspace);
+  const CascadeWs w = cascade_carve(carver, n_users, S, cap, kk, 0);  // as the size query carves it
   if (hipMemsetAsync(overflow, 0, sizeof(int), s) != hipSuccess) return check_launch("dot_topk: memset");
   if (S == n_items && thr_in == nullptr) {  // small: every score, exact top-k
     rc = dot_launch<false>(user_vec, n_users, item_vec, n_items, n_items, 1, dk, dtype, w.samp, n_items, nullptr, 0, 0, nullptr,
                            nullptr, nullptr, 0, s);
     if (rc) return rc;
-    if (x.on) {  // excluded scores -> NaN: ranked after every score that stays
-      rc = excl_mask_run(w.samp, n_users, n_items, n_items, 1, n_items, x, __builtin_nanf(""), kk, x.out_len, s);
-      if (rc) return rc;
-    }
-    rc = topk_rows<float>(w.samp, n_users, n_items, n_items, kk, out_idx, out_val, w.tws, (size_t)1 << 62, s);
+    rc = cascade_rank_all(w, n_users, n_items, kk, x, out_idx, out_val, s);
   } else {
     const float* thr = thr_in;
     int thr_stride = 1;
@@ -932,36 +905,22 @@ static int dot_topk_run(const char* fn, const void* user_vec, int n_users, const
       rc = dot_launch<false>(user_vec, n_users, item_vec, n_items, S, step, dk, dtype, w.samp, S, nullptr, 0, 0, nullptr,
                              nullptr, nullptr, 0, s);
       if (rc) return rc;
-      if (x.on) {
-        // the bound is over the sample's items that stay: the sample columns of
-        // excluded items -> -inf (a query with fewer than kk left gets -inf and
-        // admits every score); also writes out_len
-        rc = excl_mask_run(w.samp, n_users, S, S, step, n_items, x, -INFINITY, kk, x.out_len, s);
-        if (rc) return rc;
-      }
-      rc = topk_rows<float>(w.samp, n_users, S, S, kk, w.si, w.sv, w.tws, (size_t)1 << 62, s);
+      // every step-th item, lengths from the mask, always the exact kk-th; zeroes the survivor counters
+      rc = cascade_bound(w, n_users, S, step, n_items, kk, x, x.out_len, false, w.cn, &thr, &thr_stride, s);
       if (rc) return rc;
-      thr = w.sv + (kk - 1);
-      thr_stride = kk;
-    } else if (x.on) {  // a caller's bound: the lengths alone
-      rc = excl_mask_run(nullptr, n_users, 0, 0, 1, n_items, x, 0.f, kk, x.out_len, s);
+    } else {  // a caller's bound: under an exclusion the lengths alone; the counters
+      rc = x.on ? excl_mask_run(nullptr, n_users, 0, 0, 1, n_items, x, 0.f, kk, x.out_len, s) : HREC_OK;
       if (rc) return rc;
+      if (hipMemsetAsync(w.cn, 0, (size_t)n_users * 4, s) != hipSuccess) return check_launch("dot_topk: memset");
     }
     // 2) fused score + survivor filter over every item
-    if (hipMemsetAsync(w.cn, 0, (size_t)n_users * 4, s) != hipSuccess)
-      return check_launch("dot_topk: memset");
     rc = dot_launch<true>(user_vec, n_users, item_vec, n_items, n_items, 1, dk, dtype, nullptr, 0, thr, thr_stride, (int)cap,
                           w.cv, w.ci, w.cn, 0, s);
     if (rc) return rc;
-    hipLaunchKernelGGL(dot_overflow_kernel, dim3(64), dim3(256), 0, s, w.cn, n_users, (int)cap, overflow);
-    rc = check_launch("dot_overflow_kernel");
+    rc = count_overflow(w.cn, n_users, (int)cap, overflow, s);
     if (rc) return rc;
-    if (x.on) {  // the filter also kept excluded items that reach the bound
-      rc = excl_drop_run(x, n_users, w.cv, w.ci, w.cn, (int)cap, kk, nullptr, s);
-      if (rc) return rc;
-    }
-    // 3) exact stable top-k of the survivors (item index breaks ties)
-    rc = topk_rows<float>(w.cv, n_users, cap, cap, kk, out_idx, out_val, w.fws, (size_t)1 << 62, s, w.ci, w.cn);
+    // 3) the excluded survivors leave (out_len is the mask's); exact stable top-k of the rest
+    rc = cascade_tail(w, n_users, cap, kk, x, nullptr, out_idx, out_val, s);
   }
   if (rc) return rc;
   return offset_ids(out_idx, (int64_t)n_users * kk, idx_offset, s);

@@ -12,7 +12,10 @@ excluding at kk <= 8 and above; hrec_dot_topk_excluding in f32 and bf16;
 hrec_hybrid_lists in modes 0 and 1; the ALS, two-tower and hybrid models'
 recommend_for_* frames and ranking_metrics with exclude=. Exclusion patterns:
 none, empty, 50 random per row, the row's own top 200, everything but 3, and a
-raw CSR with duplicates, negative columns and columns out of range. List
+raw CSR with duplicates, negative columns and columns out of range. Also the
+plain entries over the same shapes: hrec_als_score_topk and
+hrec_als_score_topk_pruned at kk 5, 10 and 65; hrec_dot_topk in f32 and bf16,
+without and with a caller's bound (thr_in). List
 entries past a row's length are unspecified and are zeroed before hashing; a
 raw library call that raised its overflow flag contributes the flag alone (its
 lists were cut in an order atomics decide), the wrappers that resolve the flag
@@ -86,6 +89,22 @@ def frame_digest(df):
             "ids": digest(np.array([x for r in ids for x in r], np.int64)), "scores": digest(flat)}
 
 
+def dot_raw(h, Ud, Vd, num, thr):
+    """One hrec_dot_topk call (thr: a caller's bound per query, or None): (flag, idx, val)."""
+    dk, bf = h._dot_args(Ud, Vd)
+    B, N, dev = Ud.shape[0], Vd.shape[0], Ud.device
+    oi = torch.empty((B, num), dtype=torch.int64, device=dev)
+    ov = torch.empty((B, num), dtype=torch.float32, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    need = int(h.lib().hrec_dot_topk_workspace_bytes(B, N, num))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    h._check("hrec_dot_topk", h.lib().hrec_dot_topk(
+        h._vp(Ud.data_ptr()), B, h._vp(Vd.data_ptr()), N, dk, bf, num, None if thr is None else h._vp(thr.data_ptr()),
+        0, h._vp(oi.data_ptr()), h._vp(ov.data_ptr()), h._vp(flag.data_ptr()), h._vp(ws.data_ptr()), need,
+        h._stream()))
+    return flag, oi, ov
+
+
 def dump(path):
     from sklearn.preprocessing import MinMaxScaler
 
@@ -117,7 +136,17 @@ def dump(path):
         for pat in PATTERNS:
             per_row = columns(pat, order, n_items, rng)
             excl = csr(per_row, dev)
-            if pat == "none":
+            if pat == "none":  # the plain entries, same shapes and kk
+                for num in (5, 10, 65):
+                    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+                    res = h.als_score_topk(Q, rows, Ft, n_items, k, num, check_overflow=False, overflow_out=flag)
+                    put(f"plain_als/{n_items}x{k}/num{num}/exact", flag=flag,
+                        **({} if int(flag.item()) else dict(zip("iv", res))))
+                    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+                    res = h.als_score_topk_pruned(Q, rows, Ft, F, bf, n_items, k, num, check_overflow=False,
+                                                  overflow_out=flag)
+                    put(f"plain_als/{n_items}x{k}/num{num}/pruned", flag=flag,
+                        **({} if int(flag.item()) else dict(zip("iv", res))))
                 continue
             if n_items == 2049:
                 vals = h.als_score(Q, rows, Ft, None, n_items, k)
@@ -176,7 +205,13 @@ def dump(path):
         T = h.tt_score(Uv, cand.vectors)
         for dtype in (torch.float32, torch.bfloat16):
             Ud, Vd = h.dot_operand(Uv, dtype), h.dot_operand(cand.vectors, dtype)
-            order = h.dot_topk(Ud, Vd, 200)[0].cpu().numpy()
+            top200 = h.dot_topk(Ud, Vd, 200)
+            order = top200[0].cpu().numpy()
+            for num in (5, 10, 65):  # the plain entry, without and with a caller's bound (the 200th best score)
+                for tag, thr in (("own", None), ("thr_in", top200[1][:, 199].contiguous())):
+                    flag, i, v = dot_raw(h, Ud, Vd, num, thr)
+                    put(f"plain_dot/{n_items}/{str(dtype)[6:]}/num{num}/{tag}", flag=flag,
+                        **({} if int(flag.item()) else {"i": i, "v": v}))
             for pat in PATTERNS:
                 excl = csr(columns(pat, order, n_items, rng), dev)
                 for num in (5, 10, 65):
