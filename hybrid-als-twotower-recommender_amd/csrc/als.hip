@@ -41,14 +41,14 @@ __device__ __forceinline__ void als_row(int64_t row, int lane, const int64_t* __
   double* bsh = scratch + 128 + 2 * KP;
   if constexpr (IMP) {
     int n_pos = 0;
-    gram_row<NT, CH, MODE, NoHook, S64, true>(beg, end, lane, indices, values, src, n_src, k, reg, acc, bsh, lds,
-                                              NoHook(), alpha, yty, &n_pos);
+    gram_row<NT, CH, MODE, S64, true>(beg, end, lane, indices, values, src, n_src, k, reg, acc, bsh, lds, alpha, yty,
+                                      &n_pos);
     if (n_pos == 0) {  // no rating > 0: b = 0, the factor is exactly zero (wave-uniform)
       if (lane < KP) out[lane] = 0.f;
       return;
     }
   } else {
-    gram_row<NT, CH, MODE, NoHook, S64>(beg, end, lane, indices, values, src, n_src, k, reg, acc, bsh, lds);
+    gram_row<NT, CH, MODE, S64>(beg, end, lane, indices, values, src, n_src, k, reg, acc, bsh, lds);
   }
   factor_row<NT>(lane, acc, lds, scratch, bsh, out);
 }
@@ -64,10 +64,10 @@ __global__ __launch_bounds__(64, HREC_ALS_WAVES) void als_half_sweep_f64_kernel(
 }
 
 // ---- pooled kernel: three waves per SIMD, 12 waves sharing 8 LDS slices ----
-// A wave needs its LDS slice only from the end of its Gramian (the DIAG4
-// staging) to the last read of the back substitution, so the 12 waves of a
-// CU (3 per SIMD, <= 168 VGPRs: factor_row_lds keeps the Gramian in the slice)
-// share 8 slices of RowLds<64>::kSize doubles = 153,600 B. Each SIMD class
+// A wave needs its LDS slice only from the end of its Gramian (the staging of
+// the diagonal tiles) to the last read of the back substitution, so the 12
+// waves of a CU (3 per SIMD, <= 168 VGPRs: factor_row_lds keeps the Gramian in
+// the slice) share 8 slices of RowLds<64>::kSize doubles = 153,600 B. Each SIMD class
 // (wave index & 3: waves are placed round-robin over the 4 SIMDs,
 // scripts/micro/hwid_probe.hip; another placement would only cost speed) owns
 // 2 slices, so at most 2 of a SIMD's 3 waves are in their epilogue / solve and
@@ -75,15 +75,6 @@ __global__ __launch_bounds__(64, HREC_ALS_WAVES) void als_half_sweep_f64_kernel(
 // whose class has none free may borrow another class's, HREC_ALS_POOL_ANY64).
 // A wave without a slice sleeps; it holds none, so the holders always finish:
 // no deadlock.
-#ifndef HREC_ALS_POOL_LATE
-#define HREC_ALS_POOL_LATE 1  // 1 = take the slice when the Gramian loop is done; 0 = before the row starts
-#endif
-#ifndef HREC_ALS_POOL_PRIO
-#define HREC_ALS_POOL_PRIO 0  // s_setprio of a wave while it holds a slice
-#endif
-#ifndef HREC_ALS_POOL_LDSG
-#define HREC_ALS_POOL_LDSG 1  // 1 = factor_row_lds (Gramian in the slice); 0 = factor_row (in the accumulator registers)
-#endif
 // 1 = a wave may take any free slice (its class's two first), so all 3 waves
 // of a SIMD may be in their solves; per source type (measured)
 #ifndef HREC_ALS_POOL_ANY32
@@ -116,7 +107,6 @@ __device__ __forceinline__ int slice_acquire(int* busy, int cls, int lane) {
     __builtin_amdgcn_s_sleep(HREC_ALS_POOL_SLEEP);
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  if constexpr (HREC_ALS_POOL_PRIO) __builtin_amdgcn_s_setprio(HREC_ALS_POOL_PRIO);
   return slot;
 }
 
@@ -125,7 +115,6 @@ __device__ __forceinline__ int slice_acquire(int* busy, int cls, int lane) {
 __device__ __forceinline__ void slice_release(int* busy, int slot, int lane) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   if (lane == 0) atomicExch(&busy[slot], 0);
-  if constexpr (HREC_ALS_POOL_PRIO) __builtin_amdgcn_s_setprio(0);
 }
 
 // Persistent: one 12-wave workgroup per CU; every wave claims whole rows, one
@@ -168,20 +157,13 @@ __global__ __launch_bounds__(64 * kPoolWaves, 3) void als_half_sweep_f64_kernel_
       slot = slice_acquire<S64 ? HREC_ALS_POOL_ANY64 != 0 : HREC_ALS_POOL_ANY32 != 0>(busy, cls, lane);
       return pool + slot * RowLds<KP>::kSize;
     };
-    double* lds = nullptr;
-    if constexpr (HREC_ALS_POOL_LATE) {
-      gram_row<NT, HREC_ALS_CH0, 0, NoHook, S64, false, true>(beg, end, gl, indices, values, src, n_src, k, reg, acc,
-                                                         nullptr, nullptr, NoHook(), 0.0, nullptr, nullptr, acquire);
-      lds = pool + slot * RowLds<KP>::kSize;
-    } else {
-      lds = acquire();
-      gram_row<NT, HREC_ALS_CH0, 0, NoHook, S64, false, true>(beg, end, gl, indices, values, src, n_src, k, reg, acc,
-                                                 lds + RowLds<KP>::kUpPad + 128 + 2 * KP, lds);
-    }
+    // the slice is taken inside gram_row, when the Gramian loop is done
+    gram_row<NT, HREC_ALS_CH0, 0, S64, false, true>(beg, end, gl, indices, values, src, n_src, k, reg, acc, nullptr,
+                                                    nullptr, 0.0, nullptr, nullptr, acquire);
+    double* lds = pool + slot * RowLds<KP>::kSize;
     double* scratch = lds + RowLds<KP>::kUpPad;
     asm volatile("" : "+v"(fl));
-    if constexpr (HREC_ALS_POOL_LDSG) factor_row_lds<NT>(fl, acc, lds, scratch, scratch + 128 + 2 * KP, out);
-    else factor_row<NT>(fl, acc, lds, scratch, scratch + 128 + 2 * KP, out);
+    factor_row_lds<NT>(fl, acc, lds, scratch, scratch + 128 + 2 * KP, out);
     slice_release(busy, slot, lane);
   }
 }

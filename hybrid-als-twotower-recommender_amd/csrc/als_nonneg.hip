@@ -160,11 +160,11 @@ __global__ __launch_bounds__(64, HREC_ALS_WAVES) void als_half_sweep_nonneg_kern
   if (solve) {
     if constexpr (IMP) {
       int n_pos = 0;
-      gram_row<NT, CH, 0, NoHook, false, true>(beg, end, lane, indices, values, src, n_src, k, reg, acc, bsh, lds,
-                                               NoHook(), alpha, yty, &n_pos);
+      gram_row<NT, CH, 0, false, true>(beg, end, lane, indices, values, src, n_src, k, reg, acc, bsh, lds, alpha, yty,
+                                       &n_pos);
       solve = n_pos != 0;  // no rating > 0: b = 0, the factor is exactly zero (wave-uniform)
     } else {
-      gram_row<NT, CH, 0, NoHook, false>(beg, end, lane, indices, values, src, n_src, k, reg, acc, bsh, lds);
+      gram_row<NT, CH, 0>(beg, end, lane, indices, values, src, n_src, k, reg, acc, bsh, lds);
     }
   }
   if (solve) iters = nnls_row<NT>(lane, acc, lds, scratch, bsh, k, out);

@@ -23,29 +23,12 @@
 #ifndef HREC_ALS_CH1
 #define HREC_ALS_CH1 4
 #endif
-#ifndef HREC_ALS_INTCVT
-#define HREC_ALS_INTCVT 0  // 1 = Gramian operands f32 -> f64 by 32-bit integer ops (measured slower)
-#endif
-#ifndef HREC_ALS_RLPANEL
-#define HREC_ALS_RLPANEL 0  // 1 = pivot-row entries by v_readlane, 2 = only the next pivot's (both measured slower)
-#endif
-#ifndef HREC_ALS_DIAG4
-// diagonal Gramian tiles as 3 x v_mfma_f64_4x4x4_4b (3/4 of the 16x16x4 work):
-// 3 = rotated operands gathered from memory (default); 1 / 2 = rotated by DPP /
-// ds_bpermute (measured slower); 0 = whole 16x16x4 diagonal tiles
-#define HREC_ALS_DIAG4 3
-#endif
-#ifndef HREC_ALS_PIPE
-#define HREC_ALS_PIPE 1  // 1 = ring-prefetch gather with structured buffer loads; 0 = chunked flat loads
-#endif
+// The kp-64 ring pipeline of gram_row (explicit feedback):
 #ifndef HREC_ALS_PF
-#define HREC_ALS_PF 8  // PIPE: gather prefetch distance in steps of 4 ratings
+#define HREC_ALS_PF 8  // gather prefetch distance in steps of 4 ratings
 #endif
 #ifndef HREC_ALS_PF64
 #define HREC_ALS_PF64 4  // prefetch distance of f64-source gathers (steps)
-#endif
-#ifndef HREC_ALS_PAIR8
-#define HREC_ALS_PAIR8 2  // DIAG4 = 3: two diagonal tiles share one rotation-by-8 product (2: pairs (0,2), (1,3) by half-width loads)
 #endif
 #ifndef HREC_ALS_ROT1DPP
 #define HREC_ALS_ROT1DPP 1  // f32 sources: rotation by 4 by DPP moves of the converted operands (0: rotated load + conversion)
@@ -54,7 +37,7 @@
 #define HREC_ALS_ROT1DPP64 0  // f64 sources: rotation by 4 by DPP moves of the gathered operands (0: rotated loads; 1 measured 41.6 -> 41.9 ms user side, bit-identical)
 #endif
 #ifndef HREC_ALS_PR
-#define HREC_ALS_PR 2  // DIAG4 = 3: prefetch distance of the rotated loads (steps)
+#define HREC_ALS_PR 2  // f64 accumulation: prefetch distance of the rotated loads (steps)
 #endif
 // The pooled kernel (3 waves per SIMD, <= 168 VGPRs) takes its own gather knobs.
 #ifndef HREC_ALS_POOL_PF
@@ -150,8 +133,6 @@ __device__ __forceinline__ Vec<NT> struct_load(i4v rsrc, int vindex, int voffset
 #ifdef HREC_ALS_STAMPS
 // Diagnostic builds only: per-phase cycle sums (s_memtime) over all waves.
 __device__ unsigned long long g_als_stamps[8];
-#endif
-#ifdef HREC_ALS_STAMPS
 #define STAMP(i)                                                                      \
   do {                                                                                \
     __builtin_amdgcn_sched_barrier(0);                                                \
@@ -168,25 +149,6 @@ __device__ unsigned long long g_als_stamps[8];
 #define STAMP_DECL
 #endif
 
-// f32 -> f64 from the bit fields with 32-bit integer ops only: v_cvt_f64_f32
-// runs on the f64 pipe, which the Gramian's f64 MFMAs keep busy (f64 VALU ops
-// do not co-execute with them; integer ops do). Exact for normal numbers and
-// zeros; f32 subnormals (|x| < 2^-126) become zero; inf/NaN are not factor
-// values (Spark's factors are finite).
-__device__ __forceinline__ double f32_to_f64_int(float x) {
-  const uint32_t u = __float_as_uint(x);
-  const uint32_t em = u & 0x7fffffffu;
-  const bool normal = (u & 0x7f800000u) != 0u;
-  const uint32_t hi = (u & 0x80000000u) | (normal ? (em >> 3) + 0x38000000u : 0u);
-  const uint32_t lo = normal ? em << 29 : 0u;
-  return __hiloint2double((int)hi, (int)lo);
-}
-
-__device__ __forceinline__ double gram_cvt(float x) {
-  if constexpr (HREC_ALS_INTCVT) return f32_to_f64_int(x);
-  return (double)x;
-}
-
 // x of lane (l & 48) | ((l + 16 - N) & 15): a rotation inside each 16-lane
 // row (DPP row_ror:N on both halves of the double).
 template <int N>
@@ -194,13 +156,6 @@ __device__ __forceinline__ double row_ror(double x) {
   const long long v = __double_as_longlong(x);
   const int lo = __builtin_amdgcn_mov_dpp((int)v, 0x120 + N, 0xf, 0xf, false);
   const int hi = __builtin_amdgcn_mov_dpp((int)(v >> 32), 0x120 + N, 0xf, 0xf, false);
-  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-}
-
-// c ? x : y on a double as two 32-bit selects (v_cndmask_b32).
-__device__ __forceinline__ double sel64(bool c, double x, double y) {
-  const long long a = __double_as_longlong(x), b = __double_as_longlong(y);
-  const int lo = c ? (int)a : (int)b, hi = c ? (int)(a >> 32) : (int)(b >> 32);
   return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
 }
 
@@ -229,6 +184,9 @@ struct RowLds {
   static constexpr int kSize = kUpPad + 128 + 3 * KP;
 };
 
+// gram_row's `acquire` of a caller that passes its LDS slice itself.
+struct NoAcquire {};
+
 // Gramian + rhs of one destination row on one wave (lane = 0..63):
 // acc = sum_j v_j v_j^T (tile layout, + n*reg on the diagonal), b -> bsh.
 // NT floats per lane (kp = 16*NT), CH steps of 4 nnz per pipeline chunk.
@@ -238,13 +196,6 @@ struct RowLds {
 //         chunk of 16 ratings in f32 (an exact f32 fma chain), and the chunk
 //         partials are flushed into f64 accumulators — f64 summation across
 //         chunks, f32 rounding only inside a chunk.
-struct NoHook {
-  __device__ void operator()() const {}
-};
-
-// `before_lds` runs once the row's Gramian is in registers, before the first
-// LDS write (b, MODE 1 re-layout) — a no-op in the product kernel (the
-// producer/consumer splits that waited there measured slower).
 // IMP: the A-side MFMA operand of a step carries the rating's confidence
 // weight c1 = alpha |r| (the K index of both operands is the step's nnz, so
 // the products are c1 v v^T), the rhs weight is 1 + c1 for r > 0 and 0
@@ -253,20 +204,19 @@ struct NoHook {
 // Implicit rows take the chunked gather loop at every kp (the ring pipeline
 // of kp = 64 is left to the explicit kernels, whose code must not change).
 // `acquire` (pooled kernel only): called once the ring loop is done, before
-// the first LDS write of the row (the DIAG4 staging); returns the wave's LDS
-// slice, which replaces stage / bsh. The default takes both as passed.
-template <int NT, int CH, int MODE, typename Hook = NoHook, bool S64 = false, bool IMP = false,
-          bool POOLED = false, typename Acq = NoHook>
+// the first LDS write of the row (the staging of the diagonal tiles); returns
+// the wave's LDS slice, which replaces stage / bsh. The default, NoAcquire,
+// takes both as passed.
+template <int NT, int CH, int MODE, bool S64 = false, bool IMP = false, bool POOLED = false,
+          typename Acq = NoAcquire>
 __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, const int32_t* __restrict__ indices,
                                          const float* __restrict__ values, const float* __restrict__ src,
                                          int64_t n_src, int k, double reg, d4 (&acc)[NT * (NT + 1) / 2],
-                                         double* __restrict__ bsh, double* __restrict__ stage,
-                                         Hook before_lds = Hook(), double alpha = 0.0,
+                                         double* __restrict__ bsh, double* __restrict__ stage, double alpha = 0.0,
                                          const double* __restrict__ yty = nullptr, int* npos = nullptr,
                                          Acq acquire = Acq()) {
-  constexpr bool kAcq = !std::is_same_v<Acq, NoHook>;
-  static_assert(!kAcq || (HREC_ALS_PIPE && NT == 4 && !IMP && HREC_ALS_ABLATE != 4),
-                "late slice acquisition: the kp-64 ring pipeline only");
+  constexpr bool kAcq = !std::is_same_v<Acq, NoAcquire>;
+  static_assert(!kAcq || (NT == 4 && !IMP), "late slice acquisition: the kp-64 ring pipeline only");
   static_assert(!IMP || (MODE == 0 && !S64), "implicit feedback: f64 accumulation of f32 sources only");
   constexpr int KP = 16 * NT;
   constexpr int NPAIR = NT * (NT + 1) / 2;
@@ -285,6 +235,7 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
     for (int I = 0, p = 0; I < NT; p += NT - I, ++I)
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) acc[p][rr] = (sub + 4 * rr == col) ? 1.0 + reg * (double)n : 0.0;
+    if constexpr (kAcq) bsh = acquire() + RowLds<KP>::kUpPad + 128 + 2 * KP;
     if (lane < KP) bsh[lane] = 1.0;
     wave_lds_sync();
     return;
@@ -314,9 +265,9 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
     }
   };
 
-  // PIPE for kp = 64 (at kp <= 32 the scheduler hoists the unrolled window
-  // into a spill; those sizes keep the chunked loop)
-  if constexpr (HREC_ALS_PIPE && NT == 4 && !IMP) {
+  // The ring pipeline for kp = 64 (at kp <= 32 the scheduler hoists the
+  // unrolled window into a spill; those sizes keep the chunked loop)
+  if constexpr (NT == 4 && !IMP) {
   // Ring pipeline over WINDOWS of 16 steps (64 nnz: one index and one rating
   // per lane). Step s's gather is issued PF steps ahead into ring slot
   // s % PF; the index reaches the lane group by ds_bpermute and feeds a
@@ -327,8 +278,7 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
   // f64 sources sit in the MALL: shorter distance
   constexpr int PF = POOLED ? (S64 ? HREC_ALS_POOL_PF64 : HREC_ALS_POOL_PF) : (S64 ? HREC_ALS_PF64 : HREC_ALS_PF);
   static_assert(16 % PF == 0, "prefetch distance must divide the window");
-  static_assert(!S64 || (NT == 4 && MODE == 0 && (HREC_ALS_DIAG4 == 0 || HREC_ALS_DIAG4 == 3)),
-                "f64 sources: kp 64, f64 accumulation only");
+  static_assert(!S64 || MODE == 0, "f64 sources: kp 64, f64 accumulation only");
   const int voff = (S64 ? 8 : 4) * NT * col;
   const int bp_addr = 4 * sub;  // ds_bpermute byte address of nnz (4s + sub) is 16 s + 4 sub
   const uint64_t sbase = (uint64_t)src;
@@ -360,86 +310,62 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
 #pragma unroll
   for (int s = 0; s < PF; ++s) ring[s] = ring_load(bperm(iw0, s));
   int nidx = bperm(iw0, PF);  // source row of the next gather (one step ahead)
-  // DIAG4: a diagonal tile's 16 x 16 block is 16 sub-blocks of 4 x 4, of
+  // f64 accumulation (MODE 0) splits the diagonal tiles off the 16x16x4
+  // MFMAs: a diagonal tile's 16 x 16 block is 16 sub-blocks of 4 x 4, of
   // which 10 are distinct (symmetry). v_mfma_f64_4x4x4_4b runs 4 independent
   // 4 x 4 x 4 blocks at the 16x16x4 rate (16 vs 64 cycles, measured:
   // scripts/micro/mfma_f64_rate.hip); with A = B = the lane's operand it
   // yields the 4 diagonal sub-blocks (b, b), with B rotated by 4 / 8 lanes
   // inside each 16-lane row the sub-blocks (b, b + 1) and (b, b + 2) mod 4:
   // all 10, in 3/4 of the 16x16x4 time.
-  // DIAG4 = 1 rotates with DPP moves at the step itself; DIAG4 = 2 converts
-  // the next step's operands one step ahead and rotates them by ds_bpermute
-  // (LDS path), so the rotations have a whole step to land.
-  // DIAG4 = 3 gathers the rotated operands from memory instead: two more
-  // 16-B structured loads per step (the same source rows, the column slices
-  // of lane col + 4 and col + 8), PR steps ahead — no cross-lane moves.
-  constexpr bool kDiag4 = HREC_ALS_DIAG4 && MODE == 0;
-  constexpr bool kAhead = HREC_ALS_DIAG4 == 2 && MODE == 0;
-  constexpr bool kMemRot = HREC_ALS_DIAG4 == 3 && MODE == 0;
-  constexpr int PR = kMemRot ? HREC_ALS_PR : 1;  // rotated-load prefetch distance (steps)
-  constexpr bool kRot1Dpp =
-      kMemRot && (S64 ? (POOLED ? HREC_ALS_POOL_ROT1DPP64 : HREC_ALS_ROT1DPP64) : HREC_ALS_ROT1DPP);
+  // The rotated operands are gathered from memory, PR steps ahead: more
+  // structured loads of the same source rows at the column slices of lane
+  // col + 4 and col + 8 — no cross-lane moves. (kRot1Dpp: the rotation by 4
+  // is two 32-bit DPP moves of the own operand instead of a load.)
+  constexpr bool kDiag4 = MODE == 0;
+  constexpr int PR = HREC_ALS_PR;  // rotated-load prefetch distance (steps)
+  constexpr bool kRot1Dpp = S64 ? (POOLED ? HREC_ALS_POOL_ROT1DPP64 : HREC_ALS_ROT1DPP64) : HREC_ALS_ROT1DPP;
   static_assert(PR < PF, "rotated loads are issued from the current windows");
   const int voff1 = (S64 ? 8 : 4) * NT * ((col + 4) & 15), voff2 = (S64 ? 8 : 4) * NT * ((col + 8) & 15);
   auto rot_load = [&](int vi, int vo) -> RingT {
     if constexpr (S64) return struct_load_d(rsrc, vi, vo);
     else return struct_load<NT>(rsrc, vi, vo);
   };
-  // PAIR8 = 2: the shared rotation-by-8 product pairs tiles (0, 2) and
-  // (1, 3), whose operands are adjacent components: lanes col < 8 need
-  // components {0, 1}, lanes col >= 8 {2, 3} — of the own slice (A) and of
-  // the col + 8 slice (B). Two half-width loads at a per-lane offset deliver
-  // exactly those, so no lane selects are needed.
-  constexpr bool kPairL = kMemRot && HREC_ALS_PAIR8 == 2 && NT == 4;
+  // The rotation-by-8 product of a diagonal tile has 2 distinct sub-blocks in
+  // its 4 blocks, so two tiles share one v_mfma_f64_4x4x4_4b: blocks 0, 1
+  // (lanes with col < 8) take the operands of tile P, blocks 2, 3 those of
+  // tile P + 2 (P = 0, 1). The pairs (0, 2) and (1, 3) make the operands
+  // adjacent components: lanes col < 8 need components {0, 1}, lanes col >= 8
+  // {2, 3} — of the own slice (A) and of the col + 8 slice (B). Two half-width
+  // loads at a per-lane offset deliver exactly those, so no lane selects are
+  // needed.
   using PairT = std::conditional_t<S64, VecD2, Vec<2>>;
   const int hoff = (lane & 8) ? (S64 ? 16 : 8) : 0;
   auto pair_load = [&](int vi, int vo) -> PairT {
     if constexpr (S64) return struct_load_d2(rsrc, vi, vo);
     else return struct_load<2>(rsrc, vi, vo);
   };
-  RingT rot1[PR], rot2[PR];
+  RingT rot1[PR];
   PairT rotA[PR], rotB[PR];
-  if constexpr (kMemRot) {
+  if constexpr (kDiag4) {
 #pragma unroll
     for (int q = 0; q < PR; ++q) {
       const int vi = bperm(iw0, q);
       if constexpr (!kRot1Dpp) rot1[q] = rot_load(vi, voff1);
-      if constexpr (kPairL) {
-        rotA[q] = pair_load(vi, voff + hoff);
-        rotB[q] = pair_load(vi, voff2 + hoff);
-      } else {
-        rot2[q] = rot_load(vi, voff2);
-      }
+      rotA[q] = pair_load(vi, voff + hoff);
+      rotB[q] = pair_load(vi, voff2 + hoff);
     }
   }
-  double dg[NT][3];
+  // diagonal tile t: dg[t][0] the (b, b) sub-blocks, dg[t][1] the (b, b + 1);
+  // dc[P] the shared (b, b + 2) product of tiles P and P + 2. (dg[t][2] is
+  // not used. The array keeps the slot, as ar2 below keeps 2 of its 4: with
+  // either array smaller the compiler allocates the kernels' registers
+  // differently, which would have to be measured.)
+  double dg[NT][3], dc[2];
 #pragma unroll
-  for (int t = 0; t < NT; ++t) dg[t][0] = dg[t][1] = dg[t][2] = 0.0;
-  // PAIR8 (DIAG4 = 3): the rotation-by-8 product of a diagonal tile has 2
-  // distinct sub-blocks in its 4 blocks, so tiles 2P and 2P + 1 share one
-  // v_mfma_f64_4x4x4_4b: blocks 0, 1 (lanes with col < 8) take tile 2P's
-  // operands, blocks 2, 3 tile 2P + 1's (one conversion instead of two)
-  constexpr bool kPair8 = kMemRot && HREC_ALS_PAIR8 && NT % 2 == 0;
-  const bool hi8 = (lane & 8) != 0;
-  double dc[NT / 2 > 0 ? NT / 2 : 1];
+  for (int t = 0; t < NT; ++t) dg[t][0] = dg[t][1] = 0.0;
 #pragma unroll
-  for (int t = 0; t < (NT / 2 > 0 ? NT / 2 : 1); ++t) dc[t] = 0.0;
-  const int ra1 = 4 * ((lane & 48) | ((lane + 4) & 15)), ra2 = 4 * ((lane & 48) | ((lane + 8) & 15));
-  auto bperm64 = [](double x, int addr) {
-    const long long v = __double_as_longlong(x);
-    const int lo = __builtin_amdgcn_ds_bpermute(addr, (int)v);
-    const int hi = __builtin_amdgcn_ds_bpermute(addr, (int)(v >> 32));
-    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-  };
-  double an[NT], r1n[NT], r2n[NT];  // kAhead: the next step's operands
-  if constexpr (kAhead) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      an[t] = gram_cvt(ring[0].x[t]);
-      r1n[t] = bperm64(an[t], ra1);
-      r2n[t] = bperm64(an[t], ra2);
-    }
-  }
+  for (int t = 0; t < 2; ++t) dc[t] = 0.0;
   for (int64_t w = 0;; ++w) {
     int iw2;
     float rw2;
@@ -453,75 +379,28 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
         break;
       }
       const RingT cur = ring[s % PF];
-      double a[NT], ar1[NT], ar2[NT], apair[NT / 2 > 0 ? NT / 2 : 1];
-      if constexpr (kAhead) {
+      // a: the own operands; ar1: rotated by 4 lanes; apair[P] / ar2[P]: the
+      // A / B operands of the shared rotation-by-8 product P (P = 0, 1)
+      double a[NT], ar1[NT], ar2[NT], apair[2];
 #pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          a[t] = an[t];
-          ar1[t] = r1n[t];
-          ar2[t] = r2n[t];
-        }
-      } else {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          if constexpr (S64) a[t] = cur.x[t];
-          else a[t] = gram_cvt(cur.x[t]);
-        }
-      }
+      for (int t = 0; t < NT; ++t) a[t] = (double)cur.x[t];
       ring[s % PF] = ring_load(nidx);
-      if constexpr (kMemRot) {
+      if constexpr (kDiag4) {
 #pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          if constexpr (S64) {
-            ar1[t] = kRot1Dpp ? row_ror<12>(a[t]) : rot1[s % PR].x[t];
-            if constexpr (!kPair8) ar2[t] = rot2[s % PR].x[t];
-          } else {
-            // ROT1DPP: the rotation by 4 lanes of the converted operand (two
-            // 32-bit DPP moves) instead of a converted rotated load
-            ar1[t] = kRot1Dpp ? row_ror<12>(a[t]) : gram_cvt(rot1[s % PR].x[t]);
-            if constexpr (!kPair8) ar2[t] = gram_cvt(rot2[s % PR].x[t]);
-          }
-        }
-        if constexpr (kPairL) {
+        for (int t = 0; t < NT; ++t) ar1[t] = kRot1Dpp ? row_ror<12>(a[t]) : (double)rot1[s % PR].x[t];
 #pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            if constexpr (S64) {
-              apair[t] = rotA[s % PR].x[t];
-              ar2[t] = rotB[s % PR].x[t];
-            } else {
-              apair[t] = gram_cvt(rotA[s % PR].x[t]);
-              ar2[t] = gram_cvt(rotB[s % PR].x[t]);
-            }
-          }
-        } else if constexpr (kPair8) {
-#pragma unroll
-          for (int t = 0; t < NT / 2; ++t) {
-            if constexpr (S64) ar2[t] = sel64(hi8, rot2[s % PR].x[2 * t + 1], rot2[s % PR].x[2 * t]);
-            else ar2[t] = gram_cvt(hi8 ? rot2[s % PR].x[2 * t + 1] : rot2[s % PR].x[2 * t]);
-            apair[t] = sel64(hi8, a[2 * t + 1], a[2 * t]);
-          }
+        for (int t = 0; t < 2; ++t) {
+          apair[t] = (double)rotA[s % PR].x[t];
+          ar2[t] = (double)rotB[s % PR].x[t];
         }
         const int vr = (s + PR < 16) ? bperm(iw0, s + PR) : bperm(iw1, s + PR - 16);
         if constexpr (!kRot1Dpp) rot1[s % PR] = rot_load(vr, voff1);
-        if constexpr (kPairL) {
-          rotA[s % PR] = pair_load(vr, voff + hoff);
-          rotB[s % PR] = pair_load(vr, voff2 + hoff);
-        } else {
-          rot2[s % PR] = rot_load(vr, voff2);
-        }
-      }
-      if constexpr (kAhead) {
-        const Vec<NT> nx = ring[(s + 1) % PF];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          an[t] = gram_cvt(nx.x[t]);
-          r1n[t] = bperm64(an[t], ra1);
-          r2n[t] = bperm64(an[t], ra2);
-        }
+        rotA[s % PR] = pair_load(vr, voff + hoff);
+        rotB[s % PR] = pair_load(vr, voff2 + hoff);
       }
       nidx = (s + 1 + PF < 16) ? bperm(iw0, s + 1 + PF) : bperm(iw1, s + 1 + PF - 16);
       const float rf = __int_as_float(__builtin_amdgcn_ds_bpermute(bp_addr + 16 * s, __float_as_int(rw0)));
-      const double rv = gram_cvt(rf);
+      const double rv = (double)rf;
       if (MODE == 1 && (s % HREC_ALS_CH1) == 0) {
 #pragma unroll
         for (int p = 0; p < NPAIR; ++p) fa[p] = f4{0.f, 0.f, 0.f, 0.f};
@@ -532,19 +411,11 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
 #pragma unroll
         for (int J = I; J < NT; ++J) {
           if (MODE == 0) {
-            if (kDiag4 && I == J) {
+            if (I == J) {
               dg[I][0] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[I], a[I], dg[I][0], 0, 0, 0);
-              dg[I][1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[I], (kAhead || kMemRot) ? ar1[I] : row_ror<12>(a[I]),
-                                                            dg[I][1], 0, 0, 0);
-              if constexpr (kPairL) {  // tiles I and I + 2
-                if (I < 2) dc[I] = __builtin_amdgcn_mfma_f64_4x4x4f64(apair[I], ar2[I], dc[I], 0, 0, 0);
-              } else if constexpr (kPair8) {
-                if (I % 2 == 0)
-                  dc[I / 2] = __builtin_amdgcn_mfma_f64_4x4x4f64(apair[I / 2], ar2[I / 2], dc[I / 2], 0, 0, 0);
-              } else {
-                dg[I][2] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[I], (kAhead || kMemRot) ? ar2[I] : row_ror<8>(a[I]),
-                                                              dg[I][2], 0, 0, 0);
-              }
+              dg[I][1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[I], ar1[I], dg[I][1], 0, 0, 0);
+              // tiles I and I + 2
+              if (I < 2) dc[I] = __builtin_amdgcn_mfma_f64_4x4x4f64(apair[I], ar2[I], dc[I], 0, 0, 0);
             } else {
               acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[I], a[J], acc[p], 0, 0, 0);
             }
@@ -586,10 +457,10 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
 #pragma unroll
       for (int sh = 0; sh < 3; ++sh) {
         const int r = 4 * q4 + i4, c = 4 * ((q4 + sh) & 3) + j4;
-        if (kPair8 && sh == 2) {  // this tile's blocks of the shared product (with their mirrors: all 4)
+        if (sh == 2) {  // this tile's blocks of the shared product (with their mirrors: all 4)
           // the other tile's lanes write the same values to the junk slots 256, 257
-          const bool mine = kPairL ? (q4 >= 2) == (I >= 2) : (q4 >= 2) == (I % 2 == 1);
-          const double v = kPairL ? dc[I & 1] : dc[I / 2];
+          const bool mine = (q4 >= 2) == (I >= 2);
+          const double v = dc[I & 1];
           stage[mine ? r * 16 + c : 256] = v;
           stage[mine ? c * 16 + r : 257] = v;
           continue;
@@ -691,7 +562,6 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
   // U_KM -= U_JK^T U_JM on the f64 matrix cores, straight from the
   // accumulator registers (the C/D layout of tile (J,K) is exactly the A/B
   // operand layout of the 4 k-steps).
-  before_lds();
   if (sub == 0) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) bsh[16 * t + col] = bp[t];  // permuted b
@@ -805,13 +675,7 @@ __device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1
 #pragma unroll
     for (int m = 0; m < 16; ++m) {
       const int q = 16 * J + m;
-      if constexpr (HREC_ALS_RLPANEL) {
-        // the diagonal block's lanes also hold its lower triangle (A[c][q] by
-        // symmetry), so column pv carries the pivot row of the block
-        a[m] = !own ? 0.0 : q <= c ? Up[tri(c) + q] : c < 16 * J + 16 ? Up[tri(q) + c] : 0.0;
-      } else {
-        a[m] = (own && q <= c) ? Up[tri(c) + q] : 0.0;
-      }
+      a[m] = (own && q <= c) ? Up[tri(c) + q] : 0.0;
     }
     // (c) 16 pivots of A = Ut^T D Ut (LDL^T: no square roots), right-looking,
     //     columns on lanes. The unscaled pivot row goes to LDS (alternating
@@ -820,45 +684,11 @@ __device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1
     //     needs only the lane's own entries), so the per-pivot critical path is
     //     rcp -> Newton -> scale -> fma -> readlane.
     double piv = bcast(a[0], 16 * J);
-    if constexpr (HREC_ALS_RLPANEL) {
-      // Pivot pv's row within the block, A[pv][16J + m] (m > i), is lane pv's
-      // own column entries A[16J + m][pv] (the Schur complement stays
-      // symmetric): read by v_readlane at the start of the pivot, so the
-      // per-pivot critical path is rcp -> Newton -> scale -> fma -> readlane,
-      // with no LDS store/load round trip.
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int pv = 16 * J + i;
-        double u[16];
-#pragma unroll
-        for (int m0 = i + 1; m0 < 16; ++m0) u[m0] = bcast(a[m0], pv);
-        const double r0 = __builtin_amdgcn_rcp(piv);
-        const double r = fma(r0, fma(-piv, r0, 1.0), r0);
-        const double ut = a[i] * r;  // Ut[pv][c]
-        if (own && c > pv) Up[tri(c) + pv] = ut;
-        if (c == pv) {
-          dsh[pv] = piv;
-          rdsh[pv] = r;
-        }
-        const double wq = bcast(bs, pv);
-        if (own && c > pv) bs = fma(-ut, wq, bs);
-        if (i < 15) {
-#pragma unroll
-          for (int m0 = i + 1; m0 < 16; ++m0) a[m0] = fma(-u[m0], ut, a[m0]);
-          piv = bcast(a[i + 1], pv + 1);
-        }
-      }
-    } else
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int pv = 16 * J + i;
       double* cb = colbuf + 64 * (i & 1);
       if (c < KP) cb[c] = a[i];  // A[pv][c] (lane pv: the pivot)
-      // RLPANEL 2: the one pivot-row entry the NEXT pivot depends on,
-      // A[pv][pv + 1], comes by v_readlane (final since the previous pivot),
-      // so the LDS round trip of the rest has a whole pivot of slack
-      constexpr bool kRl2 = HREC_ALS_RLPANEL == 2;
-      const double u1 = (kRl2 && i < 15) ? bcast(a[i], pv + 1) : 0.0;
       // 1 / piv: v_rcp_f64 (~2^-24 relative) + one Newton step
       const double r0 = __builtin_amdgcn_rcp(piv);
       const double r = fma(r0, fma(-piv, r0, 1.0), r0);
@@ -873,18 +703,13 @@ __device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1
         if (own && c > pv) bs = fma(-ut, wq, bs);
       }
       if (i < 15) {
-        if constexpr (kRl2) {  // bit-identical: u1 is the value lane pv + 1 stored to cb
-          a[i + 1] = fma(-u1, ut, a[i + 1]);
-          piv = bcast(a[i + 1], pv + 1);
-        } else {
-          piv = bcast(fma(-a[i], ut, a[i + 1]), pv + 1);
-        }
+        piv = bcast(fma(-a[i], ut, a[i + 1]), pv + 1);
         wave_lds_sync();
 #pragma unroll
         for (int m0 = (i + 1) & ~1; m0 < 16; m0 += 2) {
           const double2 u = *reinterpret_cast<const double2*>(cb + 16 * J + m0);
-          if (m0 > i + (kRl2 ? 1 : 0)) a[m0] = fma(-u.x, ut, a[m0]);
-          if (!kRl2 || m0 > i) a[m0 + 1] = fma(-u.y, ut, a[m0 + 1]);
+          if (m0 > i) a[m0] = fma(-u.x, ut, a[m0]);
+          a[m0 + 1] = fma(-u.y, ut, a[m0 + 1]);
         }
       }
     }

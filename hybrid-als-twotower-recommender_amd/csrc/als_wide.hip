@@ -44,9 +44,6 @@
 #ifndef HREC_WIDE_G
 #define HREC_WIDE_G 4  // Gramian tile slots per operand-read group (reads of group g + 1 overlap group g's MFMAs)
 #endif
-#ifndef HREC_WIDE_BDEFER
-#define HREC_WIDE_BDEFER 0  // 1 = a window's rhs accumulation runs during the next window's MFMAs (3 window buffers; measured 640 -> 645 ms per rank-256 epoch, off)
-#endif
 #ifndef HREC_WIDE_WR_WIDE
 #define HREC_WIDE_WR_WIDE 32  // ratings per window at kp >= 192 (16: 641 ms, 32: 638 ms per rank-256 epoch) (multiple of 4; LDS: two windows of WR x (kp + 16) doubles)
 #endif
@@ -168,10 +165,9 @@ __global__ __launch_bounds__(WideShape<NT>::THREADS) void als_half_sweep_wide_ke
     int64_t n_rows, const float* __restrict__ src, int64_t n_src, int k, double reg, float* __restrict__ dst) {
   using S = WideShape<NT>;
   constexpr int KP = S::KP, LD = S::LD, WR = S::WR, kWideWaves = S::WAVES, kWideThreads = S::THREADS;
-  // window buffers: NB = 3 rotates current / next / previous window (the
-  // previous one's rhs accumulation overlaps the current one's MFMAs);
-  // phase 2 uses buffers 0, 1 as its double-buffered panel
-  constexpr int NB = HREC_WIDE_BDEFER ? 3 : 2;
+  // window buffers (current / next); phase 2 uses them as its
+  // double-buffered panel
+  constexpr int NB = 2;
   __shared__ __attribute__((aligned(16))) double buf[NB][S::BUF];
   __shared__ double bsh[KP];      // b, then w (forward), then v / x
   __shared__ double dsh[KP];      // pivots D
@@ -318,11 +314,6 @@ __global__ __launch_bounds__(WideShape<NT>::THREADS) void als_half_sweep_wide_ke
       if (win + 2 < nwin) load_idx(win + 2, ixn);
       load_rows(win + 1, ixc);
     }
-    // HREC_WIDE_BDEFER: the previous window's b (buffer nb + 1 mod 3) before
-    // this window's MFMAs — on waves 0..3, whose SIMD partners (waves 4..7)
-    // keep the matrix pipe busy meanwhile — instead of after them on the
-    // path to the barrier
-    if (HREC_WIDE_BDEFER && win > 0) rhs_window(nb + 1 == NB ? 0 : nb + 1);
     const double* wb = buf[cb];
 #pragma unroll 1
     for (int st = 0; st < WR / 4; ++st) {
@@ -356,8 +347,7 @@ __global__ __launch_bounds__(WideShape<NT>::THREADS) void als_half_sweep_wide_ke
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    // (the last window's b before the barrier: phase 2 reuses buffers 0, 1)
-    if (!HREC_WIDE_BDEFER || win + 1 == nwin) rhs_window(cb);
+    rhs_window(cb);  // before the barrier: a later window, then phase 2, reuses the buffer
     if (win + 1 < nwin) store_window(nb);
     __syncthreads();
     cb = nb;
