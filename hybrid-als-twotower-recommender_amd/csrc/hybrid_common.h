@@ -121,6 +121,31 @@ __device__ __forceinline__ uint64_t hp_order_key(double v, int64_t idx) {
   return idx == INT64_MAX ? 0ull : (v != v ? 1ull : ord);
 }
 
+// What hrec_hybrid_lists (csrc/hybrid_lists.hip) and hrec_hybrid_model_f1
+// (csrc/hybrid_f1.hip) share: the sample / list sizes, the segment a wave
+// covers, the substituted ALS score and the key of a live column.
+constexpr int kHlSample = HREC_HYBRID_LISTS_SAMPLE;  // HYBRID_LISTS_SAMPLE of src/_hrec.py
+constexpr int kHlCap = HREC_HYBRID_LISTS_CAP;        // >= kHlSample: n <= kHlSample never overflows
+constexpr int kHlPer = 16;       // columns per lane per segment
+constexpr int kHlSeg = 64 * kHlPer;
+constexpr int kHlBoundBlock = 256;
+constexpr int kHlBoundPer = kHlSample / kHlBoundBlock;
+static_assert(kHlCap >= kHlSample && kHlCap >= kTopkSelectMax, "a list holds the sample and any top_k");
+
+__device__ __forceinline__ void hl_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// a_rj: the f32 score widened, or the column's fallback value where it is NaN
+__device__ __forceinline__ double hl_als(float a, const double* __restrict__ fb, int64_t j) {
+  return (a != a && fb) ? fb[j] : (double)a;
+}
+
+// hp_order_key of a live (non-excluded) column
+__device__ __forceinline__ uint64_t hl_key(double v) { return hp_order_key(v, 0); }
+
 // 64-bit moves across lanes: DPP (CTRL: gfx9 dpp_ctrl, all sources valid)
 // and readlane, as two 32-bit halves.
 template <int CTRL, typename T>

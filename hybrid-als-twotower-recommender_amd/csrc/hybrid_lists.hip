@@ -13,32 +13,21 @@
 //   3. mode 1: hl_pass_kernel<1> writes every fused value and its column (-1
 //      where excluded) and topk_rows ranks the whole rows.
 // Keys are hp_order_key's: 0 = excluded / empty, 1 = NaN, numbers above.
+// hrec_hybrid_lists_rowwise is the same body with the fusion weights chosen
+// per row (row_wins, hrec_hybrid_model_f1's output) instead of per call.
 #include "exclusion.h"
 #include "hybrid_common.h"
 
 namespace hrec {
 
-constexpr int kHlSample = HREC_HYBRID_LISTS_SAMPLE;  // HYBRID_LISTS_SAMPLE of src/_hrec.py
-constexpr int kHlCap = HREC_HYBRID_LISTS_CAP;        // >= kHlSample: n <= kHlSample never overflows
-constexpr int kHlPer = 16;       // columns per lane per segment
-constexpr int kHlSeg = 64 * kHlPer;
-constexpr int kHlBoundBlock = 256;
-constexpr int kHlBoundPer = kHlSample / kHlBoundBlock;
-static_assert(kHlCap >= kHlSample && kHlCap >= kTopkSelectMax, "a list holds the sample and any top_k");
-
-__device__ __forceinline__ void hl_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+// The fusion weights of row r: (0.8, 0.2) when ALS wins, else (0.2, 0.8); row_wins (optional) decides per row.
+struct HlWeights {
+  double w0, w1;
+};
+__device__ __forceinline__ HlWeights hl_weights(const int32_t* __restrict__ row_wins, int als_wins, int64_t r) {
+  const bool wins = row_wins ? row_wins[r] != 0 : als_wins != 0;
+  return {wins ? 0.8 : 0.2, wins ? 0.2 : 0.8};
 }
-
-// a_rj: the f32 score widened, or the column's fallback value where it is NaN
-__device__ __forceinline__ double hl_als(float a, const double* __restrict__ fb, int64_t j) {
-  return (a != a && fb) ? fb[j] : (double)a;
-}
-
-// hp_order_key of a live (non-excluded) column
-__device__ __forceinline__ uint64_t hl_key(double fused) { return hp_order_key(fused, 0); }
 
 // One 1024-thread block per row: ALS min / max in f64 after the substitution,
 // two-tower min / max in f32 (NaN ignored; hrec_fuse_topk's fmin / fmax from
@@ -127,8 +116,8 @@ __global__ __launch_bounds__(1024) void hl_extremes_kernel(
 __global__ __launch_bounds__(kHlBoundBlock) void hl_bound_kernel(
     const float* __restrict__ als, const float* __restrict__ tt, int64_t ld, const double* __restrict__ fb,
     const int64_t* __restrict__ excl_rows, const int64_t* __restrict__ excl_indptr,
-    const int32_t* __restrict__ excl_cols, const HpScale* __restrict__ coef, double w0, double w1, int kk,
-    uint64_t* __restrict__ bound) {
+    const int32_t* __restrict__ excl_cols, const HpScale* __restrict__ coef, const int32_t* __restrict__ row_wins,
+    int als_wins, int kk, uint64_t* __restrict__ bound) {
   __shared__ uint32_t bm[kHlSample / 32];
   __shared__ int cn[64];
   const int64_t r = blockIdx.x;
@@ -144,6 +133,7 @@ __global__ __launch_bounds__(kHlBoundBlock) void hl_bound_kernel(
   }
   __syncthreads();
   const HpScale sc = coef[r];
+  const auto [w0, w1] = hl_weights(row_wins, als_wins, r);
   uint64_t key[kHlBoundPer];
 #pragma unroll
   for (int e = 0; e < kHlBoundPer; ++e) {
@@ -178,9 +168,9 @@ template <int MODE>
 __global__ __launch_bounds__(256) void hl_pass_kernel(
     const float* __restrict__ als, const float* __restrict__ tt, int64_t n, int64_t ld, int64_t segs,
     const double* __restrict__ fb, const int64_t* __restrict__ excl_rows, const int64_t* __restrict__ excl_indptr,
-    const int32_t* __restrict__ excl_cols, const HpScale* __restrict__ coef, double w0, double w1,
-    const uint64_t* __restrict__ bound, int64_t L, double* __restrict__ out_v, int64_t* __restrict__ out_i,
-    int* __restrict__ cnt) {
+    const int32_t* __restrict__ excl_cols, const HpScale* __restrict__ coef, const int32_t* __restrict__ row_wins,
+    int als_wins, const uint64_t* __restrict__ bound, int64_t L, double* __restrict__ out_v,
+    int64_t* __restrict__ out_i, int* __restrict__ cnt) {
   __shared__ uint32_t bm_sh[4][kHlSeg / 32];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t seg = (int64_t)blockIdx.x * 4 + wv;
@@ -201,6 +191,7 @@ __global__ __launch_bounds__(256) void hl_pass_kernel(
   }
   hl_wave_sync();
   const HpScale sc = coef[r];
+  const auto [w0, w1] = hl_weights(row_wins, als_wins, r);
   const uint64_t tk = (MODE == 0 && bound) ? bound[r] : 0ull;
   const float* ar = als + r * ld + seg0 + lane;
   const float* tr = tt + r * ld + seg0 + lane;
@@ -283,25 +274,27 @@ extern "C" size_t hrec_hybrid_lists_workspace_bytes(int64_t n_rows, int64_t n, i
   return hl_layout(nullptr, n_rows, n, (int)(top_k < n ? top_k : n), mode == 1 ? 1 : 0).total;
 }
 
-extern "C" int hrec_hybrid_lists(const float* als, const float* tt, int64_t n_rows, int64_t n, int64_t ld,
-                                 const double* als_fallback, int als_wins, int top_k, int mode,
-                                 const int64_t* excl_rows, const int64_t* excl_indptr, const int32_t* excl_cols,
-                                 int64_t* out_idx, double* out_val, int32_t* out_len, double* out_minmax,
-                                 int* overflow, void* workspace, size_t workspace_bytes, void* stream) {
-  HREC_REQUIRE(n_rows >= 0 && n >= 1, "hybrid_lists: bad shape");
-  HREC_REQUIRE(ld >= n, "hybrid_lists: ld must be >= n");
-  HREC_REQUIRE(n_rows < 65536, "hybrid_lists: at most 65535 rows per call");
-  HREC_REQUIRE(top_k >= 1 && top_k <= 1024, "hybrid_lists: top_k must be in [1, 1024]");
-  HREC_REQUIRE(mode == 0 || mode == 1, "hybrid_lists: mode must be 0 or 1");
+// The body of hrec_hybrid_lists (row_wins null: als_wins for every row) and
+// hrec_hybrid_lists_rowwise (rowwise: row_wins[r] != 0 chooses row r's weights).
+static int hl_run(const char* who, bool rowwise, const float* als, const float* tt, int64_t n_rows, int64_t n,
+                  int64_t ld, const double* als_fallback, const int32_t* row_wins, int als_wins, int top_k, int mode,
+                  const int64_t* excl_rows, const int64_t* excl_indptr, const int32_t* excl_cols, int64_t* out_idx,
+                  double* out_val, int32_t* out_len, double* out_minmax, int* overflow, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+  HREC_REQUIRE(n_rows >= 0 && n >= 1, "%s: bad shape", who);
+  HREC_REQUIRE(ld >= n, "%s: ld must be >= n", who);
+  HREC_REQUIRE(n_rows < 65536, "%s: at most 65535 rows per call", who);
+  HREC_REQUIRE(top_k >= 1 && top_k <= 1024, "%s: top_k must be in [1, 1024]", who);
+  HREC_REQUIRE(mode == 0 || mode == 1, "%s: mode must be 0 or 1", who);
   const bool any_excl = excl_rows || excl_indptr || excl_cols;
   HREC_REQUIRE(!any_excl || (excl_rows && excl_indptr && excl_cols),
-               "hybrid_lists: the exclusion CSR needs excl_rows, excl_indptr and excl_cols (or none of them)");
+               "%s: the exclusion CSR needs excl_rows, excl_indptr and excl_cols (or none of them)", who);
   if (n_rows == 0) return HREC_OK;
-  HREC_REQUIRE(als && tt && out_idx && out_val && out_len && overflow && workspace, "hybrid_lists: null pointer");
+  HREC_REQUIRE(als && tt && out_idx && out_val && out_len && overflow && workspace && (row_wins || !rowwise),
+               "%s: null pointer", who);
   const size_t need = hrec_hybrid_lists_workspace_bytes(n_rows, n, top_k, mode);
-  HREC_REQUIRE(workspace_bytes >= need, "hybrid_lists: workspace %zu < %zu", workspace_bytes, need);
+  HREC_REQUIRE(workspace_bytes >= need, "%s: workspace %zu < %zu", who, workspace_bytes, need);
   hipStream_t s = as_stream(stream);
-  const double w0 = als_wins ? 0.8 : 0.2, w1 = als_wins ? 0.2 : 0.8;
   const int kk = (int)(top_k < n ? top_k : n);
   const HlWs w = hl_layout(workspace, n_rows, n, kk, mode);
   const int vec4 = (ld % 4 == 0) && (((reinterpret_cast<uintptr_t>(als) | reinterpret_cast<uintptr_t>(tt)) & 15) == 0);
@@ -313,7 +306,8 @@ extern "C" int hrec_hybrid_lists(const float* als, const float* tt, int64_t n_ro
   const dim3 gp((unsigned)((segs + 3) / 4), (unsigned)n_rows);
   if (mode == 1) {
     hipLaunchKernelGGL(hl_pass_kernel<1>, gp, dim3(256), 0, s, als, tt, n, ld, segs, als_fallback, excl_rows,
-                       excl_indptr, excl_cols, w.coef, w0, w1, (const uint64_t*)nullptr, n, w.v, w.i, w.cnt);
+                       excl_indptr, excl_cols, w.coef, row_wins, als_wins, (const uint64_t*)nullptr, n, w.v, w.i,
+                       w.cnt);
     rc = check_launch("hl_pass_kernel (full)");
     if (rc) return rc;
     return topk_rows<double>(w.v, n_rows, n, n, kk, out_idx, out_val, w.tws, (size_t)1 << 62, s, w.i);
@@ -321,16 +315,37 @@ extern "C" int hrec_hybrid_lists(const float* als, const float* tt, int64_t n_ro
   const bool sampled = n > kHlSample;  // else the whole row is the sample: every live column goes to the list
   if (sampled) {
     hipLaunchKernelGGL(hl_bound_kernel, dim3((unsigned)n_rows), dim3(kHlBoundBlock), 0, s, als, tt, ld, als_fallback,
-                       excl_rows, excl_indptr, excl_cols, w.coef, w0, w1, kk, w.bound);
+                       excl_rows, excl_indptr, excl_cols, w.coef, row_wins, als_wins, kk, w.bound);
     rc = check_launch("hl_bound_kernel");
     if (rc) return rc;
   }
   hipLaunchKernelGGL(hl_pass_kernel<0>, gp, dim3(256), 0, s, als, tt, n, ld, segs, als_fallback, excl_rows,
-                     excl_indptr, excl_cols, w.coef, w0, w1, sampled ? (const uint64_t*)w.bound : nullptr, w.L, w.v,
-                     w.i, w.cnt);
+                     excl_indptr, excl_cols, w.coef, row_wins, als_wins,
+                     sampled ? (const uint64_t*)w.bound : nullptr, w.L, w.v, w.i, w.cnt);
   rc = check_launch("hl_pass_kernel (bounded)");
   if (rc) return rc;
   rc = count_overflow(w.cnt, (int)n_rows, (int)w.L, overflow, s);
   if (rc) return rc;
   return topk_rows<double>(w.v, n_rows, w.L, w.L, kk, out_idx, out_val, w.tws, (size_t)1 << 62, s, w.i, w.cnt);
+}
+
+extern "C" int hrec_hybrid_lists(const float* als, const float* tt, int64_t n_rows, int64_t n, int64_t ld,
+                                 const double* als_fallback, int als_wins, int top_k, int mode,
+                                 const int64_t* excl_rows, const int64_t* excl_indptr, const int32_t* excl_cols,
+                                 int64_t* out_idx, double* out_val, int32_t* out_len, double* out_minmax,
+                                 int* overflow, void* workspace, size_t workspace_bytes, void* stream) {
+  return hl_run("hybrid_lists", false, als, tt, n_rows, n, ld, als_fallback, nullptr, als_wins, top_k, mode, excl_rows,
+                excl_indptr, excl_cols, out_idx, out_val, out_len, out_minmax, overflow, workspace, workspace_bytes,
+                stream);
+}
+
+extern "C" int hrec_hybrid_lists_rowwise(const float* als, const float* tt, int64_t n_rows, int64_t n, int64_t ld,
+                                         const double* als_fallback, const int32_t* row_wins, int top_k, int mode,
+                                         const int64_t* excl_rows, const int64_t* excl_indptr,
+                                         const int32_t* excl_cols, int64_t* out_idx, double* out_val,
+                                         int32_t* out_len, double* out_minmax, int* overflow, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+  return hl_run("hybrid_lists_rowwise", true, als, tt, n_rows, n, ld, als_fallback, row_wins, 0, top_k, mode,
+                excl_rows, excl_indptr, excl_cols, out_idx, out_val, out_len, out_minmax, overflow, workspace,
+                workspace_bytes, stream);
 }

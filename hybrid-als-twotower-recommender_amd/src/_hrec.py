@@ -93,6 +93,11 @@ _SIGNATURES = {
     "hrec_hybrid_lists_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i32, _c_i32]),
     "hrec_hybrid_lists": (_c_i32, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _c_i32, _c_i32, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "hrec_hybrid_lists_rowwise": (_c_i32, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i32, _c_i32, _vp, _vp, _vp,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "hrec_hybrid_model_f1_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i32, _c_i32]),
+    "hrec_hybrid_model_f1": (_c_i32, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _c_i32, _vp, _vp, _vp, _vp,
+                                      _c_i32, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
     "hrec_fuse_workspace_bytes": (_c_sz, [_c_i64, _c_i32]),
     "hrec_fuse_topk": (_c_i32, [_vp, _vp, _c_i32, _c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp,
                                 _c_sz, _vp]),
@@ -1517,19 +1522,9 @@ HYBRID_LISTS_SAMPLE = 4096  # HREC_HYBRID_LISTS_SAMPLE: columns whose kk-th best
 HYBRID_LISTS_CAP = 4096     # HREC_HYBRID_LISTS_CAP: entries of a row's list (mode 0)
 
 
-def hybrid_lists(als, tt, top_k, als_wins, fallback=None, excl=None, mode=0, want_minmax=False):
-    """hrec_hybrid_lists over the f32 device score matrices als / tt [n_rows,
-    n] (unit column stride, one shared row stride >= n): per row the stable
-    descending ranking of hrec_fuse_topk's fused scores without the row's
-    excluded columns, cut to kk = min(top_k, n). fallback (f64 [n] device,
-    optional) replaces NaN ALS entries per column; excl (optional) =
-    (excl_rows int64 [n_rows], excl_indptr int64, excl_cols int32), the CSR
-    of dot_topk_excluding. mode 0: bounded (a set overflow flag means some
-    row's list was cut: repeat with mode 1); mode 1: full. Returns (idx int64
-    [n_rows, kk], val f64 [n_rows, kk], lens int32 [n_rows], overflow int32
-    [1][, minmax f64 [n_rows, 4]]) as device tensors; entries past a row's
-    length are unspecified."""
-    name = "hybrid_lists"
+def _score_pair(name, als, tt, fallback):
+    """The checks hybrid_lists and hybrid_model_f1 share: (als, tt, ld) of two
+    f32 device matrices with unit column stride and one row stride >= n."""
     for t, what in ((als, "als"), (tt, "tt")):
         if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
             raise HrecError(f"{name}: {what} must be a 2-D f32 device tensor")
@@ -1544,6 +1539,14 @@ def hybrid_lists(als, tt, top_k, als_wins, fallback=None, excl=None, mode=0, wan
         als, tt, ld = als.contiguous(), tt.contiguous(), n
     if fallback is not None and fallback.numel() != n:
         raise HrecError(f"{name}: fallback must hold one value per column")
+    return als, tt, ld
+
+
+def _hybrid_lists(name, als, tt, top_k, wins, fallback, excl, mode, want_minmax):
+    """The body of hybrid_lists (wins: a bool) and hybrid_lists_rowwise (wins:
+    int32 [n_rows] on the device)."""
+    als, tt, ld = _score_pair(name, als, tt, fallback)
+    n_rows, n = als.shape
     dev = als.device
     kk = min(int(top_k), n)
     idx = torch.empty((n_rows, kk), dtype=torch.int64, device=dev)
@@ -1557,16 +1560,88 @@ def hybrid_lists(als, tt, top_k, als_wins, fallback=None, excl=None, mode=0, wan
         excl_args = (_dev(excl[0], torch.int64, f"{name}: excl_rows"), *_excl_args(name, excl[1], excl[2]))
     else:
         excl_args = (None, None, None)
+    if isinstance(wins, torch.Tensor):
+        if wins.numel() != n_rows:
+            raise HrecError(f"{name}: row_wins must hold one entry per row")
+        wins = _dev(wins, torch.int32, f"{name}: row_wins")
+    else:
+        wins = int(bool(wins))
     need = int(lib().hrec_hybrid_lists_workspace_bytes(n_rows, n, int(top_k), int(mode)))
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    _check("hrec_hybrid_lists", lib().hrec_hybrid_lists(
+    _check(f"hrec_{name}", getattr(lib(), f"hrec_{name}")(
         _vp(als.data_ptr()), _vp(tt.data_ptr()), n_rows, n, ld, _dev(fallback, torch.float64, "fallback"),
-        int(bool(als_wins)), int(top_k), int(mode), *excl_args, _dev(idx, torch.int64, "out_idx"),
+        wins, int(top_k), int(mode), *excl_args, _dev(idx, torch.int64, "out_idx"),
         _dev(val, torch.float64, "out_val"), _dev(lens, torch.int32, "out_len"),
         _dev(minmax, torch.float64, "out_minmax"), _dev(overflow, torch.int32, "overflow"),
         _dev(ws, torch.uint8, "ws"), need, _stream()))
     res = (idx, val, lens, overflow)
     return res + (minmax,) if want_minmax else res
+
+
+def hybrid_lists(als, tt, top_k, als_wins, fallback=None, excl=None, mode=0, want_minmax=False):
+    """hrec_hybrid_lists over the f32 device score matrices als / tt [n_rows,
+    n] (unit column stride, one shared row stride >= n): per row the stable
+    descending ranking of hrec_fuse_topk's fused scores without the row's
+    excluded columns, cut to kk = min(top_k, n). fallback (f64 [n] device,
+    optional) replaces NaN ALS entries per column; excl (optional) =
+    (excl_rows int64 [n_rows], excl_indptr int64, excl_cols int32), the CSR
+    of dot_topk_excluding. mode 0: bounded (a set overflow flag means some
+    row's list was cut: repeat with mode 1); mode 1: full. Returns (idx int64
+    [n_rows, kk], val f64 [n_rows, kk], lens int32 [n_rows], overflow int32
+    [1][, minmax f64 [n_rows, 4]]) as device tensors; entries past a row's
+    length are unspecified."""
+    return _hybrid_lists("hybrid_lists", als, tt, top_k, bool(als_wins), fallback, excl, mode, want_minmax)
+
+
+def hybrid_lists_rowwise(als, tt, top_k, row_wins, fallback=None, excl=None, mode=0, want_minmax=False):
+    """hrec_hybrid_lists_rowwise: hybrid_lists with row r's weights chosen by
+    row_wins[r] != 0 (int32 [n_rows] on the device, hybrid_model_f1's wins)."""
+    if not isinstance(row_wins, torch.Tensor):
+        raise HrecError("hybrid_lists_rowwise: row_wins: expected a device tensor")
+    return _hybrid_lists("hybrid_lists_rowwise", als, tt, top_k, row_wins, fallback, excl, mode, want_minmax)
+
+
+def hybrid_model_f1(als, tt, k, labels=None, default_wins=False, fallback=None, mode=0, want_top=False):
+    """hrec_hybrid_model_f1 over hybrid_lists' score matrices: per row each
+    model's own stable top-min(k, n) (ALS keys with the fallback substituted,
+    in f64; two-tower keys in f32; NaN last) and compute_f1_score's F1 of it
+    against the row's labels. labels (optional) = (label_rows int64 [n_rows]
+    (-1: no labels), label_indptr int64, label_cols int32 (candidate columns,
+    ascending and distinct per row), label_total int32 (one per CSR row: the
+    size of the whole ground-truth set)). Returns (f1 f64 [n_rows, 2] (ALS,
+    two-tower; NaN for a row without labels), wins int32 [n_rows] (f1_als >
+    f1_tt; default_wins for a row without labels), overflow int32 [1][, top
+    int64 [n_rows, 2, min(k, n)]]) as device tensors. mode 0: bounded (a set
+    overflow flag: repeat with mode 1); mode 1: full."""
+    name = "hybrid_model_f1"
+    als, tt, ld = _score_pair(name, als, tt, fallback)
+    n_rows, n = als.shape
+    dev = als.device
+    f1 = torch.empty((n_rows, 2), dtype=torch.float64, device=dev)
+    wins = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+    top = torch.empty((n_rows, 2, min(max(int(k), 0), n)), dtype=torch.int64, device=dev) if want_top else None
+    if labels is not None:
+        rows, indptr, cols, total = labels
+        if rows.numel() != n_rows:
+            raise HrecError(f"{name}: label_rows must hold one entry per row")
+        if total.numel() != indptr.numel() - 1:
+            raise HrecError(f"{name}: label_total must hold one entry per label row")
+        if total.numel() == 0:
+            total = torch.zeros(1, dtype=torch.int32, device=dev)  # a stand-in entry, never read
+        label_args = (_dev(rows, torch.int64, f"{name}: label_rows"), *_excl_args(name, indptr, cols),
+                      _dev(total, torch.int32, f"{name}: label_total"))
+    else:
+        label_args = (None, None, None, None)
+    need = int(lib().hrec_hybrid_model_f1_workspace_bytes(n_rows, n, int(k), int(mode)))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    _check("hrec_hybrid_model_f1", lib().hrec_hybrid_model_f1(
+        _vp(als.data_ptr()), _vp(tt.data_ptr()), n_rows, n, ld, _dev(fallback, torch.float64, "fallback"), int(k),
+        int(mode), *label_args, int(bool(default_wins)), _dev(f1, torch.float64, "out_f1"),
+        _dev(wins, torch.int32, "out_wins"), _dev(top, torch.int64, "out_top"), _dev(overflow, torch.int32, "overflow"),
+        _dev(ws, torch.uint8, "ws"), need, _stream()))
+    res = (f1, wins, overflow)
+    return res + (top,) if want_top else res
 
 
 # ------------------------------------------------------- multi-GPU (C-ABI)

@@ -16,6 +16,9 @@ device pass, with an optional seen-item exclusion) and ranking_metrics /
 evaluate_ranking (Spark's five ranking metrics of those lists against a
 held-out frame) — hrec_hybrid_lists over both models' batched scores. Equal
 fused scores keep candidate-frame order there, not the set order above.
+With actual= those four fuse each user by its own F1@k (DESIGN §23:
+hrec_hybrid_model_f1, hrec_hybrid_lists_rowwise); evaluate_models /
+fit_fusion_weights are the batch form of evaluate_individual_models.
 """
 import itertools
 import os
@@ -325,51 +328,138 @@ class HybridRecommendationSystem:
                              "part of the batched lists")
         return fb
 
-    def _recommend_device(self, users, cand, num, exclude=None):
+    def _spans(self, s, e, N, row_bytes):
+        """[s, e) cut into sub-batches whose rows of row_bytes * N bytes stay under RECOMMEND_SCORE_BYTES."""
+        sub = max(1, min(self.RECOMMEND_ROWS, self.RECOMMEND_SCORE_BYTES // (row_bytes * N)))
+        return [(s1, min(s1 + sub, e)) for s1 in range(s, e, sub)]
+
+    def _scores(self, users, cand):
+        """(ALS f32 [m, N] — transform's, NaN where an id is unknown —, two-tower f32 [m, N] — the bits
+        predict_for_user gives) of a sub-batch of users."""
+        tt = self.twotower_model
+        a = self.als_model.model.score(users, cand.item_ids)
+        U = tt.model.user_vectors(torch.as_tensor(users.astype(np.int32), device=tt.model.device))
+        return a, _hrec.tt_score(U, cand.vectors)
+
+    def _labels(self, users, cand, actual):
+        """The device label inputs of hrec_hybrid_model_f1 for the queried
+        `users` (ascending, distinct) from an `actual` frame (userId, itemId):
+        (label_rows int64 [n]: q, or -1 for a user without rows in `actual`;
+        indptr, cols: row q's distinct candidate FRAME ROW indices, ascending;
+        total int32 [n]: the user's distinct itemIds, inside the candidate
+        frame or not)."""
+        dev = self.twotower_model.model.device
+        au, ai = ranked_lists.int_ids(actual["userId"], "userId"), ranked_lists.int_ids(actual["itemId"], "itemId")
+        indptr, cols = ranked_lists.exclusion_csr(users, cand.item_ids, au, ai, dev,
+                                                  self.twotower_model.EXCLUSION_HOST_PAIRS,
+                                                  what="actual: userId and itemId")
+        total = ranked_lists.distinct_counts(users, au, ai, dev, self.RANKING_HOST_ROWS)
+        rows = torch.arange(int(users.size), dtype=torch.int64, device=dev)
+        return torch.where(total > 0, rows, torch.full_like(rows, -1)), indptr, cols, total
+
+    def _adaptive_device(self, users, cand, kk, excl, fallback, labels, f1_k, als_wins):
+        """Per sub-batch of `users`: both models' scores, hrec_hybrid_model_f1
+        (mode 0) over them and — kk > 0 — hrec_hybrid_lists_rowwise (mode 0)
+        with the weights the F1s just chose. All flags of both kinds are read
+        back once, after the last sub-batch. A sub-batch whose F1 flag is set
+        is redone whole (F1 in mode 1, the lists in mode 0 with their own flag
+        read, then in mode 1 if it is set); one with only the lists flag set
+        is redone in lists mode 1 with the weights it has. Returns device (f1
+        f64 [n, 2], wins int32 [n], idx, val, lens) (the last three None when
+        kk == 0)."""
+        dev = self.twotower_model.model.device
+        n, N = int(users.size), len(cand)
+        f1 = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        wins = torch.empty(n, dtype=torch.int32, device=dev)
+        idx = val = lens = None
+        if kk:
+            idx = torch.empty((n, kk), dtype=torch.int64, device=dev)
+            val = torch.empty((n, kk), dtype=torch.float64, device=dev)
+            lens = torch.empty(n, dtype=torch.int32, device=dev)
+            rows = torch.arange(n, dtype=torch.int64, device=dev)  # query q reads exclusion row q
+
+        def f1_pass(s, e, a, t, mode):
+            f, w, over = _hrec.hybrid_model_f1(a, t, f1_k, labels=(labels[0][s:e], *labels[1:]),
+                                               default_wins=als_wins, fallback=fallback, mode=mode)
+            f1[s:e], wins[s:e] = f, w
+            return over
+
+        def lists_pass(s, e, a, t, mode):
+            i, v, m, over = _hrec.hybrid_lists_rowwise(a, t, kk, wins[s:e], fallback=fallback,
+                                                       excl=None if excl is None else (rows[s:e], *excl), mode=mode)
+            idx[s:e], val[s:e], lens[s:e] = i, v, m
+            return over
+
+        spans = self._spans(0, n, N, 8)
+        flags = []
+        for s, e in spans:
+            a, t = self._scores(users[s:e], cand)
+            flags.append(f1_pass(s, e, a, t, 0))
+            if kk:
+                flags.append(lists_pass(s, e, a, t, 0))
+        flags = torch.cat(flags).tolist()  # one host read
+        per = 2 if kk else 1
+        for q, (s, e) in enumerate(spans):
+            f1_over, lists_over = flags[per * q], bool(kk) and flags[per * q + 1]
+            if not f1_over and not lists_over:
+                continue
+            for s1, e1 in self._spans(s, e, N, 16):
+                a, t = self._scores(users[s1:e1], cand)
+                if f1_over:
+                    f1_pass(s1, e1, a, t, 1)
+                    if kk and int(lists_pass(s1, e1, a, t, 0).item()):
+                        lists_pass(s1, e1, a, t, 1)
+                else:
+                    lists_pass(s1, e1, a, t, 1)
+        return f1, wins, idx, val, lens
+
+    def _recommend_device(self, users, cand, num, exclude=None, actual=None, f1_k=10):
         """Top-`num` fused candidates for each of `users` (TwoTowerModel.
         _query_users' array): device (raw itemIds int64 [n, kk], fused scores
         f64 [n, kk], lens int32 [n] or None when every list is full), kk =
         min(num, candidates). Past a list's length: id 0, score NaN. Users go
         through hrec_hybrid_lists in sub-batches (mode 0); the sub-batches
         whose overflow flag is set — read back once, after the last one — are
-        redone in mode 1."""
+        redone in mode 1. With `actual`: _adaptive_device, each user with
+        rows there fused by its own two F1@f1_k."""
         num = ranked_lists.check_num(num, self.RECOMMEND_MAX, "num_items")
-        tt, als = self.twotower_model, self.als_model
+        f1_k = ranked_lists.check_num(f1_k, self.RECOMMEND_MAX, "f1_k")
+        tt = self.twotower_model
         dev = tt.model.device
         n, N = int(users.size), len(cand)
         kk = min(num, N)
         if n == 0 or kk == 0:
             return ranked_lists.empty_lists(n, kk, torch.float64, dev, exclude is not None)
         excl = tt._exclusion(users, cand, exclude) if exclude is not None else None
-        keys = cand.item_ids
-        fallback = self._als_fallback(users, keys)
+        fallback = self._als_fallback(users, cand.item_ids)
         als_wins = self.als_f1_score > self.twotower_f1_score
+        if actual is not None:
+            _, _, idx, val, lens = self._adaptive_device(users, cand, kk, excl, fallback,
+                                                         self._labels(users, cand, actual), f1_k, als_wins)
+            ids, val = ranked_lists.pad_lists(cand.ids_dev, idx, val, lens, N)
+            return ids, val, (None if exclude is None else lens)
         rows = torch.arange(n, dtype=torch.int64, device=dev)  # query q reads exclusion row q
         idx = torch.empty((n, kk), dtype=torch.int64, device=dev)
         val = torch.empty((n, kk), dtype=torch.float64, device=dev)
         lens = torch.empty(n, dtype=torch.int32, device=dev)
 
         def run(s, e, mode):
-            a = als.model.score(users[s:e], keys)  # transform's f32, NaN where an id is unknown
-            U = tt.model.user_vectors(torch.as_tensor(users[s:e].astype(np.int32), device=dev))
-            t = _hrec.tt_score(U, cand.vectors)    # the bits predict_for_user gives
+            a, t = self._scores(users[s:e], cand)
             i, v, m, over = _hrec.hybrid_lists(a, t, kk, als_wins, fallback=fallback,
                                                excl=None if excl is None else (rows[s:e], *excl), mode=mode)
             idx[s:e], val[s:e], lens[s:e] = i, v, m
             return over
 
-        sub = max(1, min(self.RECOMMEND_ROWS, self.RECOMMEND_SCORE_BYTES // (8 * N)))
-        spans = [(s, min(s + sub, n)) for s in range(0, n, sub)]
+        spans = self._spans(0, n, N, 8)
         flagged = torch.cat([run(s, e, 0) for s, e in spans]).tolist()  # one host read
-        sub1 = max(1, min(self.RECOMMEND_ROWS, self.RECOMMEND_SCORE_BYTES // (16 * N)))
         for (s, e), over in zip(spans, flagged):
             if over:
-                for s1 in range(s, e, sub1):
-                    run(s1, min(s1 + sub1, e), 1)
+                for s1, e1 in self._spans(s, e, N, 16):
+                    run(s1, e1, 1)
         ids, val = ranked_lists.pad_lists(cand.ids_dev, idx, val, lens, N)
         return ids, val, (None if exclude is None else lens)
 
-    def recommend_for_users(self, users, item_features, num_items, exclude=None):
+    def recommend_for_users(self, users, item_features, num_items, exclude=None, actual=None, f1_k=10):
         """Top-n lists of the fused model for many users in one device pass:
         a DataFrame with `userId` (the distinct ids of `users`, ascending; a
         DataFrame with a userId column or an array-like) and `recommendations`:
@@ -397,42 +487,93 @@ class HybridRecommendationSystem:
         Non-finite scores: a row follows hrec_fuse_topk's arithmetic — NaN is
         ignored by the scalers and a NaN fused score ranks last, in frame
         order; the ValueError the per-user path raises for infinite scores is
-        not reproduced. One GPU; models not loaded raise ValueError."""
+        not reproduced. One GPU; models not loaded raise ValueError.
+        actual (optional): a DataFrame with userId and itemId columns (other
+        columns ignored, repeated pairs counting once, users outside the
+        query changing nothing): the known items of some users. A queried
+        user with rows there is fused with the weights ITS OWN two F1@f1_k
+        choose — what get_hybrid_recommendations(u, items, actual_ratings=
+        that user's items) does through evaluate_individual_models: each
+        model's own top f1_k (1 .. 1024) over ALL candidates (before and
+        independent of `exclude`, as the scalers are) against the user's
+        items, those outside the candidate frame counting in recall's
+        denominator; (0.8, 0.2) when the ALS F1 is strictly larger, else
+        (0.2, 0.8). Every other user keeps the instance's weights. The call
+        leaves als_f1_score / twotower_f1_score as they are (the reference
+        leaves the last evaluated user's scores there). Within a
+        model's top f1_k equal scores keep frame order and NaN scores rank
+        last in frame order; for non-finite two-tower scores the reference's
+        order is Python's unspecified one and is not reproduced."""
         self._require_models()
         cand = self.twotower_model.candidates(item_features)
         users = self.twotower_model._query_users(users)
-        ids, val, lens = self._recommend_device(users, cand, num_items, exclude)
+        ids, val, lens = self._recommend_device(users, cand, num_items, exclude, actual, f1_k)
         return ranked_lists.lists_frame("userId", users, ids, val, lens)
 
-    def recommend_for_all_users(self, item_features, num_items, exclude=None):
+    def recommend_for_all_users(self, item_features, num_items, exclude=None, actual=None, f1_k=10):
         """recommend_for_users for every user of the two-tower user table."""
         self._require_models()
         return self.recommend_for_users(np.arange(int(self.twotower_model.num_users), dtype=np.int64), item_features,
-                                        num_items, exclude)
+                                        num_items, exclude, actual, f1_k)
 
-    def ranking_metrics(self, data, item_features, k=10, label_col=None, min_rating=None, exclude=None):
+    def evaluate_models(self, data, item_features, k=10):
+        """evaluate_individual_models for every user of `data` (columns
+        userId, itemId) in one device pass: a DataFrame with `userId` (the
+        distinct users of `data`, ascending), `als_f1` and `twotower_f1`
+        (float64: compute_f1_score(that user's items, dict(model.
+        predict_for_user(u, item_features)), k) bit for bit, ties and NaN as
+        in recommend_for_users' `actual`) and `als_wins` (bool: als_f1 >
+        twotower_f1). k in 1 .. 1024. The instance's attributes are not
+        touched. Unknown ALS ids without a fallback vector raise ValueError, a
+        user id outside the two-tower table IndexError."""
+        self._require_models()
+        k = ranked_lists.check_num(k, self.RECOMMEND_MAX, "k")
+        cand = self.twotower_model.candidates(item_features)
+        users = self.twotower_model._query_users(data)
+        if users.size and len(cand):
+            f1, wins, *_ = self._adaptive_device(users, cand, 0, None, self._als_fallback(users, cand.item_ids),
+                                                 self._labels(users, cand, data), k, False)
+            f1, wins = f1.cpu().numpy(), wins.cpu().numpy() != 0
+        else:  # no candidate: every selection is empty
+            f1, wins = np.zeros((users.size, 2), np.float64), np.zeros(users.size, bool)
+        return pd.DataFrame({"userId": users, "als_f1": f1[:, 0], "twotower_f1": f1[:, 1], "als_wins": wins})
+
+    def fit_fusion_weights(self, data, item_features, k=10):
+        """Global weights from a validation frame: sets als_f1_score /
+        twotower_f1_score to np.mean of evaluate_models' two columns and
+        returns the pair. An empty `data` raises ValueError."""
+        scores = self.evaluate_models(data, item_features, k)
+        if len(scores) == 0:
+            raise ValueError("fit_fusion_weights: `data` holds no user")
+        self.als_f1_score = float(np.mean(scores["als_f1"].to_numpy()))
+        self.twotower_f1_score = float(np.mean(scores["twotower_f1"].to_numpy()))
+        return self.als_f1_score, self.twotower_f1_score
+
+    def ranking_metrics(self, data, item_features, k=10, label_col=None, min_rating=None, exclude=None, actual=None,
+                        f1_k=10):
         """Spark's RankingMetrics (binary relevance) of the fused model's top-k
         lists over `item_features` against `data` (columns userId, itemId):
         the five RANKING_METRIC_NAMES plus "count", with TwoTowerModel.
         ranking_metrics' semantics (ground truth = the user's itemIds in
         `data`, of the rows with label_col >= min_rating when given; each
         metric the mean over the `count` users, NaN when count is 0; each list
-        evaluated at its own length). exclude as in recommend_for_users. The
-        lists go from hrec_hybrid_lists into hrec_ranking_metrics without
+        evaluated at its own length). exclude, actual and f1_k as in
+        recommend_for_users. The lists go from hrec_hybrid_lists into hrec_ranking_metrics without
         leaving the device."""
         self._require_models()
         tt = self.twotower_model
         cand = tt.candidates(item_features)
         return ranked_lists.ranking_metrics(
             data, k, label_col, min_rating, tt.model.device, self.RANKING_HOST_ROWS, self.RANKING_METRIC_NAMES,
-            lambda users, k: self._recommend_device(tt._query_users(users), cand, k, exclude)[::2])
+            lambda users, k: self._recommend_device(tt._query_users(users), cand, k, exclude, actual, f1_k)[::2])
 
     def evaluate_ranking(self, data, item_features, metric_name="meanAveragePrecision", k=10, label_col=None,
-                         min_rating=None, exclude=None):
+                         min_rating=None, exclude=None, actual=None, f1_k=10):
         """Spark's RankingEvaluator(metricName=metric_name, k=k).evaluate of
         the fused model's lists for the users of `data` (a float)."""
         ranked_lists.check_metric_name(metric_name, self.RANKING_METRIC_NAMES)
-        return float(self.ranking_metrics(data, item_features, k, label_col, min_rating, exclude)[metric_name])
+        return float(self.ranking_metrics(data, item_features, k, label_col, min_rating, exclude, actual,
+                                          f1_k)[metric_name])
 
     def cleanup(self):
         if self.als_model:

@@ -104,6 +104,28 @@ def exclusion_csr(row_keys, col_keys, excl_rows, excl_cols, dev, host_pairs, col
     return exclusion_csr_device(row_keys, col_keys, excl_rows, excl_cols, dev, cols_sorted, what)
 
 
+def distinct_counts(row_keys, pair_rows, pair_items, dev, host_rows):
+    """int32 device [len(row_keys)]: how many distinct items the (row, item)
+    pairs give row_keys[q] (int64, ascending, distinct; items fit 32 bits:
+    int_ids'). Pairs with a row outside row_keys are dropped. On the host up
+    to host_rows pairs, on the device above."""
+    n = int(np.asarray(row_keys).size)
+    if n == 0 or np.asarray(pair_rows).size == 0:
+        return torch.zeros(n, dtype=torch.int32, device=dev)
+    if np.asarray(pair_rows).size <= host_rows:
+        rk, pr, pi = (np.asarray(a, np.int64).reshape(-1) for a in (row_keys, pair_rows, pair_items))
+        pos = np.minimum(np.searchsorted(rk, pr), n - 1)
+        ok = rk[pos] == pr
+        key = np.unique((pos[ok] << 32) | (pi[ok] + (1 << 31)))  # one key per distinct (row, item)
+        return torch.as_tensor(np.bincount(key >> 32, minlength=n).astype(np.int32), device=dev)
+    rk, pr, pi = (torch.as_tensor(a, dtype=torch.int64, device=dev).reshape(-1)
+                  for a in (row_keys, pair_rows, pair_items))
+    pos = torch.searchsorted(rk, pr).clamp_(max=n - 1)
+    ok = rk[pos] == pr
+    key = torch.unique((pos[ok] << 32) | (pi[ok] + (1 << 31)))
+    return torch.bincount(key >> 32, minlength=n).to(torch.int32)
+
+
 # ---------------------------------------------------------------- label CSR
 def label_csr_host(users, items, dev):
     """(distinct users, indptr, labels) of the (user, item) rows, int64

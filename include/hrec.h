@@ -24,6 +24,10 @@
  *   Python/sklearn fusion     src/hybrid_system.py:57-75,108 -> hrec_fuse_topk
  *          the same for many users, minus seen pairs
  *          (no reference line)                        -> hrec_hybrid_lists
+ *   Python evaluate_individual_models (F1@10 per model chooses the user's
+ *          weights) src/hybrid_system.py:42-55, for many
+ *          users                                       -> hrec_hybrid_model_f1,
+ *                                                          hrec_hybrid_lists_rowwise
  *   Keras  two-tower graph    src/two_tower_model.py:38-89 -> hrec_tt_*
  *   Keras  Dot + sorted(...)[:k] for many users        -> hrec_dot_topk
  *          the same minus a training frame's pairs
@@ -567,6 +571,57 @@ int hrec_hybrid_lists(const float* als, const float* tt, int64_t n_rows, int64_t
                       const int32_t* excl_cols, int64_t* out_idx, double* out_val,
                       int32_t* out_len, double* out_minmax, int* overflow, void* workspace,
                       size_t workspace_bytes, void* stream);
+/* hrec_hybrid_lists with the fusion weights chosen per row (additive to ABI
+ * 7): row r fuses with (0.8, 0.2) when row_wins[r] != 0 and with (0.2, 0.8)
+ * otherwise (row_wins: [n_rows] int32, device, not NULL). Everything else —
+ * the arguments, their checks, the modes, the outputs' bits and the
+ * workspace (hrec_hybrid_lists_workspace_bytes) — is hrec_hybrid_lists'; a
+ * constant row_wins gives hrec_hybrid_lists(als_wins = that constant). */
+int hrec_hybrid_lists_rowwise(const float* als, const float* tt, int64_t n_rows, int64_t n,
+                              int64_t ld, const double* als_fallback, const int32_t* row_wins,
+                              int top_k, int mode, const int64_t* excl_rows,
+                              const int64_t* excl_indptr, const int32_t* excl_cols,
+                              int64_t* out_idx, double* out_val, int32_t* out_len,
+                              double* out_minmax, int* overflow, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
+/* Per-row, per-model F1@k (additive to ABI 7): the batch form of the
+ * reference's evaluate_individual_models, which chooses the fusion weights of
+ * one user. als / tt / ld / als_fallback / n_rows as for hrec_hybrid_lists; k
+ * in [1, 1024]; mode 0 or 1. Per row r and model, the selection is the first
+ * min(k, n) columns of the stable descending ranking of the model's keys
+ * (equal keys keep column order, NaN last in column order): ALS keys are the
+ * f64 values a_rj of hrec_hybrid_lists, two-tower keys the f32 scores — the
+ * order sorted(dict(preds).items(), key=score, reverse=True)[:k] gives
+ * predict_for_user's list over a frame of distinct ids. Then, in f64 and in
+ * compute_f1_score's operation order: tp = the row's labels found in the
+ * selection, p = tp / k (k as passed, also when n < k), r = tp / total,
+ * f1 = (p + r > 0) ? 2 * (p * r) / (p + r) : 0.
+ * Labels (a CSR shaped like the exclusion CSR): row r's candidate labels are
+ * label_cols[label_indptr[q] .. label_indptr[q + 1]) with q = label_rows[r]
+ * (q < 0: a row without labels), column indices ascending and distinct;
+ * label_total[q] (int32) is the size of the user's whole ground-truth set, >=
+ * the number of its labels that are candidates. All four NULL: no row has
+ * labels.
+ * out_f1 [n_rows][2] = (ALS, two-tower); out_wins [n_rows] = f1_als > f1_tt;
+ * out_top (optional) [n_rows][2][min(k, n)] = the two selections' columns. A
+ * row with q < 0 or label_total[q] == 0 gets NaN for both F1s and out_wins =
+ * (default_wins != 0).
+ * mode 0 (bounded): per model, the row's first HREC_HYBRID_LISTS_SAMPLE
+ * columns give a lower bound of the selection's last key; one pass over both
+ * matrices appends the columns reaching it to a list of
+ * HREC_HYBRID_LISTS_CAP entries per row and model. *overflow = 1 when some
+ * list had more: the answer is then incomplete and the caller repeats the
+ * call with mode 1. n <= HREC_HYBRID_LISTS_SAMPLE never overflows. mode 1
+ * (full): both key rows are written to the workspace (>= 16 * n_rows * n
+ * bytes) and ranked; always complete, *overflow = 0. */
+size_t hrec_hybrid_model_f1_workspace_bytes(int64_t n_rows, int64_t n, int k, int mode);
+int hrec_hybrid_model_f1(const float* als, const float* tt, int64_t n_rows, int64_t n, int64_t ld,
+                         const double* als_fallback, int k, int mode, const int64_t* label_rows,
+                         const int64_t* label_indptr, const int32_t* label_cols,
+                         const int32_t* label_total, int default_wins, double* out_f1,
+                         int32_t* out_wins, int64_t* out_top, int* overflow, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------ cold-start sim --
  * ALSModel._find_similar_items (src/als_model.py:93-104): out[q*n_items+j] =
