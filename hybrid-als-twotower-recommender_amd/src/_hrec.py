@@ -98,6 +98,9 @@ _SIGNATURES = {
     "hrec_hybrid_model_f1_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i32, _c_i32]),
     "hrec_hybrid_model_f1": (_c_i32, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _c_i32, _vp, _vp, _vp, _vp,
                                       _c_i32, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "hrec_user_metrics_workspace_bytes": (_c_sz, [_c_i64]),
+    "hrec_user_metrics": (_c_i32, [_vp, _c_i64, _c_i32, _vp, _c_i64, _c_i64, _vp, _c_i32, _c_i32, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _c_i32, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
     "hrec_fuse_workspace_bytes": (_c_sz, [_c_i64, _c_i32]),
     "hrec_fuse_topk": (_c_i32, [_vp, _vp, _c_i32, _c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp,
                                 _c_sz, _vp]),
@@ -1642,6 +1645,127 @@ def hybrid_model_f1(als, tt, k, labels=None, default_wins=False, fallback=None, 
         _dev(ws, torch.uint8, "ws"), need, _stream()))
     res = (f1, wins, overflow)
     return res + (top,) if want_top else res
+
+
+# ------------------------------------------------ per-user reference metrics
+UM_MAX_K = 8       # HREC_UM_MAX_K: k values of one hrec_user_metrics call
+UM_LIST_MAX = 1024  # largest k, ndcg_k and list length
+UM_SOURCES = {"f64": 0, "f32": 1, "als": 2, "fused": 3}  # HREC_UM_SRC_*
+# bit b of user_metrics' status (HREC_UM_* of include/hrec.h)
+UM_STATUS = ("ndcg_undefined", "err_undefined", "no_common", "no_relevant", "no_ratings")
+UM_NDCG_UNDEFINED, UM_ERR_UNDEFINED, UM_NO_COMMON, UM_NO_RELEVANT, UM_NO_RATINGS = 1, 2, 4, 8, 16
+
+
+def um_columns(k_values):
+    """The columns of user_metrics' per_row, in order (the reference's result keys)."""
+    return ([f"Precision@{int(k)}" for k in k_values] + [f"Recall@{int(k)}" for k in k_values]
+            + ["NDCG", "MAE", "RMSE"])
+
+
+def um_sums(k_values):
+    """The slots of user_metrics' sums, in order: per column its sum over the rows
+    where it is defined, per column the count of those rows, per status bit its rows."""
+    cols = um_columns(k_values)
+    return tuple([f"sum_{c}" for c in cols] + [f"n_{c}" for c in cols] + [f"n_{s}" for s in UM_STATUS])
+
+
+def um_discounts(ndcg_k):
+    """The host table hrec_user_metrics reads (numpy f64, ndcg_k + 1 entries): 0, then the
+    running sums of sklearn's discount 1 / (ln(i + 2) / ln 2), i < ndcg_k, added in
+    order (cumsum is sequential)."""
+    d = 1.0 / (np.log(np.arange(int(ndcg_k), dtype=np.float64) + 2.0) / np.log(2.0))
+    return np.concatenate([np.zeros(1), np.cumsum(d)])
+
+
+def _rows_matrix(name, what, t, dtype, n_rows):
+    """(pointer, row stride) of a 2-D device tensor with unit column stride (a
+    view with a larger row stride is taken as it is)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or t.dim() != 2:
+        raise HrecError(f"{name}: {what} must be a 2-D {dtype} device tensor")
+    if t.shape[0] != n_rows:
+        raise HrecError(f"{name}: {what} must hold one row per list")
+    if t.shape[1] == 0:
+        return None, t, 0
+    if t.stride(1) != 1 or (n_rows > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return _vp(t.data_ptr()), t, (int(t.stride(0)) if n_rows > 1 else int(t.shape[1]))
+
+
+def user_metrics(ranked, k_values, actual, scores, source=None, ndcg_k=10, list_len=None, tt=None, fallback=None,
+                 minmax=None, row_wins=None):
+    """hrec_user_metrics: the reference RecommenderEvaluator's per-user
+    Precision@k / Recall@k (each k of k_values, at most UM_MAX_K), NDCG@ndcg_k,
+    MAE and RMSE for every row. ranked: int64 [n_rows, L <= 1024] device (a
+    view with a row stride is fine), row r's candidate columns best first in
+    its first list_len[r] (int32 [n_rows]; None: L) entries. actual = (rows
+    int64 [n_rows] (-1: no ratings), indptr int64, cols int32 (each rated
+    item's candidate column, ascending, -1 outside the frame), ratings f64
+    aligned with cols, frame f64: the ratings in frame order), or None.
+    scores [n_rows, n]: f64 (source "f64") or f32 ("f32": np.float32
+    semantics; "als": the ALS matrix with `fallback`; "fused": with tt,
+    fallback, minmax [n_rows, 4] and row_wins int32 [n_rows] of the lists
+    call); source None: by dtype. Returns device (per_row f64 [n_rows,
+    2 * n_k + 3] in um_columns' order, status int32 [n_rows], sums f64
+    [len(um_sums(k_values))]). The same bits on every call."""
+    name = "user_metrics"
+    ks = [int(k) for k in k_values]
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 2:
+        raise HrecError(f"{name}: scores must be a 2-D device tensor")
+    n_rows, n = (int(x) for x in scores.shape)
+    dev = scores.device
+    if source is None:
+        source = "f32" if scores.dtype == torch.float32 else "f64"
+    if source not in UM_SOURCES:
+        raise HrecError(f"{name}: source must be one of {sorted(UM_SOURCES)}")
+    s_ptr, scores, ld = _rows_matrix(name, "scores", scores, torch.float64 if source == "f64" else torch.float32, n_rows)
+    r_ptr, ranked, r_ld = _rows_matrix(name, "ranked", ranked, torch.int64, n_rows)
+    list_n = int(ranked.shape[1])
+    if r_ptr is None:  # empty lists: a stand-in column, never read
+        stand_in = torch.zeros((max(n_rows, 1), 1), dtype=torch.int64, device=dev)
+        r_ptr, r_ld = _vp(stand_in.data_ptr()), 1
+    t_ptr = None
+    if source == "fused":
+        t_ptr, tt, t_ld = _rows_matrix(name, "tt", tt, torch.float32, n_rows)
+        if tuple(tt.shape) != (n_rows, n) or (n_rows > 1 and t_ld != ld):
+            raise HrecError(f"{name}: scores and tt need the same shape and row stride")
+        if minmax is None or tuple(minmax.shape) != (n_rows, 4) or row_wins is None or row_wins.numel() != n_rows:
+            raise HrecError(f"{name}: the fused source needs minmax [n_rows, 4] and row_wins [n_rows]")
+    if fallback is not None and fallback.numel() != n:
+        raise HrecError(f"{name}: fallback must hold one value per column")
+    if list_len is not None and list_len.numel() != n_rows:
+        raise HrecError(f"{name}: list_len must have one entry per row")
+    if actual is not None:
+        rows, indptr, cols, ratings, frame = actual
+        if rows.numel() != n_rows:
+            raise HrecError(f"{name}: act_rows must hold one entry per row")
+        if cols.numel() != ratings.numel() or cols.numel() != frame.numel():
+            raise HrecError(f"{name}: act_cols, act_ratings and act_frame must have the same length")
+        if cols.numel() == 0:  # stand-in entries, never read
+            cols = torch.zeros(1, dtype=torch.int32, device=dev)
+            ratings = frame = torch.zeros(1, dtype=torch.float64, device=dev)
+        act_args = (_dev(rows, torch.int64, "act_rows"), _dev(indptr, torch.int64, "act_indptr"),
+                    _dev(cols, torch.int32, "act_cols"), _dev(ratings, torch.float64, "act_ratings"),
+                    _dev(frame, torch.float64, "act_frame"))
+    else:
+        act_args = (None,) * 5
+    n_k = len(ks)
+    ncol = 2 * n_k + 3
+    k_arr = (ctypes.c_int32 * max(n_k, 1))(*ks)
+    cs_h = um_discounts(ndcg_k) if 1 <= int(ndcg_k) <= UM_LIST_MAX else np.zeros(2)  # the library rejects ndcg_k
+    cs = torch.as_tensor(cs_h, device=dev)
+    per_row = torch.empty((n_rows, ncol), dtype=torch.float64, device=dev)
+    status = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    sums = torch.zeros(2 * ncol + len(UM_STATUS), dtype=torch.float64, device=dev)
+    need = int(lib().hrec_user_metrics_workspace_bytes(n_rows))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    _check("hrec_user_metrics", lib().hrec_user_metrics(
+        r_ptr, r_ld, list_n, _dev(list_len, torch.int32, "list_len"), n_rows, n, ctypes.cast(k_arr, _vp), n_k,
+        int(ndcg_k), _dev(cs, torch.float64, "disc_cs"), *act_args, UM_SOURCES[source], s_ptr, t_ptr, ld,
+        _dev(fallback, torch.float64, "fallback"), _dev(minmax, torch.float64, "minmax"),
+        _dev(row_wins, torch.int32, "row_wins"), _dev(per_row, torch.float64, "per_row"),
+        _dev(status, torch.int32, "status"), _dev(sums, torch.float64, "sums"), _dev(ws, torch.uint8, "ws"), need,
+        _stream()))
+    return per_row, status, sums
 
 
 # ------------------------------------------------------- multi-GPU (C-ABI)

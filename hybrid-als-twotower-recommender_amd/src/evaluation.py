@@ -20,6 +20,12 @@ produced by executing the reference):
   * NDCG on a single common item and MAE/RMSE on constant ratings raise
     ValueError (sklearn rejects one document / NaN).
 Plotting needs matplotlib/seaborn, which this build does not ship.
+
+Not in the reference (failures raise): `evaluate_scores`, the same
+metrics for every user of a score matrix in one device pass (`_hrec.topk`
+followed by hrec_user_metrics), `summarize`, and the helpers
+HybridRecommendationSystem.evaluate_users shares with it (the actual-ratings
+CSR, the result frame).
 """
 import os
 
@@ -59,8 +65,166 @@ def _common(actual_ratings, predicted_scores):
     return ([actual_ratings[i] for i in common], [predicted_scores[i] for i in common]) if common else None
 
 
+# ------------------------------------------------- batched evaluation
+EVALUATE_ROWS = 65535  # rows of one hrec_user_metrics / hrec_topk call
+
+
+def metric_columns(k_values):
+    """The batched frames' metric columns in the order of comprehensive_evaluation's keys."""
+    cols = []
+    for k in k_values:
+        cols += [f"Precision@{int(k)}", f"Recall@{int(k)}"]
+    return cols + ["NDCG", "MAE", "RMSE"]
+
+
+def check_k_values(k_values, ndcg_k):
+    ks = [int(k) for k in k_values]
+    if not 1 <= len(ks) <= _hrec.UM_MAX_K:
+        raise ValueError(f"k_values must hold 1 .. {_hrec.UM_MAX_K} values (got {len(ks)})")
+    for k in ks + [int(ndcg_k)]:
+        if not 1 <= k <= _hrec.UM_LIST_MAX:
+            raise ValueError(f"k_values and ndcg_k must be in [1, {_hrec.UM_LIST_MAX}] (got {k})")
+    return ks, int(ndcg_k)
+
+
+def actual_csr(data, users, item_ids, rating_col="average_review_rating"):
+    """The host arrays of hrec_user_metrics' actual CSR for `users` (int64,
+    ascending, distinct) over the candidate ids `item_ids` (int64, distinct,
+    frame order) from `data` (columns userId, itemId, rating_col): (rows int64
+    [len(users)]: q, or -1 for a user without rows in `data`; indptr int64
+    [len(users) + 1]; cols int32: each rated item's candidate column,
+    ascending per user, -1 outside the frame; ratings f64 aligned with cols;
+    frame f64: the user's ratings in frame order). Rows of other users are
+    ignored. A (userId, itemId) pair held twice raises ValueError (the
+    reference's dict(zip(...)) would silently keep the last one)."""
+    from .ranked_lists import int_ids
+
+    du, di = int_ids(data["userId"], "userId"), int_ids(data["itemId"], "itemId")
+    r = np.asarray(data[rating_col], dtype=np.float64)
+    users, item_ids = np.asarray(users, np.int64), np.asarray(item_ids, np.int64)
+    n = users.size
+    indptr = np.zeros(n + 1, np.int64)
+    if n == 0 or du.size == 0:
+        return np.full(n, -1, np.int64), indptr, np.zeros(0, np.int32), np.zeros(0), np.zeros(0)
+    q = np.minimum(np.searchsorted(users, du), n - 1)
+    keep = users[q] == du
+    q, di, r = q[keep], di[keep], r[keep]
+    if q.size == 0:
+        return np.full(n, -1, np.int64), indptr, np.zeros(0, np.int32), np.zeros(0), np.zeros(0)
+    by_user = np.argsort(q, kind="stable")  # frame order within a user
+    q, di, r = q[by_user], di[by_user], r[by_user]
+    if item_ids.size:
+        sorter = np.argsort(item_ids, kind="stable")
+        p = np.minimum(np.searchsorted(item_ids[sorter], di), item_ids.size - 1)
+        col = np.where(item_ids[sorter][p] == di, sorter[p], -1)
+    else:
+        col = np.full(di.size, -1, np.int64)
+    # one int64 key per pair (ids fit 32 bits: int_ids; q < 2^31)
+    pair = np.sort(q * (1 << 32) + (di - di.min()))
+    if pair.size > 1 and np.any(pair[1:] == pair[:-1]):
+        raise ValueError("data holds a (userId, itemId) pair more than once: a user's ratings must be one per item")
+    # by user, then by column; stable: items outside the frame (-1) first, in frame order
+    by_col = np.argsort(q * (item_ids.size + 1) + (col + 1), kind="stable")
+    counts = np.bincount(q, minlength=n)
+    np.cumsum(counts, out=indptr[1:])
+    rows = np.where(counts > 0, np.arange(n, dtype=np.int64), -1)
+    return rows, indptr, col[by_col].astype(np.int32), r[by_col], r
+
+
+def actual_csr_device(data, users, item_ids, rating_col, dev):
+    """actual_csr as device tensors, and the host mask of the users that have rows."""
+    rows, indptr, cols, ratings, frame = actual_csr(data, users, item_ids, rating_col)
+    return tuple(torch.as_tensor(a, device=dev) for a in (rows, indptr, cols, ratings, frame)), rows >= 0
+
+
+def metrics_frame(users, per_row, status, k_values, has_rows):
+    """The batched result: userId (the users with rows, ascending), the
+    reference's result keys and the row's status bits (_hrec.UM_STATUS)."""
+    import pandas as pd
+
+    per_row, status = np.asarray(per_row)[has_rows], np.asarray(status)[has_rows]
+    native = _hrec.um_columns(k_values)
+    frame = {"userId": np.asarray(users)[has_rows]}
+    for name in metric_columns(k_values):
+        frame[name] = per_row[:, native.index(name)]
+    frame["status"] = status.astype(np.int32)
+    return pd.DataFrame(frame)
+
+
 class RecommenderEvaluator:
     """src/evaluation.py:19 — same methods and return values."""
+
+    @staticmethod
+    def evaluate_scores(data, scores, user_ids, item_ids, k_values=(5, 10, 15, 20), ndcg_k=10,
+                        rating_col="average_review_rating"):
+        """The per-user methods above for many users in one device pass (not
+        in the reference): `scores` [len(user_ids), len(item_ids)] (f32 or f64,
+        array or device tensor) holds user_ids[i]'s predicted score of
+        item_ids[j]; `data` (columns userId, itemId, rating_col) the actual
+        ratings, each (userId, itemId) once (else ValueError). Returns a
+        DataFrame with `userId` (the users of `data` that are in user_ids,
+        ascending), `Precision@k` and `Recall@k` per k of k_values (at most 8,
+        each in 1 .. 1024), `NDCG` (at ndcg_k), `MAE`, `RMSE` and `status`.
+        A row equals precision_at_k / recall_at_k / ndcg_at_k / mae_rmse of
+        (actual = {itemId: rating} of the user's rows in frame order,
+        predicted = {item_ids[j]: scores[i, j]}): Precision and Recall
+        exactly, the others to the summation order. f32 scores follow the
+        np.float32 arithmetic of the per-user path, f64 scores its Python
+        float arithmetic. Where the per-user methods raise ValueError (NDCG
+        with one common item; MAE / RMSE with one common item, constant
+        ratings or scores, a NaN score) the value is NaN and the bit of
+        `status` is set (_hrec.UM_STATUS names the bits). The F1_Score entry
+        of comprehensive_evaluation, which raises in the reference, has no
+        column. The ranking is the device's stable top-k (equal scores keep
+        item_ids order, NaN last) followed by hrec_user_metrics."""
+        ks, ndcg_k = check_k_values(k_values, ndcg_k)
+        _hrec.require_device()
+        uid = np.asarray(user_ids).reshape(-1).astype(np.int64)
+        iid = np.asarray(item_ids).reshape(-1).astype(np.int64)
+        if np.unique(uid).size != uid.size or np.unique(iid).size != iid.size:
+            raise ValueError("evaluate_scores: user_ids and item_ids must not repeat an id")
+        s = scores if isinstance(scores, torch.Tensor) else torch.as_tensor(np.asarray(scores))
+        if s.dtype not in (torch.float32, torch.float64):
+            s = s.to(torch.float64)
+        if s.dim() != 2 or tuple(s.shape) != (uid.size, iid.size):
+            raise ValueError("evaluate_scores: scores must be [len(user_ids), len(item_ids)]")
+        if iid.size == 0:
+            raise ValueError("evaluate_scores: no candidate item")
+        s = s.cuda()
+        dev = s.device
+        order = np.argsort(uid, kind="stable")
+        users = uid[order]
+        (rows, *csr), has_rows = actual_csr_device(data, users, iid, rating_col, dev)
+        inverse = np.empty_like(order)
+        inverse[order] = np.arange(order.size)
+        rows = rows[torch.as_tensor(inverse, device=dev)]  # score row i is user uid[i]
+        kk = min(max(ks), iid.size)
+        out = []
+        for lo in range(0, uid.size, EVALUATE_ROWS):
+            part = s[lo: lo + EVALUATE_ROWS]
+            ranked, _ = _hrec.topk(part if part.is_contiguous() else part.contiguous(), kk)
+            per_row, status, _ = _hrec.user_metrics(ranked, ks, (rows[lo: lo + EVALUATE_ROWS], *csr), part,
+                                                    ndcg_k=ndcg_k)
+            out.append(torch.cat([per_row, status.double().unsqueeze(1)], dim=1))
+        ncol = 2 * len(ks) + 3
+        host = (torch.cat(out) if out else torch.zeros((0, ncol + 1), dtype=torch.float64)).cpu().numpy()[order]
+        return metrics_frame(users, host[:, :ncol], host[:, ncol], ks, has_rows)
+
+    @staticmethod
+    def summarize(frame):
+        """Per metric column of an evaluate_scores / evaluate_users frame: its
+        mean over the users where it is defined (not NaN) and their count, as
+        a DataFrame indexed by metric with columns `mean` and `count`."""
+        import pandas as pd
+
+        names = [c for c in frame.columns if c not in ("userId", "status")]
+        means, counts = [], []
+        for c in names:
+            v = frame[c].to_numpy(dtype=np.float64)
+            n = int(np.sum(~np.isnan(v)))
+            means.append(float(np.nanmean(v)) if n else float("nan"))
+            counts.append(n)
+        return pd.DataFrame({"mean": means, "count": counts}, index=pd.Index(names, name="metric"))
 
     def __init__(self):
         from sklearn.preprocessing import MinMaxScaler

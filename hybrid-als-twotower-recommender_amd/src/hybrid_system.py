@@ -19,6 +19,9 @@ fused scores keep candidate-frame order there, not the set order above.
 With actual= those four fuse each user by its own F1@k (DESIGN §23:
 hrec_hybrid_model_f1, hrec_hybrid_lists_rowwise); evaluate_models /
 fit_fusion_weights are the batch form of evaluate_individual_models.
+evaluate_users is the batch form of the reference's evaluation loop
+(RecommenderEvaluator's metrics of all three models per user; DESIGN §24:
+hrec_user_metrics over the same scores and lists).
 """
 import itertools
 import os
@@ -548,6 +551,103 @@ class HybridRecommendationSystem:
         self.als_f1_score = float(np.mean(scores["als_f1"].to_numpy()))
         self.twotower_f1_score = float(np.mean(scores["twotower_f1"].to_numpy()))
         return self.als_f1_score, self.twotower_f1_score
+
+    EVALUATE_MODELS = ("als", "twotower", "hybrid")
+
+    def evaluate_users(self, data, item_features, k_values=(5, 10, 15, 20), ndcg_k=10,
+                       models=EVALUATE_MODELS, actual=None, f1_k=10,
+                       rating_col="average_review_rating"):
+        """The reference's evaluation protocol (RecommenderEvaluator's
+        Precision@k / Recall@k, NDCG, MAE, RMSE; reproduce_results.sh loops
+        over the test users for it) for every user of `data` (columns userId,
+        itemId, rating_col; each pair once, else ValueError) in one device
+        pass: {model: DataFrame} for each of `models`, with the columns of
+        RecommenderEvaluator.evaluate_scores. A user's row is what the
+        per-user methods return for actual = {itemId: rating} of its rows in
+        frame order and predicted = dict(als_model.predict_for_user(u, ids)) /
+        dict(twotower_model.predict_for_user(u, frame)) / dict(adaptive_fusion
+        (those two)) over `item_features`: ALS and fused scores as f64, the
+        two-tower's as np.float32. Per sub-batch both models' scores are
+        computed once; hrec_hybrid_model_f1 gives each model's own top max(k),
+        hrec_hybrid_lists_rowwise the fused lists and scaler extremes, and
+        hrec_user_metrics runs once per model; scores and lists stay on the
+        device and one host read returns the tables.
+        actual / f1_k: as in recommend_for_users — a user with rows in
+        `actual` is fused with the weights its own two F1@f1_k choose, every
+        other user (all of them without `actual`) with the instance's.
+        Cold ALS ids use the cold-start vector; without it they raise
+        ValueError, as the lists do. Ties among fused scores keep
+        candidate-frame order, not the reference's set order. No exclusion:
+        the reference's metrics are taken over all candidates. One GPU."""
+        from . import evaluation as ev
+
+        self._require_models()
+        ks, ndcg_k = ev.check_k_values(k_values, ndcg_k)
+        f1_k = ranked_lists.check_num(f1_k, self.RECOMMEND_MAX, "f1_k")
+        models = tuple(models)
+        for m in models:
+            if m not in self.EVALUATE_MODELS:
+                raise ValueError(f"models must be among {self.EVALUATE_MODELS} (got {m!r})")
+        tt = self.twotower_model
+        dev = tt.model.device
+        cand = tt.candidates(item_features)
+        users = tt._query_users(data)
+        n, N = int(users.size), len(cand)
+        if N == 0:
+            raise ValueError("evaluate_users: the candidate frame is empty")
+        (act_rows, *csr), has_rows = ev.actual_csr_device(data, users, cand.item_ids, rating_col, dev)
+        ncol = 2 * len(ks) + 3
+        if n == 0 or not models:
+            return {m: ev.metrics_frame(users, np.zeros((n, ncol)), np.zeros(n), ks, has_rows) for m in models}
+        kmax = max(ks)
+        fallback = self._als_fallback(users, cand.item_ids)
+        als_wins = self.als_f1_score > self.twotower_f1_score
+        labels = self._labels(users, cand, actual) if actual is not None else None
+        want_top = "als" in models or "twotower" in models
+        want_fused = "hybrid" in models
+        out = torch.empty((len(models), n, ncol + 1), dtype=torch.float64, device=dev)
+
+        def run(s, e, mode):
+            a, t = self._scores(users[s:e], cand)
+            flags, top, wins = [], None, None
+            lab = None if labels is None else (labels[0][s:e], *labels[1:])
+            if want_fused and lab is not None and f1_k != kmax:  # the weights' own k
+                _, wins, over = _hrec.hybrid_model_f1(a, t, f1_k, labels=lab, default_wins=als_wins,
+                                                      fallback=fallback, mode=mode)
+                flags.append(over)
+            if lab is None and not want_top:  # the instance's weights for every row
+                wins = torch.full((e - s,), int(als_wins), dtype=torch.int32, device=dev)
+            if want_top or (want_fused and wins is None):
+                _, w, over, top = _hrec.hybrid_model_f1(a, t, kmax, labels=lab, default_wins=als_wins,
+                                                        fallback=fallback, mode=mode, want_top=True)
+                wins = w if wins is None else wins
+                flags.append(over)
+            rows = (act_rows[s:e], *csr)
+            if want_fused:
+                idx, _, lens, over, mm = _hrec.hybrid_lists_rowwise(a, t, kmax, wins, fallback=fallback, mode=mode,
+                                                                    want_minmax=True)
+                flags.append(over)
+            for i, m in enumerate(models):
+                if m == "als":
+                    res = _hrec.user_metrics(top[:, 0, :], ks, rows, a, source="als", ndcg_k=ndcg_k,
+                                             fallback=fallback)
+                elif m == "twotower":
+                    res = _hrec.user_metrics(top[:, 1, :], ks, rows, t, source="f32", ndcg_k=ndcg_k)
+                else:
+                    res = _hrec.user_metrics(idx, ks, rows, a, source="fused", ndcg_k=ndcg_k, list_len=lens, tt=t,
+                                             fallback=fallback, minmax=mm, row_wins=wins)
+                out[i, s:e, :ncol], out[i, s:e, ncol] = res[0], res[1].double()
+            return torch.cat(flags).sum().view(1)
+
+        spans = self._spans(0, n, N, 8)
+        flagged = torch.cat([run(s, e, 0) for s, e in spans]).tolist()  # one host read
+        for (s, e), over in zip(spans, flagged):
+            if over:
+                for s1, e1 in self._spans(s, e, N, 16):
+                    run(s1, e1, 1)  # mode 1 ranks every key: its flags are always 0
+        host = out.cpu().numpy()  # one host read: the per-row tables
+        return {m: ev.metrics_frame(users, host[i, :, :ncol], host[i, :, ncol], ks, has_rows)
+                for i, m in enumerate(models)}
 
     def ranking_metrics(self, data, item_features, k=10, label_col=None, min_rating=None, exclude=None, actual=None,
                         f1_k=10):

@@ -28,6 +28,9 @@
  *          weights) src/hybrid_system.py:42-55, for many
  *          users                                       -> hrec_hybrid_model_f1,
  *                                                          hrec_hybrid_lists_rowwise
+ *   Python RecommenderEvaluator (Precision@k / Recall@k, NDCG, MAE, RMSE
+ *          per user) src/evaluation.py:19-149, for many
+ *          users                                       -> hrec_user_metrics
  *   Keras  two-tower graph    src/two_tower_model.py:38-89 -> hrec_tt_*
  *   Keras  Dot + sorted(...)[:k] for many users        -> hrec_dot_topk
  *          the same minus a training frame's pairs
@@ -622,6 +625,97 @@ int hrec_hybrid_model_f1(const float* als, const float* tt, int64_t n_rows, int6
                          const int32_t* label_total, int default_wins, double* out_f1,
                          int32_t* out_wins, int64_t* out_top, int* overflow, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+/* Per-user evaluation by the reference's own protocol (additive to ABI 7):
+ * RecommenderEvaluator's Precision@k / Recall@k, NDCG, MAE and RMSE
+ * (src/evaluation.py:19-149) for every row of a batch, from ranked lists and
+ * scores that are already on the device. Row r's result is what the per-user
+ * methods return for (actual, predicted) with actual = {itemId: rating} of the
+ * user's rows in frame order and predicted = the row's scores over the n
+ * candidates in candidate order.
+ * Lists: ranked[r * ranked_ld + i], i < len_r = list_len ? list_len[r]
+ * (clamped to [0, list_n]) : list_n, are row r's candidate columns, best
+ * first: the stable descending ranking of the row's scores (equal scores keep
+ * column order, NaN last) cut to min(max k, n) or longer — hrec_hybrid_lists'
+ * out_idx, a model's half of hrec_hybrid_model_f1's out_top (ranked_ld = 2 *
+ * kk), or a hrec_topk_* result. 0 <= list_n <= 1024, ranked_ld >= list_n; a
+ * column outside [0, n) hits nothing.
+ * Actual ratings (a CSR shaped like the exclusion CSR): row r's user is q =
+ * act_rows[r] (q < 0, or all five pointers NULL: a row without ratings), its
+ * segment [act_indptr[q], act_indptr[q + 1]). act_cols holds the candidate
+ * column of each rated item, ascending, -1 (first) for an item outside the
+ * candidate frame; act_ratings the ratings aligned with act_cols; act_frame
+ * the same ratings in frame order. A user's items are distinct.
+ *   threshold = the bits of np.mean(ratings in frame order): numpy's pairwise
+ *     summation (below 8 terms serial; up to 128 eight interleaved
+ *     accumulators combined as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the
+ *     tail; above 128 the recursive halving, the split rounded down to a
+ *     multiple of 8), divided by the count;
+ *   relevant = the items with threshold - 0.1 <= rating <= threshold + 0.1,
+ *     items outside the candidate frame included;
+ *   Precision@k = hits / k, Recall@k = hits / |relevant| (0 when empty) with
+ *     hits = the relevant items among the first min(k, len_r) list entries,
+ *     for each of k_values[n_k] (a HOST array; 1 <= n_k <= 8, k in [1, 1024]);
+ *   over the m common items (column in [0, n)), t = rating, p = score:
+ *   NDCG@ndcg_k: MinMaxScaler fitted on t (scale = 1 / range, a range below
+ *     10 eps -> 1; min_ = 0 - min * scale; x * scale + min_, two roundings)
+ *     applied to both sides, grades (x >= 0.33) + (x >= 0.66) (NaN: 2),
+ *     sklearn's tie-averaged DCG over the three predicted-grade groups, best
+ *     first: (mean true grade of the group) * (disc_cs[end] - disc_cs[begin])
+ *     of the positions it occupies; IDCG = 2 * disc_cs[n2] + (disc_cs[n2 +
+ *     n1] - disc_cs[n2]) over the true grades' counts; 0 when IDCG is 0.
+ *     disc_cs (device, ndcg_k + 1 entries) = 0 followed by the running sums
+ *     of 1 / log2(i + 2), i < ndcg_k, made by the caller on the host (indices
+ *     past ndcg_k read entry ndcg_k), so no device logarithm decides a bit;
+ *   MAE / RMSE: both sides as ((4 * (v - min)) / (max - min)) + 1 over the
+ *     common items, MAE = mean |t - p|, RMSE = sqrt(mean (t - p)^2).
+ * Score sources (source; scores / ld >= n as [n_rows][ld]):
+ *   HREC_UM_SRC_F64    scores: f64 matrix; all arithmetic in f64;
+ *   HREC_UM_SRC_F32    scores: f32 matrix with np.float32 semantics (the
+ *     two-tower model's): in NDCG f32(f64(p) * scale), then f32(f64(that) +
+ *     min_), compared in f64; the 1-5 rescale all in f32, widened before the
+ *     subtraction;
+ *   HREC_UM_SRC_ALS    scores: the ALS f32 matrix; p = a_rj of
+ *     hrec_hybrid_lists (als_fallback[j] where NaN and given), f64;
+ *   HREC_UM_SRC_FUSED  scores / tt_scores: both f32 matrices, als_fallback,
+ *     minmax = hrec_hybrid_lists' out_minmax rows, row_wins [n_rows] int32:
+ *     p = the fused score hrec_hybrid_lists(_rowwise) ranks, recomputed to its
+ *     bits, f64.
+ * All metric arithmetic is f64 (f32 where stated), unfused.
+ * Outputs: per_row [n_rows][2 * n_k + 3] = Precision per k, Recall per k,
+ * NDCG, MAE, RMSE; status [n_rows] = the HREC_UM_* bits below. Where the
+ * reference raises ValueError the value is NaN and the bit is set: NDCG with
+ * exactly one common item (or an infinite score among them), MAE / RMSE when a
+ * rescaled value is not finite (one common item, constant ratings, constant
+ * scores, a NaN score). No common item: NDCG = MAE = RMSE = 0 as the
+ * reference returns. A row without ratings: all zeros, counted nowhere.
+ * sums_out [2 * (2 * n_k + 3) + HREC_UM_STATUS_BITS] (device f64): per column
+ * the sum over the rows where it is defined, then per column the count of
+ * those rows, then the number of rows with each status bit. Per-block
+ * partials in the workspace, added in a fixed order by a second launch, no
+ * floating-point atomics: equal inputs give equal bits on every call.
+ * n_rows < 65536; n_rows == 0 returns HREC_OK and touches nothing.
+ * Workspace: hrec_user_metrics_workspace_bytes(n_rows). */
+#define HREC_UM_MAX_K 8
+#define HREC_UM_SRC_F64 0
+#define HREC_UM_SRC_F32 1
+#define HREC_UM_SRC_ALS 2
+#define HREC_UM_SRC_FUSED 3
+#define HREC_UM_NDCG_UNDEFINED 1 /* NDCG is NaN                                  */
+#define HREC_UM_ERR_UNDEFINED 2  /* MAE and RMSE are NaN                         */
+#define HREC_UM_NO_COMMON 4      /* no rated item among the candidates           */
+#define HREC_UM_NO_RELEVANT 8    /* nothing in the band: Recall is 0             */
+#define HREC_UM_NO_RATINGS 16    /* a row without ratings                        */
+#define HREC_UM_STATUS_BITS 5
+size_t hrec_user_metrics_workspace_bytes(int64_t n_rows);
+int hrec_user_metrics(const int64_t* ranked, int64_t ranked_ld, int list_n, const int32_t* list_len,
+                      int64_t n_rows, int64_t n, const int32_t* k_values, int n_k, int ndcg_k,
+                      const double* disc_cs, const int64_t* act_rows, const int64_t* act_indptr,
+                      const int32_t* act_cols, const double* act_ratings, const double* act_frame,
+                      int source, const void* scores, const float* tt_scores, int64_t ld,
+                      const double* als_fallback, const double* minmax, const int32_t* row_wins,
+                      double* per_row, int32_t* status, double* sums_out, void* workspace,
+                      size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------ cold-start sim --
  * ALSModel._find_similar_items (src/als_model.py:93-104): out[q*n_items+j] =
