@@ -22,31 +22,9 @@
 // in a register across the chunks of CW columns of a wider row. At CW = 64 a
 // workgroup of 4 waves holds 66,560 B of tiles + 4 KiB of row indices: two
 // workgroups = 8 waves per CU.
-#include "common.h"
+#include "pairs.h"
 
 namespace hrec {
-
-constexpr int kPairBlock = 256;        // 4 waves, one tile of 64 pairs each per step
-constexpr int kPairMaxBlocks = 2048;   // grid cap: the tiles beyond are taken in grid strides
-constexpr int kPairBatch = 8;          // row fetches per side in flight per lane (at most)
-
-__device__ __forceinline__ void pair_wave_sync() {  // a wave's LDS operations complete in issue order
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Blocks of a launch over n pairs: a function of n alone, so the partial sums
-// of the metrics mode have one layout (and one summation order) per n.
-__host__ __device__ inline int64_t pair_blocks(int64_t n) {
-  const int64_t b = (n + kPairBlock - 1) / kPairBlock;
-  return b < 1 ? 1 : (b > kPairMaxBlocks ? kPairMaxBlocks : b);
-}
-
-// A row index as the kernel uses it: itself when inside [0, n_rows), else -1.
-__device__ __forceinline__ int64_t pair_row(int64_t r, int64_t n_rows) {
-  return (uint64_t)r < (uint64_t)n_rows ? r : -1;
-}
 
 // CW: columns per chunk (16, 32 or 64; kp is a multiple of it). METRICS: also
 // the f64 sums of the pairs with a prediction (label - prediction), one
@@ -172,19 +150,6 @@ __global__ __launch_bounds__(kPairBlock) void als_pairs_kernel(
   }
 }
 
-// sums[i] = the blocks' partials of slot i: wave i, lane l adds blocks l,
-// l + 64, ... in ascending order, then the lanes' xor tree.
-__global__ __launch_bounds__(64 * HREC_PAIR_SUMS) void als_pairs_reduce_kernel(const double* __restrict__ partials,
-                                                                              int64_t n_blocks,
-                                                                              double* __restrict__ sums) {
-  const int lane = threadIdx.x & 63, i = threadIdx.x >> 6;
-  double v = 0.0;
-  for (int64_t b = lane; b < n_blocks; b += 64) v += partials[b * HREC_PAIR_SUMS + i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  if (lane == 0) sums[i] = v;
-}
-
 static int pair_chunk(int kp) { return kp == 16 ? 16 : ((kp == 32 || kp == 96) ? 32 : 64); }
 
 // The checks both entries share, then the launch (metrics: labels != null).
@@ -226,7 +191,7 @@ static int pairs_run(const char* who, bool metrics, const float* U, int64_t n_u,
   }
 #undef HREC_PAIRS
   if (metrics)
-    hipLaunchKernelGGL(als_pairs_reduce_kernel, dim3(1), dim3(64 * HREC_PAIR_SUMS), 0, s, part, nb, sums);
+    hipLaunchKernelGGL(pairs_reduce_kernel, dim3(1), dim3(64 * HREC_PAIR_SUMS), 0, s, part, nb, sums);
   return check_launch("als_pairs_kernel");
 }
 

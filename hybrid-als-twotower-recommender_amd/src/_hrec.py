@@ -128,6 +128,10 @@ _SIGNATURES.update({
     "hrec_tt_user_forward": (_c_i32, [_PP, _vp, _c_i64, _vp, _vp]),
     "hrec_tt_score": (_c_i32, [_vp, _c_i32, _vp, _c_i64, _c_i32, _vp, _vp]),
     "hrec_tt_pair_score": (_c_i32, [_vp, _vp, _c_i64, _c_i32, _vp, _vp]),
+    "hrec_tt_predict_pairs": (_c_i32, [_vp, _c_i64, _vp, _c_i64, _c_i32, _vp, _vp, _c_i64, _vp, _vp]),
+    "hrec_tt_pair_metrics_workspace_bytes": (_c_sz, [_c_i64]),
+    "hrec_tt_pair_metrics": (_c_i32, [_vp, _c_i64, _vp, _c_i64, _c_i32, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _c_sz,
+                                      _vp]),
     "hrec_tt_item_inputs_workspace_bytes": (_c_sz, [_c_i64]),
     "hrec_tt_item_inputs": (_c_i32, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _c_sz, _vp]),
@@ -1361,6 +1365,48 @@ def tt_pair_score(user_vec, item_vec):
         _dev(user_vec, torch.float32, "user_vec"), _dev(item_vec, torch.float32, "item_vec"), n, d,
         _dev(out, torch.float32, "out"), _stream()))
     return out
+
+
+def _tt_pair_args(name, user_vec, user_rows, item_vec, item_rows):
+    d = user_vec.shape[1]
+    n = user_rows.numel()
+    if item_vec.shape[1] != d or item_rows.numel() != n:
+        raise HrecError(f"{name}: vector widths or row list lengths do not match")
+    return d, n, (_dev(user_vec, torch.float32, "user_vec"), user_vec.shape[0],
+                  _dev(item_vec, torch.float32, "item_vec"), item_vec.shape[0], d,
+                  _dev(user_rows, torch.int64, "user_rows"), _dev(item_rows, torch.int64, "item_rows"), n)
+
+
+def tt_predict_pairs(user_vec, user_rows, item_vec, item_rows, out=None):
+    """f32 [n]: the two-tower score of every (user_vec[user_rows[p]],
+    item_vec[item_rows[p]]) pair (hrec_tt_predict_pairs), with the bits
+    tt_pair_score / tt_score give that pair; both matrices row-major [rows,
+    d], 1 <= d <= 256. NaN where either row is outside its matrix."""
+    d, n, args = _tt_pair_args("tt_predict_pairs", user_vec, user_rows, item_vec, item_rows)
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=user_vec.device)
+    elif out.numel() != n:
+        raise HrecError("tt_predict_pairs: out must have one entry per pair")
+    _check("hrec_tt_predict_pairs", lib().hrec_tt_predict_pairs(*args, _dev(out, torch.float32, "out"), _stream()))
+    return out
+
+
+def tt_pair_sums(user_vec, user_rows, item_vec, item_rows, labels, pred_out=None):
+    """f64 device [len(PAIR_SUMS)]: the counts and sums of
+    hrec_tt_pair_metrics over the pairs' scores against labels (f64 [n]);
+    pred_out (f32 [n], optional) also receives the scores. One scoring launch
+    + a fixed-order reduction: the same bits on every call."""
+    d, n, args = _tt_pair_args("tt_pair_sums", user_vec, user_rows, item_vec, item_rows)
+    if labels.numel() != n or (pred_out is not None and pred_out.numel() != n):
+        raise HrecError("tt_pair_sums: labels / pred_out must have one entry per pair")
+    dev = user_vec.device
+    sums = torch.empty(len(PAIR_SUMS), dtype=torch.float64, device=dev)
+    need = int(lib().hrec_tt_pair_metrics_workspace_bytes(n))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    _check("hrec_tt_pair_metrics", lib().hrec_tt_pair_metrics(
+        *args, _dev(labels, torch.float64, "labels"), _dev(pred_out, torch.float32, "pred_out"),
+        _dev(sums, torch.float64, "sums"), _dev(ws, torch.uint8, "ws"), need, _stream()))
+    return sums
 
 
 TT_INPUTS_IDS, TT_INPUTS_INF, TT_INPUTS_DUP = 1, 2, 4

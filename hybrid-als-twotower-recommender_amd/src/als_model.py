@@ -58,7 +58,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _hrec, ranked_lists
+from . import _hrec, pair_metrics, ranked_lists
 from .ranked_lists import int_ids as _int_ids
 from .als_engine import DeviceALS, padded_k, process_group
 from .als_ingest import check_same_frame, frame_fingerprint, sharded_ingest
@@ -779,7 +779,7 @@ class ALSModel:
     # Spark's ALSModel.transform on a frame of (userId, itemId) rows and its
     # RegressionEvaluator over the result. Neither has a counterpart in the
     # reference, so failures raise instead of printing a sentinel.
-    METRIC_NAMES = ("rmse", "mse", "mae", "r2", "var")
+    METRIC_NAMES = pair_metrics.METRIC_NAMES
 
     def _pair_ids(self, data):
         if self.model is None:
@@ -813,26 +813,7 @@ class ALSModel:
         never leave the device (hrec_als_pair_metrics)."""
         users, items = self._pair_ids(data)
         s = self.model.pair_sums(users, items, np.asarray(data[label_col], np.float64))
-        n_ok, n_nan = int(s["n_ok"]), int(s["n_nan"])
-        nan = float("nan")
-        res = {name: nan for name in self.METRIC_NAMES}
-        if self.cold_start_strategy == "nan":
-            res.update(count=n_ok + n_nan, dropped=0)
-            if n_nan:
-                return res
-        else:
-            res.update(count=n_ok, dropped=n_nan)
-        if n_ok == 0:
-            return res
-        n = float(n_ok)
-        ybar = s["sum_y"] / n
-        ss_tot = s["sum_y2"] - s["sum_y"] * ybar                        # sum (y - ybar)^2
-        ss_reg = s["sum_p2"] - 2.0 * ybar * s["sum_p"] + n * ybar * ybar  # sum (p - ybar)^2
-        mse = s["sum_e2"] / n
-        with np.errstate(all="ignore"):  # constant labels: ss_tot is 0 and r2 is -inf or NaN, as in Spark
-            r2 = float(1.0 - np.float64(s["sum_e2"]) / np.float64(ss_tot))
-        res.update(mse=mse, rmse=float(np.sqrt(mse)), mae=s["sum_abs_e"] / n, var=ss_reg / n, r2=r2)
-        return res
+        return pair_metrics.regression_metrics(s, drop_nan=self.cold_start_strategy != "nan")
 
     def evaluate(self, data, metric_name="rmse", label_col="average_review_rating"):
         """Spark's RegressionEvaluator(metricName=metric_name).evaluate of

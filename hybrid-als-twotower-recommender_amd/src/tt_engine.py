@@ -144,6 +144,27 @@ class DeviceTwoTower:
         """model.predict on per-row inputs: score[r] for row r."""
         return _hrec.tt_pair_score(self.user_vectors(user), self.item_vectors(item, man, cat, numeric))
 
+    def _pair_operands(self, users, item_rows):
+        """The user tower once per DISTINCT user: (user vectors of the sorted
+        distinct ids, each pair's row in them, item_rows as int64)."""
+        uniq, inverse = torch.unique(users, return_inverse=True)
+        return self.user_vectors(uniq.to(torch.int32)), inverse.contiguous(), item_rows.to(torch.int64).contiguous()
+
+    def predict_pairs(self, users, item_vectors, item_rows):
+        """f32 device [n]: the score of users[p] (int32 ids, repeats welcome)
+        with item_vectors[item_rows[p]] (hrec_tt_predict_pairs), the bits
+        predict_rows gives that pair. NaN where item_rows[p] is outside
+        item_vectors."""
+        uvec, urows, irows = self._pair_operands(users, item_rows)
+        return _hrec.tt_predict_pairs(uvec, urows, item_vectors, irows)
+
+    def pair_sums(self, users, item_vectors, item_rows, labels, pred_out=None):
+        """f64 device [len(_hrec.PAIR_SUMS)]: hrec_tt_pair_metrics' sums of
+        predict_pairs' scores against labels (f64 device [n]); the scores go
+        to pred_out (f32 [n]) when given and stay on the device either way."""
+        uvec, urows, irows = self._pair_operands(users, item_rows)
+        return _hrec.tt_pair_sums(uvec, urows, item_vectors, irows, labels, pred_out)
+
     # ------------------------------------------------------------ train
     def train_step(self, user, item, man, cat, numeric, y):
         """One Keras train_step: forward + MSE + backward + Adam. Returns the

@@ -13,7 +13,10 @@ an optional seen-item exclusion), ranking_metrics / evaluate_ranking (Spark's
 five ranking metrics of those lists against a held-out frame) and candidates
 (the item tower's vectors of a frame, computed once) — hrec_dot_topk /
 hrec_dot_topk_excluding at widths 32 / 64 / 128 / 256, the materialised
-hrec_tt_score chain at any other width.
+hrec_tt_score chain at any other width. Likewise transform /
+regression_metrics / evaluate: the prediction of every row of a frame and the
+regression metrics of a split, over hrec_tt_predict_pairs /
+hrec_tt_pair_metrics.
 
 Deviations from the committed reference (documented in DESIGN.md):
   * `if val_data:` on a DataFrame raises in the reference (D5); here
@@ -33,7 +36,7 @@ import torch
 from sklearn.model_selection import train_test_split  # noqa: F401  (reference import surface)
 from sklearn.preprocessing import MinMaxScaler
 
-from . import _hrec, ranked_lists
+from . import _hrec, pair_metrics, ranked_lists
 from .als_model import _int_ids
 from .tt_engine import TABLES, DeviceTwoTower
 
@@ -53,9 +56,22 @@ class TwoTowerCandidates:
         self.engine = engine
         self.iterations = int(iterations)
         self.scaler_stamp = scaler_stamp
+        self._sorted = None  # (ids ascending, their frame rows), built by the first rows_of
 
     def __len__(self):
         return int(self.item_ids.size)
+
+    def rows_of(self, item_ids):
+        """Frame rows (int64 device [n]) of a device int64 id list: a binary
+        search over the frame's sorted (distinct) ids; -1 for an id the frame
+        does not hold."""
+        if len(self) == 0:
+            return torch.full_like(item_ids, -1)
+        if self._sorted is None:
+            self._sorted = torch.sort(self.ids_dev)
+        sid, order = self._sorted
+        pos = torch.searchsorted(sid, item_ids).clamp_(max=sid.numel() - 1)
+        return torch.where(sid[pos] == item_ids, order[pos], torch.full_like(item_ids, -1))
 
 
 class History:
@@ -499,6 +515,77 @@ class TwoTowerModel:
         the model's lists for the users of `data` (a float)."""
         ranked_lists.check_metric_name(metric_name, self.RANKING_METRIC_NAMES)
         return float(self.ranking_metrics(data, item_features, k, label_col, min_rating, exclude)[metric_name])
+
+    # ------------------------------------------- transform / regression metrics
+    # The pointwise side (the reference compiles this model with
+    # loss='mean_squared_error', metrics=['mae']): the prediction of every row
+    # of a frame and the regression metrics of a split, as ALSModel.transform /
+    # regression_metrics / evaluate. No counterpart in the reference: failures
+    # raise. The model has no coldStartStrategy, so transform keeps every row.
+    METRIC_NAMES = pair_metrics.METRIC_NAMES
+
+    def _pair_operands(self, data, candidates):
+        """(user ids int32 [n], item vectors f32 [m, d], item rows int64 [n]),
+        all on the device: row p of `data` scores user p with item vector
+        item_rows[p] (-1: an itemId the candidate frame does not hold)."""
+        if self.model is None:
+            raise RuntimeError("the two-tower model is not built or loaded")
+        dev, sz = self.model.device, self.model.sizes
+        users = torch.as_tensor(_ids(data["userId"].values, sz["user_emb"], "user_in"), device=dev)
+        if candidates is not None:
+            cand = self.candidates(candidates)
+            return users, cand.vectors, cand.rows_of(torch.as_tensor(_int_ids(data["itemId"], "itemId"), device=dev))
+        n = len(data)
+        if n == 0:
+            vec = torch.empty((0, int(self.embedding_size)), dtype=torch.float32, device=dev)
+        else:
+            num = _minmax_transform(self.scaler, data, ["price", "average_review_rating"])
+            vec = self.model.item_vectors(
+                torch.as_tensor(_ids(data["itemId"].values, sz["item_emb"], "item_id_in"), device=dev),
+                torch.as_tensor(_ids(data["manufacturer_id"].values, sz["man_emb"], "manufacturer_in"), device=dev),
+                torch.as_tensor(_ids(data["category_id"].values, sz["cat_emb"], "category_in"), device=dev),
+                torch.as_tensor(np.ascontiguousarray(np.asarray(num, dtype=np.float32).reshape(-1, 2)), device=dev))
+        return users, vec, torch.arange(n, dtype=torch.int64, device=dev)
+
+    def transform(self, data, prediction_col="prediction", candidates=None):
+        """A copy of `data` with the f32 prediction of every row in
+        `prediction_col` (all rows kept), from one hrec_tt_predict_pairs
+        launch; the user tower runs once per distinct user.
+        Without `candidates`, `data` carries userId and the item columns
+        predict_for_user needs; the item tower runs once per row over the
+        fitted scaler's transform (never a refit), and row p has the bits
+        predict_for_user(data.userId[p], data) gives at position p.
+        With candidates (a frame, or candidates()'s object, whose stamp is
+        checked as the list calls check it) `data` needs only userId and
+        itemId: each itemId is looked up in the candidate frame on the device
+        and scored with that row's vector - the bits predict_for_user over the
+        candidate frame gives the pair; an itemId the frame does not hold gives
+        NaN, a frame that repeats an itemId raises ValueError. A user id
+        outside the table raises IndexError."""
+        users, vec, rows = self._pair_operands(data, candidates)
+        out = data.copy()
+        out[prediction_col] = self.model.predict_pairs(users, vec, rows).cpu().numpy()
+        return out
+
+    def regression_metrics(self, data, label_col="average_review_rating", candidates=None):
+        """Spark's RegressionMetrics of transform(data, candidates=candidates)
+        against `label_col`: {"rmse", "mse", "mae", "r2", "var", "count",
+        "dropped"} by ALSModel.regression_metrics' formulas. Rows with a NaN
+        prediction (an item missing from the candidate frame) are left out and
+        counted in "dropped". One hrec_tt_pair_metrics launch: the predictions
+        never leave the device, only the ten f64 sums do."""
+        users, vec, rows = self._pair_operands(data, candidates)
+        y = torch.as_tensor(np.ascontiguousarray(np.asarray(data[label_col], np.float64)), device=self.model.device)
+        sums = self.model.pair_sums(users, vec, rows, y)
+        return pair_metrics.regression_metrics(dict(zip(_hrec.PAIR_SUMS, sums.tolist())))
+
+    def evaluate(self, data, metric_name="rmse", label_col="average_review_rating", candidates=None):
+        """One of rmse, mse, mae, r2, var of regression_metrics (a float).
+        mse and mae are what Keras' model.evaluate reports for this model's
+        loss='mean_squared_error' and metrics=['mae'], up to the f32 rounding
+        of Keras' running batch means (the sums here are f64)."""
+        ranked_lists.check_metric_name(metric_name, self.METRIC_NAMES)
+        return float(self.regression_metrics(data, label_col, candidates)[metric_name])
 
     # --------------------------------------------------------- persistence
     def save_model(self, model_path="models/twotower.keras"):

@@ -808,6 +808,38 @@ int hrec_tt_item_inputs(const int64_t* item, const int64_t* manufacturer, const 
 int hrec_tt_pair_score(const float* user_vec, const float* item_vec, int64_t n, int d,
                        float* out, void* stream);
 
+/* Two-tower scores of a pair list, and the regression sums over them
+ * (csrc/tt_pairs.hip; the two-tower counterpart of hrec_als_predict_pairs /
+ * hrec_als_pair_metrics).
+ * hrec_tt_predict_pairs: out[p] = <user_vec[user_rows[p]],
+ * item_vec[item_rows[p]]> for p < n. user_vec [n_user_rows, d] and item_vec
+ * [n_item_rows, d] are dense f32 with row stride d (what hrec_tt_user_forward
+ * / hrec_tt_item_forward write), 1 <= d <= 256, each matrix aligned to 16 B
+ * when d % 4 == 0, to 8 B when d % 2 == 0, to 4 B otherwise. The chain is
+ * hrec_tt_score's (an fmaf chain from zero in its k order for this d), so a
+ * pair has the bits hrec_tt_pair_score and hrec_tt_score give it. A row index
+ * outside [0, n_rows) on either side gives a quiet NaN and is never turned
+ * into an address. n == 0 is a no-op.
+ * hrec_tt_pair_metrics: the same predictions (stored when pred_out is not
+ * null) against labels (f64 [n]); sums_out[HREC_PAIR_SUMS] (device f64) has
+ * the HREC_PAIR_* layout and meaning of hrec_als_pair_metrics, with p^ =
+ * (double)prediction and e = y - p^. Pairs with a NaN prediction (a bad row
+ * index, a NaN in either vector) count in HREC_PAIR_N_NAN and enter no sum.
+ * No floating-point atomics: per-block partials in the workspace (the block
+ * count depends on n alone), added in a fixed order by a second launch, so
+ * equal inputs give equal bits on every call; n == 0 writes zeros.
+ * Workspace: hrec_tt_pair_metrics_workspace_bytes(n). */
+int hrec_tt_predict_pairs(const float* user_vec, int64_t n_user_rows,
+                          const float* item_vec, int64_t n_item_rows, int d,
+                          const int64_t* user_rows, const int64_t* item_rows, int64_t n,
+                          float* out, void* stream);
+size_t hrec_tt_pair_metrics_workspace_bytes(int64_t n);
+int hrec_tt_pair_metrics(const float* user_vec, int64_t n_user_rows,
+                         const float* item_vec, int64_t n_item_rows, int d,
+                         const int64_t* user_rows, const int64_t* item_rows, int64_t n,
+                         const double* labels, float* pred_out, double* sums_out,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* One minibatch of model.fit (src/two_tower_model.py:111): forward, MSE
  * loss, backward. grad_dense receives hrec_tt_grad_len(d) floats:
  * dW2[(d+32)*d] | db2[d] | dgamma_i[d] | dbeta_i[d] | dgamma_u[d] | dbeta_u[d]
