@@ -28,6 +28,7 @@
 // floating-point atomics).
 #include "exclusion.h"
 #include "hybrid_common.h"
+#include "um_score.h"
 
 #pragma clang fp contract(off)
 
@@ -40,7 +41,7 @@ constexpr int kUmListMax = 1024;  // largest k and list length
 constexpr int kUmWork = 96;       // um_sum's work stack: 2 entries per halving level + 1 (counts < 2^31: 26 levels)
 constexpr int kUmVals = 48;
 
-struct UmParams {
+struct UmParams : UmSource {  // sa, sb, ld, fb: csrc/um_score.h
   const int64_t* ranked;
   int64_t ranked_ld;
   int list_n;
@@ -54,10 +55,6 @@ struct UmParams {
   const int32_t* cols;
   const double* ratings;
   const double* frame;
-  const void* sa;
-  const float* sb;
-  int64_t ld;
-  const double* fb;
   const double* minmax;
   const int32_t* wins;
   double* per_row;
@@ -139,38 +136,6 @@ __device__ __forceinline__ T um_wave_max(T v) {
   return v;
 }
 
-// The score dtype of a source: the dense f32 matrix keeps np.float32 (the
-// two-tower rule), every other source is f64.
-template <int SRC>
-struct UmScore {
-  typedef double type;
-};
-template <>
-struct UmScore<HREC_UM_SRC_F32> {
-  typedef float type;
-};
-
-// The fused source's row state: hrec_hybrid_lists' coefficients from its out_minmax row, and the row's weights.
-struct UmFuse {
-  HpScale sc;
-  double w0, w1;
-};
-
-template <int SRC>
-__device__ __forceinline__ typename UmScore<SRC>::type um_score(const UmParams& P, int64_t row, int64_t c,
-                                                                const UmFuse& f) {
-  const int64_t at = row * P.ld + c;
-  if constexpr (SRC == HREC_UM_SRC_F64) {
-    return static_cast<const double*>(P.sa)[at];
-  } else if constexpr (SRC == HREC_UM_SRC_F32) {
-    return static_cast<const float*>(P.sa)[at];
-  } else if constexpr (SRC == HREC_UM_SRC_ALS) {
-    return hl_als(static_cast<const float*>(P.sa)[at], P.fb, c);
-  } else {
-    return hp_fuse64(f.sc, hl_als(static_cast<const float*>(P.sa)[at], P.fb, c), P.sb[at], f.w0, f.w1);
-  }
-}
-
 // np.digitize(x, [0.33, 0.66]): NaN sorts past both edges.
 __device__ __forceinline__ int um_grade(double x) { return x != x ? 2 : (x >= 0.33 ? 1 : 0) + (x >= 0.66 ? 1 : 0); }
 
@@ -198,13 +163,7 @@ __device__ __forceinline__ void um_row(const UmParams& P, int64_t row, int lane,
   thr = __shfl(thr, 0, kWave);
   const double blo = thr - 0.1, bhi = thr + 0.1;
   UmFuse f{};
-  if constexpr (SRC == HREC_UM_SRC_FUSED) {
-    const double* mm = P.minmax + 4 * row;
-    f.sc = hp_scale64(mm[0], mm[1], (float)mm[2], (float)mm[3]);
-    const bool wins = P.wins[row] != 0;
-    f.w0 = wins ? 0.8 : 0.2;
-    f.w1 = wins ? 0.2 : 0.8;
-  }
+  if constexpr (SRC == HREC_UM_SRC_FUSED) f = um_fuse_row(P.minmax, P.wins, row);
   // 2. band size, common items, extremes
   int n_rel = 0, m = 0, inf = 0;
   double tmin = __builtin_inf(), tmax = -__builtin_inf();

@@ -101,6 +101,8 @@ _SIGNATURES = {
     "hrec_user_metrics_workspace_bytes": (_c_sz, [_c_i64]),
     "hrec_user_metrics": (_c_i32, [_vp, _c_i64, _c_i32, _vp, _c_i64, _c_i64, _vp, _c_i32, _c_i32, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _c_i32, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "hrec_rank_positions_workspace_bytes": (_c_sz, [_c_i64]),
+    "hrec_rank_positions": (_c_i32, [_c_i64, _c_i64, _c_i32, _vp, _vp, _c_i64] + [_vp] * 15 + [_c_sz, _vp]),
     "hrec_fuse_workspace_bytes": (_c_sz, [_c_i64, _c_i32]),
     "hrec_fuse_topk": (_c_i32, [_vp, _vp, _c_i32, _c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp,
                                 _c_sz, _vp]),
@@ -1812,6 +1814,89 @@ def user_metrics(ranked, k_values, actual, scores, source=None, ndcg_k=10, list_
         _dev(status, torch.int32, "status"), _dev(sums, torch.float64, "sums"), _dev(ws, torch.uint8, "ws"), need,
         _stream()))
     return per_row, status, sums
+
+
+# ------------------------------------------- positions in the full catalogue
+RP_CHUNK = 1024  # HREC_RP_CHUNK: label entries of a row keyed and sorted at a time (one pass over the row each)
+# the slots of rank_positions' sums (HREC_RP_SUMS of include/hrec.h)
+RP_SUMS = ("sum_auc", "sum_reciprocal_rank", "sum_w_pr", "sum_w", "n_auc", "n_reciprocal_rank", "n_w_pr", "n_w",
+           "ranked", "unranked")
+RP_ROW = ("auc", "reciprocal_rank", "sum_w_pr", "sum_w")
+RP_ROW_N = ("live", "ranked", "unranked")
+
+
+def rank_positions(scores, labels, source=None, weight=None, excl=None, tt=None, fallback=None, minmax=None,
+                   row_wins=None, want_rank=True, out_rank=None):
+    """hrec_rank_positions: for every label entry its 0-based position among
+    ALL live candidates of its row, in the order of every top-k list here
+    (larger first, equal values by smaller column, NaN last), and per row the
+    AUC, the reciprocal rank and the percentile-rank sums. Ties are resolved
+    by the list order, not counted as 1/2: the AUC of the ranking that is
+    served. scores [n_rows, n] and source / tt / fallback / minmax / row_wins
+    as in user_metrics (a view with a row stride is fine; source None: by
+    dtype). labels = (rows int64 [n_rows] (-1: no labels), indptr int64, cols
+    int32 (any order, duplicates allowed, -1: not a candidate)), weight f64
+    aligned with cols or None; excl (optional) = (excl_rows int64 [n_rows],
+    excl_indptr int64, excl_cols int32) of hybrid_lists. Returns device
+    (rank int32 aligned with cols (-1: unranked; None unless want_rank; the
+    entries of CSR rows that no row of the call reads are left as they are:
+    out_rank, when given, is the tensor to write into), row f64 [n_rows, 4] in
+    RP_ROW's order, row_n int32 [n_rows, 3] in RP_ROW_N's, sums f64
+    [len(RP_SUMS)]). The same bits on every call."""
+    name = "rank_positions"
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 2:
+        raise HrecError(f"{name}: scores must be a 2-D device tensor")
+    n_rows, n = (int(x) for x in scores.shape)
+    dev = scores.device
+    if source is None:
+        source = "f32" if scores.dtype == torch.float32 else "f64"
+    if source not in UM_SOURCES:
+        raise HrecError(f"{name}: source must be one of {sorted(UM_SOURCES)}")
+    s_ptr, scores, ld = _rows_matrix(name, "scores", scores, torch.float64 if source == "f64" else torch.float32, n_rows)
+    t_ptr = None
+    if source == "fused":
+        t_ptr, tt, t_ld = _rows_matrix(name, "tt", tt, torch.float32, n_rows)
+        if tuple(tt.shape) != (n_rows, n) or (n_rows > 1 and t_ld != ld):
+            raise HrecError(f"{name}: scores and tt need the same shape and row stride")
+        if minmax is None or tuple(minmax.shape) != (n_rows, 4) or row_wins is None or row_wins.numel() != n_rows:
+            raise HrecError(f"{name}: the fused source needs minmax [n_rows, 4] and row_wins [n_rows]")
+    if fallback is not None and fallback.numel() != n:
+        raise HrecError(f"{name}: fallback must hold one value per column")
+    rows, indptr, cols = labels
+    if rows.numel() != n_rows:
+        raise HrecError(f"{name}: label_rows must hold one entry per row")
+    if weight is not None and weight.numel() != cols.numel():
+        raise HrecError(f"{name}: weight must be aligned with the label columns")
+    n_lab = int(cols.numel())
+    if out_rank is not None:
+        if out_rank.numel() != n_lab:
+            raise HrecError(f"{name}: out_rank must be aligned with the label columns")
+        rank = out_rank
+    else:
+        rank = torch.empty(n_lab, dtype=torch.int32, device=dev) if want_rank else None
+    if n_lab == 0:  # stand-in entries, never read
+        cols = torch.zeros(1, dtype=torch.int32, device=dev)
+        weight = None
+    if excl is not None:
+        if excl[0].numel() != n_rows:
+            raise HrecError(f"{name}: excl_rows must hold one entry per row")
+        excl_args = (_dev(excl[0], torch.int64, f"{name}: excl_rows"), *_excl_args(name, excl[1], excl[2]))
+    else:
+        excl_args = (None, None, None)
+    row = torch.empty((n_rows, len(RP_ROW)), dtype=torch.float64, device=dev)
+    row_n = torch.empty((n_rows, len(RP_ROW_N)), dtype=torch.int32, device=dev)
+    sums = torch.zeros(len(RP_SUMS), dtype=torch.float64, device=dev)
+    need = int(lib().hrec_rank_positions_workspace_bytes(n_rows))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    _check("hrec_rank_positions", lib().hrec_rank_positions(
+        n_rows, n, UM_SOURCES[source], s_ptr, t_ptr, ld, _dev(fallback, torch.float64, "fallback"),
+        _dev(minmax, torch.float64, "minmax"), _dev(row_wins, torch.int32, "row_wins"),
+        _dev(rows, torch.int64, "label_rows"), _dev(indptr, torch.int64, "label_indptr"),
+        _dev(cols, torch.int32, "label_cols"), _dev(weight, torch.float64, "label_weight"), *excl_args,
+        _dev(rank if n_lab else None, torch.int32, "out_rank"), _dev(row, torch.float64, "out_row"),
+        _dev(row_n, torch.int32, "out_row_n"), _dev(sums, torch.float64, "sums"), _dev(ws, torch.uint8, "ws"), need,
+        _stream()))
+    return rank, row, row_n, sums
 
 
 # ------------------------------------------------------- multi-GPU (C-ABI)

@@ -45,6 +45,10 @@ ALSModel.transform at :75) is replaced by libhrec's HIP kernels:
                       NDCG@k; not in the reference) -> recommend's lists,
                       still on the device, against a label CSR ->
                       hrec_ranking_metrics                           [K2r]
+  rank_of / full_ranking_metrics / evaluate_full_ranking (every held-out
+                      item's position among ALL items: expected percentile
+                      rank, AUC, uncut MRR; not in the reference) ->
+                      hrec_als_score per sub-batch + hrec_rank_positions
 
 `initialize_spark` / `stop_spark` keep their names: they bind / release the
 HIP device session that plays the SparkSession's role.
@@ -965,6 +969,104 @@ class ALSModel:
         ranking_metrics."""
         ranked_lists.check_metric_name(metric_name, self.RANKING_METRIC_NAMES)
         return float(self.ranking_metrics(data, k, label_col, min_rating, exclude)[metric_name])
+
+    # --------------------------------- positions in the full catalogue
+    # Where every held-out item stands among ALL items of the model: what the
+    # lists above, cut at 1024, cannot say. Expected percentile rank is the
+    # measure of Hu, Koren and Volinsky's paper (Spark's implicitPrefs), AUC
+    # and the uncut reciprocal rank the usual companions. No counterpart in the
+    # reference: failures raise.
+    FULL_RANKING_METRIC_NAMES = ranked_lists.FULL_RANK_NAMES
+
+    def _full_rank(self, users, items, weights, exclude):
+        """(rank per pair, metrics with "dropped") of ranked_lists.full_rank_metrics over the model's items."""
+        model, dev = self._trained(), self.model.U.device
+        if self.cold_start_strategy not in ("drop", "nan"):
+            raise ValueError(f"coldStartStrategy {self.cold_start_strategy!r} is not supported")
+        item_ids = np.asarray(model.item_ids, np.int64)
+        user_ids = np.asarray(model.user_ids, np.int64)
+        n_items = int(item_ids.size)
+        excl = self._exclusion("user", exclude) if exclude is not None else None
+
+        def scores(uids):
+            urows = torch.as_tensor(model._lookup(user_ids, uids), device=dev)
+            kw = dict(scores=_hrec.als_score(model.U, urows, model.Vt, None, n_items, model.k), source="f32")
+            if excl is not None:
+                kw["excl"] = (urows, *excl)
+            return kw
+
+        rank, res = ranked_lists.full_rank_metrics(
+            users, items, weights, item_ids, dev, scores, 4, model.RECOMMEND_FALLBACK_BYTES,
+            known=lambda uniq: model._lookup(user_ids, uniq) >= 0, cols_sorted=True,
+            host_rows=self.RANKING_HOST_ROWS)
+        return rank, res
+
+    def _known_users(self, users):
+        """bool per entry of `users` (int64 numpy): the model knows the id (long lists: looked up on the device)."""
+        model = self.model
+        if users.size > model.PAIR_DEVICE_LOOKUP:
+            return (model._lookup_device(users, "user") >= 0).cpu().numpy()
+        return model._lookup(np.asarray(model.user_ids, np.int64), users) >= 0
+
+    def rank_of(self, data, exclude=None):
+        """A copy of `data` (columns userId, itemId) with an int64 `rank`
+        column: the 0-based position of the row's item among ALL items of the
+        model in the user's ranking — larger transform prediction first, equal
+        predictions by smaller itemId — without the pairs of `exclude` (a frame
+        with userId and itemId, typically the training frame). For any n <=
+        1024, rank < n holds exactly when the item stands at position rank of
+        the user's list from recommend_for_user_subset(n, exclude). -1: the
+        pair cannot be ranked (the user or the item is unknown to the model,
+        or the pair is excluded). cold_start_strategy "drop" removes the rows
+        of unknown users (order and index kept), "nan" keeps them. The scores
+        (hrec_als_score, transform's bits) and the counting (hrec_rank_positions)
+        stay on the device."""
+        users, items = self._pair_ids(data)
+        rank, _ = self._full_rank(users, items, None, exclude)
+        out = ranked_lists.rank_frame(data, rank)
+        if self.cold_start_strategy == "drop":
+            out = out[self._known_users(users)]
+        return out
+
+    def full_ranking_metrics(self, data, weight_col=None, min_rating=None, label_col=None, exclude=None):
+        """The ranking measures that need every position, of the pairs of
+        `data` (columns userId, itemId; with min_rating the rows whose
+        label_col, default average_review_rating, is >= it) among ALL items of
+        the model: {"meanPercentileRank", "auc", "meanReciprocalRank", "count",
+        "pairs", "unranked", "dropped"}.
+        meanPercentileRank: Hu, Koren and Volinsky's expected percentile rank,
+        sum w * rank / (live - 1) / sum w over the ranked pairs, w = weight_col
+        (finite and >= 0, else ValueError; 1 without) and live the user's items
+        left after `exclude`; in [0, 1], lower is better, 0.5 is random. auc:
+        the mean over users of the fraction of (held-out, other) item pairs
+        ranked in the right order; meanReciprocalRank: the mean of 1 / (1 + the
+        user's best rank), with no cut-off; both over the users where they are
+        defined, `count` = the users with a ranked pair. Ties are resolved by
+        the list order (smaller itemId first), not counted as 1/2: the AUC of
+        the ranking that is served. `pairs` / `unranked`: the pairs that entered
+        / could not enter. Unlike ranking_metrics' set size, an item the model
+        does not know (or an excluded pair) cannot be ranked and enters no
+        statistic. Users unknown to the model: cold_start_strategy "drop"
+        leaves them out and counts them in `dropped`, "nan" keeps them with
+        every pair unranked. Nothing ranked: NaN metrics."""
+        self._pair_ids(data)
+        users, items, weights = ranked_lists.full_rank_frame(data, weight_col, min_rating, label_col)
+        dropped = 0
+        if self.cold_start_strategy == "drop":
+            known = self._known_users(users)
+            dropped = int(np.unique(users[~known]).size)
+            users, items = users[known], items[known]
+            weights = None if weights is None else weights[known]
+        _, res = self._full_rank(users, items, weights, exclude)
+        res["dropped"] = dropped
+        return res
+
+    def evaluate_full_ranking(self, data, metric_name="meanPercentileRank", weight_col=None, min_rating=None,
+                              label_col=None, exclude=None):
+        """One of full_ranking_metrics' meanPercentileRank, auc,
+        meanReciprocalRank (a float)."""
+        ranked_lists.check_metric_name(metric_name, self.FULL_RANKING_METRIC_NAMES)
+        return float(self.full_ranking_metrics(data, weight_col, min_rating, label_col, exclude)[metric_name])
 
     # ----------------------------------------------------------- persistence
     def save_model(self, model_path="models/als"):

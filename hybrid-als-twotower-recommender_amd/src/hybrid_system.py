@@ -22,6 +22,9 @@ fit_fusion_weights are the batch form of evaluate_individual_models.
 evaluate_users is the batch form of the reference's evaluation loop
 (RecommenderEvaluator's metrics of all three models per user; DESIGN §24:
 hrec_user_metrics over the same scores and lists).
+rank_of / full_ranking_metrics / evaluate_full_ranking place every held-out
+item among ALL candidates of the fused ranking (expected percentile rank,
+AUC, uncut reciprocal rank; DESIGN §26: hrec_rank_positions' fused source).
 """
 import itertools
 import os
@@ -674,6 +677,82 @@ class HybridRecommendationSystem:
         ranked_lists.check_metric_name(metric_name, self.RANKING_METRIC_NAMES)
         return float(self.ranking_metrics(data, item_features, k, label_col, min_rating, exclude, actual,
                                           f1_k)[metric_name])
+
+    # --------------------------------- positions in the full catalogue
+    FULL_RANKING_METRIC_NAMES = ranked_lists.FULL_RANK_NAMES
+
+    def _full_rank(self, users, items, weights, cand, exclude):
+        """(rank per pair, metrics) of ranked_lists.full_rank_metrics over the
+        fused scores: per sub-batch both score matrices, the scaler extremes
+        from the hrec_hybrid_lists call the list path makes (top_k 1: only its
+        out_minmax is used), then hrec_rank_positions' fused source with the
+        instance's weights in every row."""
+        tt = self.twotower_model
+        dev = tt.model.device
+        queried = tt._query_users(users)  # an id outside the user table: IndexError
+        N = len(cand)
+        if queried.size == 0 or N == 0:
+            return ranked_lists.full_rank_metrics(users, items, weights, cand.item_ids, dev, None, 8, 1)
+        excl = tt._exclusion(queried, cand, exclude) if exclude is not None else None
+        fallback = self._als_fallback(queried, cand.item_ids)
+        als_wins = self.als_f1_score > self.twotower_f1_score
+
+        def scores(uids):
+            a, t = self._scores(uids, cand)
+            *_, mm = _hrec.hybrid_lists(a, t, 1, als_wins, fallback=fallback, mode=0, want_minmax=True)
+            kw = dict(scores=a, source="fused", tt=t, fallback=fallback, minmax=mm,
+                      row_wins=torch.full((uids.size,), int(als_wins), dtype=torch.int32, device=dev))
+            if excl is not None:  # exclusion row q is queried[q]
+                kw["excl"] = (torch.as_tensor(np.searchsorted(queried, uids), device=dev), *excl)
+            return kw
+
+        return ranked_lists.full_rank_metrics(users, items, weights, cand.item_ids, dev, scores, 8,
+                                              self.RECOMMEND_SCORE_BYTES, max_rows=self.RECOMMEND_ROWS,
+                                              host_rows=self.RANKING_HOST_ROWS)
+
+    def rank_of(self, data, item_features, exclude=None):
+        """A copy of `data` (columns userId, itemId) with an int64 `rank`
+        column: the 0-based position of the row's item among ALL candidates of
+        `item_features` in the user's fused ranking (recommend_for_users'
+        scores, weights and ties: equal fused scores in frame order, NaN last)
+        without the pairs of `exclude`. For any n <= 1024, rank < n holds
+        exactly when the item stands at position rank of the user's list from
+        recommend_for_users(users, item_features, n, exclude). -1: the item is
+        not a candidate, or the pair is excluded. The scalers are fitted over
+        all candidates, as for the lists; cold ALS ids use the cold-start
+        vector (ValueError without it). Every user is fused with the
+        instance's weights: the per-user `actual=` weights of
+        recommend_for_users are not part of these methods."""
+        self._require_models()
+        cand = self.twotower_model.candidates(item_features)
+        users = ranked_lists.int_ids(data["userId"], "userId")
+        items = ranked_lists.int_ids(data["itemId"], "itemId")
+        rank, _ = self._full_rank(users, items, None, cand, exclude)
+        return ranked_lists.rank_frame(data, rank)
+
+    def full_ranking_metrics(self, data, item_features, weight_col=None, min_rating=None, label_col=None,
+                             exclude=None):
+        """ALSModel.full_ranking_metrics of the fused model over the
+        candidates of `item_features`: {"meanPercentileRank", "auc",
+        "meanReciprocalRank", "count", "pairs", "unranked", "dropped"} of the
+        pairs of `data` among ALL candidates, ranked as rank_of ranks them
+        (ties in frame order, not counted as 1/2). `dropped` is 0. The
+        instance's weights for every user; per-user `actual=` weights are not
+        part of these methods."""
+        self._require_models()
+        cand = self.twotower_model.candidates(item_features)
+        users, items, weights = ranked_lists.full_rank_frame(data, weight_col, min_rating, label_col)
+        _, res = self._full_rank(users, items, weights, cand, exclude)
+        res["dropped"] = 0
+        return res
+
+    def evaluate_full_ranking(self, data, item_features, metric_name="meanPercentileRank", weight_col=None,
+                              min_rating=None, label_col=None, exclude=None):
+        """One of full_ranking_metrics' meanPercentileRank, auc,
+        meanReciprocalRank (a float)."""
+        ranked_lists.check_metric_name(metric_name, self.FULL_RANKING_METRIC_NAMES)
+        return float(self.full_ranking_metrics(data, item_features, weight_col, min_rating, label_col,
+                                               exclude)[metric_name])
 
     def cleanup(self):
         if self.als_model:

@@ -190,6 +190,135 @@ def ranking_metrics(data, k, label_col, min_rating, dev, host_rows, names, lists
     return res
 
 
+# ------------------------------------------- positions in the full catalogue
+# What a list cut at 1024 cannot say: where every held-out item stands among
+# ALL candidates (hrec_rank_positions), and the three measures that need it.
+FULL_RANK_NAMES = ("meanPercentileRank", "auc", "meanReciprocalRank")
+
+
+def full_rank_frame(data, weight_col=None, min_rating=None, label_col=None):
+    """(users, items int64, weights f64 or None) of a frame with userId and
+    itemId: the rows whose label_col (default average_review_rating) is >=
+    min_rating when given. Weights must be finite and >= 0."""
+    users, items = int_ids(data["userId"], "userId"), int_ids(data["itemId"], "itemId")
+    weights = None if weight_col is None else np.asarray(data[weight_col], np.float64).reshape(-1)
+    if weights is not None and (not np.all(np.isfinite(weights)) or np.any(weights < 0)):
+        raise ValueError(f"{weight_col} must hold finite weights >= 0")
+    if min_rating is not None:
+        keep = np.asarray(data[label_col or "average_review_rating"], np.float64) >= float(min_rating)
+        users, items = users[keep], items[keep]
+        weights = None if weights is None else weights[keep]
+    return users, items, weights
+
+
+def _full_rank_csr_host(users, items, weights, col_keys, cols_sorted, dev):
+    """The label CSR of full_rank_metrics, sorted on the host: (distinct users
+    ascending (numpy), indptr int64, cols int32 (-1: not a candidate), weights
+    f64 or None on the device, unsort: device ranks in CSR order -> numpy int64
+    in frame order). A user's entries keep frame order (a stable sort)."""
+    n_pairs, n = int(users.size), int(col_keys.size)
+    order = np.argsort(users, kind="stable")
+    u = users[order]
+    first = np.flatnonzero(np.r_[True, u[1:] != u[:-1]])
+    indptr = np.r_[first, n_pairs].astype(np.int64)
+    if cols_sorted:
+        sorted_keys, back = col_keys, None
+    else:
+        back = np.argsort(col_keys, kind="stable")
+        sorted_keys = col_keys[back]
+    it = items[order]
+    pos = np.minimum(np.searchsorted(sorted_keys, it), n - 1)
+    cols = np.where(sorted_keys[pos] == it, pos if back is None else back[pos], -1).astype(np.int32)
+    d_weight = None if weights is None else torch.as_tensor(np.ascontiguousarray(weights[order], np.float64), device=dev)
+
+    def unsort(d_rank):
+        rank = np.empty(n_pairs, np.int64)
+        rank[order] = d_rank.cpu().numpy()
+        return rank
+
+    return u[first], torch.as_tensor(indptr, device=dev), torch.as_tensor(cols, device=dev), d_weight, unsort
+
+
+def _full_rank_csr_device(users, items, weights, col_keys, cols_sorted, dev):
+    """_full_rank_csr_host with the sort and the searches on the device."""
+    n_pairs, n = int(users.size), int(col_keys.size)
+    u, order = torch.sort(torch.as_tensor(users, device=dev), stable=True)
+    uniq, counts = torch.unique_consecutive(u, return_counts=True)
+    indptr = torch.zeros(uniq.numel() + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=indptr[1:])
+    keys = torch.as_tensor(col_keys, device=dev)
+    sorted_keys, back = (keys, None) if cols_sorted else torch.sort(keys, stable=True)
+    it = torch.as_tensor(items, device=dev)[order]
+    pos = torch.searchsorted(sorted_keys, it).clamp_(max=n - 1)
+    cols = torch.where(sorted_keys[pos] == it, pos if back is None else back[pos], torch.full_like(pos, -1))
+    d_weight = None if weights is None else torch.as_tensor(weights, dtype=torch.float64, device=dev)[order].contiguous()
+
+    def unsort(d_rank):
+        rank = torch.empty(n_pairs, dtype=torch.int64, device=dev)
+        rank[order] = d_rank.to(torch.int64)
+        return rank.cpu().numpy()
+
+    return uniq.cpu().numpy(), indptr, cols.to(torch.int32).contiguous(), d_weight, unsort
+
+
+def full_rank_metrics(users, items, weights, col_keys, dev, scores, row_bytes, max_bytes, known=None,
+                      cols_sorted=False, max_rows=1 << 20, host_rows=1 << 16):
+    """The positions of the (users[p], items[p]) pairs among all candidates,
+    and their metrics. col_keys: the candidates' ids (int64, distinct), position
+    = score column; an item outside them is unranked. The label CSR holds one
+    row per distinct user (ascending), a user's entries in frame order with
+    their weights; it is built on the host for frames up to host_rows rows, on
+    the device above. The users with known(uniq) true (None: all) go in
+    sub-batches of at most max_bytes // (row_bytes * n) rows through
+    scores(user_ids) -> the keyword arguments of _hrec.rank_positions for those
+    rows (scores, source, ..., excl with one excl_rows entry per row); the
+    other users' pairs are unranked. The sums stay on the device until one
+    host read at the end. Returns (rank int64 per pair (-1: unranked),
+    {"meanPercentileRank", "auc", "meanReciprocalRank", "count", "pairs",
+    "unranked"}): meanPercentileRank = sum w * rank / (live - 1) / sum w over
+    the ranked pairs (Hu, Koren and Volinsky's expected percentile rank: 0 is
+    best, 0.5 random), auc and meanReciprocalRank the means over the users
+    where they are defined, count those users (of the reciprocal rank: the
+    users with a ranked pair), pairs the ranked pairs. Ties are resolved by the
+    list order, not counted as 1/2. Nothing ranked: NaN metrics."""
+    users, items = np.asarray(users, np.int64).reshape(-1), np.asarray(items, np.int64).reshape(-1)
+    col_keys = np.asarray(col_keys, np.int64).reshape(-1)
+    n_pairs, n = int(users.size), int(col_keys.size)
+    res = dict({name: float("nan") for name in FULL_RANK_NAMES}, count=0, pairs=0, unranked=n_pairs)
+    rank = np.full(n_pairs, -1, np.int64)
+    if n_pairs == 0 or n == 0:
+        return rank, res
+    build = _full_rank_csr_host if n_pairs <= host_rows else _full_rank_csr_device
+    uniq, d_indptr, d_cols, d_weight, unsort = build(users, items, weights, col_keys, cols_sorted, dev)
+    rows = np.arange(uniq.size, dtype=np.int64)
+    if known is not None:
+        rows = rows[np.asarray(known(uniq), bool)]
+    d_rank = torch.full((n_pairs,), -1, dtype=torch.int32, device=dev)
+    total = torch.zeros(len(_hrec.RP_SUMS), dtype=torch.float64, device=dev)
+    sub = int(max(1, min(max_rows, max_bytes // (row_bytes * n))))
+    for lo in range(0, rows.size, sub):
+        q = rows[lo: lo + sub]
+        kw = scores(uniq[q])
+        _, _, _, sums = _hrec.rank_positions(labels=(torch.as_tensor(q, device=dev), d_indptr, d_cols),
+                                             weight=d_weight, out_rank=d_rank, **kw)
+        total += sums
+    s = dict(zip(_hrec.RP_SUMS, total.tolist()))  # one host read
+    rank = unsort(d_rank)
+    res.update(count=int(s["n_reciprocal_rank"]), pairs=int(s["ranked"]), unranked=n_pairs - int(s["ranked"]))
+    if s["ranked"] > 0:
+        res["meanPercentileRank"] = s["sum_w_pr"] / s["sum_w"] if s["sum_w"] > 0 else float("nan")
+        res["auc"] = s["sum_auc"] / s["n_auc"] if s["n_auc"] > 0 else float("nan")
+        res["meanReciprocalRank"] = s["sum_reciprocal_rank"] / s["n_reciprocal_rank"]
+    return rank, res
+
+
+def rank_frame(data, rank):
+    """A copy of `data` with the int64 `rank` column (-1: unranked)."""
+    out = data.copy()
+    out["rank"] = np.asarray(rank, np.int64)
+    return out
+
+
 # ----------------------------------------------------------- list finishing
 def empty_lists(n, kk, dtype, dev, with_lens):
     """The (ids, scores, lens) of n lists of kk entries when either is 0."""

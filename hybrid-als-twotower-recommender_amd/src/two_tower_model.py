@@ -516,6 +516,68 @@ class TwoTowerModel:
         ranked_lists.check_metric_name(metric_name, self.RANKING_METRIC_NAMES)
         return float(self.ranking_metrics(data, item_features, k, label_col, min_rating, exclude)[metric_name])
 
+    # --------------------------------- positions in the full catalogue
+    # ALSModel.rank_of / full_ranking_metrics / evaluate_full_ranking over a
+    # candidate frame. No counterpart in the reference: failures raise.
+    FULL_RANKING_METRIC_NAMES = ranked_lists.FULL_RANK_NAMES
+
+    def _full_rank(self, users, items, weights, cand, exclude):
+        """(rank per pair, metrics) of ranked_lists.full_rank_metrics over the candidate frame."""
+        dev = self.model.device
+        queried = self._query_users(users)  # an id outside the user table: IndexError
+        V = cand.vectors
+        excl = self._exclusion(queried, cand, exclude) if exclude is not None and len(cand) else None
+
+        def scores(uids):
+            U = self.model.user_vectors(torch.as_tensor(uids.astype(np.int32), device=dev))
+            kw = dict(scores=_hrec.tt_score(U, V), source="f32")
+            if excl is not None:  # exclusion row q is queried[q]
+                kw["excl"] = (torch.as_tensor(np.searchsorted(queried, uids), device=dev), *excl)
+            return kw
+
+        return ranked_lists.full_rank_metrics(users, items, weights, cand.item_ids, dev, scores, 4,
+                                              self.RECOMMEND_FALLBACK_BYTES, host_rows=self.RANKING_HOST_ROWS)
+
+    def rank_of(self, data, item_features, exclude=None):
+        """A copy of `data` (columns userId, itemId) with an int64 `rank`
+        column: the 0-based position of the row's item among ALL candidates of
+        `item_features` (a frame, or candidates()'s object) in the user's
+        ranking — larger predict_for_user score first, equal scores in frame
+        order, NaN last — without the pairs of `exclude`. For any n <= 1024,
+        rank < n holds exactly when the item stands at position rank of the
+        user's list from recommend_for_users(users, item_features, n, exclude).
+        -1: the item is not a candidate, or the pair is excluded. A user id
+        outside the table raises IndexError. The scores are hrec_tt_score's
+        at every width (predict_for_user's bits); scoring and counting
+        (hrec_rank_positions) stay on the device."""
+        cand = self.candidates(item_features)
+        users, items = _int_ids(data["userId"], "userId"), _int_ids(data["itemId"], "itemId")
+        rank, _ = self._full_rank(users, items, None, cand, exclude)
+        return ranked_lists.rank_frame(data, rank)
+
+    def full_ranking_metrics(self, data, item_features, weight_col=None, min_rating=None, label_col=None,
+                             exclude=None):
+        """ALSModel.full_ranking_metrics over the candidates of
+        `item_features`: {"meanPercentileRank", "auc", "meanReciprocalRank",
+        "count", "pairs", "unranked", "dropped"} of the pairs of `data` among
+        ALL candidates (ties in frame order, not counted as 1/2; an item
+        outside the candidate frame or an excluded pair is unranked and enters
+        no statistic). The model has no coldStartStrategy: `dropped` is 0 and a
+        user id outside the table raises IndexError."""
+        cand = self.candidates(item_features)
+        users, items, weights = ranked_lists.full_rank_frame(data, weight_col, min_rating, label_col)
+        _, res = self._full_rank(users, items, weights, cand, exclude)
+        res["dropped"] = 0
+        return res
+
+    def evaluate_full_ranking(self, data, item_features, metric_name="meanPercentileRank", weight_col=None,
+                              min_rating=None, label_col=None, exclude=None):
+        """One of full_ranking_metrics' meanPercentileRank, auc,
+        meanReciprocalRank (a float)."""
+        ranked_lists.check_metric_name(metric_name, self.FULL_RANKING_METRIC_NAMES)
+        return float(self.full_ranking_metrics(data, item_features, weight_col, min_rating, label_col,
+                                               exclude)[metric_name])
+
     # ------------------------------------------- transform / regression metrics
     # The pointwise side (the reference compiles this model with
     # loss='mean_squared_error', metrics=['mae']): the prediction of every row

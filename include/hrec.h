@@ -717,6 +717,62 @@ int hrec_user_metrics(const int64_t* ranked, int64_t ranked_ld, int list_n, cons
                       double* per_row, int32_t* status, double* sums_out, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* The position of every held-out item among ALL candidates (additive to ABI
+ * 7): what a top-n list cut at 1024 cannot say. For row r with candidate
+ * columns 0 .. n - 1 and scores s_rj from one of hrec_user_metrics' sources
+ * (source, scores, tt_scores, ld, als_fallback, minmax, row_wins exactly as
+ * there; the fused value is recomputed to its bits), a label entry with
+ * column p gets
+ *   rank = #{ j : j != p, j not excluded for r, j stands before p }
+ * in the order of every top-k here: larger value first, equal values by
+ * smaller column first, NaN last (NaNs by column). That is the 0-based
+ * position of p in the list hrec_hybrid_lists / hrec_dot_topk_excluding /
+ * hrec_als_score_topk_excluding would return for row r if n entries were
+ * allowed. Ties are resolved by that order, not counted as 1/2: the AUC below
+ * is the AUC of the ranking that is served.
+ * Labels (a CSR shaped like the exclusion CSR): row r's entries are
+ * label_cols[label_indptr[q] .. label_indptr[q + 1]) with q = label_rows[r]
+ * (q < 0, or all three pointers NULL: a row without labels); columns in any
+ * order, duplicates allowed, every entry answered. An entry whose column is
+ * outside [0, n) (-1: not a candidate) or in the row's exclusion set is
+ * unranked: rank -1. label_weight (optional, f64, aligned with label_cols):
+ * the entry's weight w, 1 when NULL.
+ * Exclusion (optional): (excl_rows, excl_indptr, excl_cols), the triple of
+ * hrec_hybrid_lists (columns ascending per row).
+ * Outputs: out_rank (optional) int32 aligned with label_cols. out_row_n
+ * [n_rows][3] int32 = live (n minus the row's distinct excluded columns in
+ * [0, n)), ranked and unranked label entries. out_row [n_rows][4] f64, with h
+ * = the row's ranked labels after collapsing duplicate columns, S = the sum of
+ * their ranks and L = live, integers in int64 and exactly these f64
+ * operations:
+ *   auc = 1.0 - (double)(S - h * (h - 1) / 2) / ((double)h * (double)(L - h)),
+ *     NaN when h == 0 or L == h;
+ *   reciprocal_rank = 1.0 / (double)(1 + min rank), NaN when h == 0;
+ *   sum_w_pr = sum of w_p * ((double)rank_p / (double)(L - 1)) over the ranked
+ *     entries (the fraction is 0 when L == 1), sum_w = sum of w_p: per thread
+ *     in CSR order, the threads in a fixed tree.
+ * sums_out [HREC_RP_SUMS] (device f64): the sums over rows of auc,
+ * reciprocal_rank, sum_w_pr, sum_w where each is defined (the last two: rows
+ * with a ranked entry), then the four counts of those rows, then the ranked and
+ * the unranked entries of all rows. Partials of 256 rows in the workspace,
+ * added in a fixed order by a further launch, no floating-point atomics: equal
+ * inputs give equal bits on every call.
+ * A row's label entries are keyed and sorted HREC_RP_CHUNK at a time in LDS
+ * and the score row is read once per chunk; nothing of size n_rows * n is
+ * allocated. n < 2^31; n_rows == 0 returns HREC_OK and touches nothing.
+ * Workspace: hrec_rank_positions_workspace_bytes(n_rows). */
+#define HREC_RP_CHUNK 1024
+#define HREC_RP_SUMS 10
+size_t hrec_rank_positions_workspace_bytes(int64_t n_rows);
+int hrec_rank_positions(int64_t n_rows, int64_t n, int source, const void* scores,
+                        const float* tt_scores, int64_t ld, const double* als_fallback,
+                        const double* minmax, const int32_t* row_wins, const int64_t* label_rows,
+                        const int64_t* label_indptr, const int32_t* label_cols,
+                        const double* label_weight, const int64_t* excl_rows,
+                        const int64_t* excl_indptr, const int32_t* excl_cols, int32_t* out_rank,
+                        double* out_row, int32_t* out_row_n, double* sums_out, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------ cold-start sim --
  * ALSModel._find_similar_items (src/als_model.py:93-104): out[q*n_items+j] =
  * cosine(feats[query_rows[q]], feats[j]) with sklearn's normalise-then-dot
