@@ -103,6 +103,10 @@ _SIGNATURES = {
                                    _vp, _vp, _c_i32, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
     "hrec_rank_positions_workspace_bytes": (_c_sz, [_c_i64]),
     "hrec_rank_positions": (_c_i32, [_c_i64, _c_i64, _c_i32, _vp, _vp, _c_i64] + [_vp] * 15 + [_c_sz, _vp]),
+    "hrec_row_inv_norms": (_c_i32, [_vp, _c_i64, _c_i32, _c_i64, _vp, _vp]),
+    "hrec_list_quality_workspace_bytes": (_c_sz, [_c_i64]),
+    "hrec_list_quality": (_c_i32, [_vp, _c_i64, _c_i32, _vp, _c_i64, _c_i64, _vp, _c_i32, _c_i64, _vp, _vp, _vp, _vp,
+                                   _vp, _c_i32, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
     "hrec_fuse_workspace_bytes": (_c_sz, [_c_i64, _c_i32]),
     "hrec_fuse_topk": (_c_i32, [_vp, _vp, _c_i32, _c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp,
                                 _c_sz, _vp]),
@@ -1897,6 +1901,107 @@ def rank_positions(scores, labels, source=None, weight=None, excl=None, tt=None,
         _dev(row_n, torch.int32, "out_row_n"), _dev(sums, torch.float64, "sums"), _dev(ws, torch.uint8, "ws"), need,
         _stream()))
     return rank, row, row_n, sums
+
+
+# ------------------------------------------------------------- list quality
+LQ_MAX_TABLES = 4   # HREC_LQ_MAX_TABLES
+LQ_LIST_MAX = 1024  # longest list
+LQ_MAX_D = 256      # widest item vector
+
+
+def lq_columns(n_tab):
+    """The columns of list_quality's per_row and row_n, in order."""
+    return ("intraListDiversity", "unexpectedness") + tuple(f"table{t}" for t in range(int(n_tab)))
+
+
+def lq_sums(n_tab):
+    """The slots of list_quality's sums, in order: per column its sum over the
+    rows where it is defined, then per column the count of those rows."""
+    cols = lq_columns(n_tab)
+    return tuple([f"sum_{c}" for c in cols] + [f"n_{c}" for c in cols])
+
+
+def _vector_rows(name, vectors, d):
+    """(pointer, n, d, ld) of a 2-D f32 device matrix whose first d columns
+    (None: all) are the item vectors; a view with a row stride is taken as it is."""
+    if not isinstance(vectors, torch.Tensor) or not vectors.is_cuda or vectors.dtype != torch.float32 \
+            or vectors.dim() != 2:
+        raise HrecError(f"{name}: vectors must be a 2-D float32 device tensor")
+    n = int(vectors.shape[0])
+    d = int(vectors.shape[1]) if d is None else int(d)
+    if d > vectors.shape[1]:
+        raise HrecError(f"{name}: d exceeds the vectors' columns")
+    if vectors.stride(1) != 1 or (n > 1 and vectors.stride(0) < vectors.shape[1]):
+        raise HrecError(f"{name}: vectors must have unit column stride")
+    return _vp(vectors.data_ptr()), n, d, (int(vectors.stride(0)) if n > 1 else int(vectors.shape[1]))
+
+
+def row_inv_norms(vectors, d=None):
+    """hrec_row_inv_norms: f64 device [n] = 1 / |row j| over the first d
+    columns (None: all) of the f32 device matrix, 0 where the squared norm is
+    0 or not finite."""
+    ptr, n, d, ld = _vector_rows("row_inv_norms", vectors, d)
+    out = torch.empty(n, dtype=torch.float64, device=vectors.device)
+    _check("hrec_row_inv_norms", lib().hrec_row_inv_norms(ptr, n, d, ld, _dev(out, torch.float64, "out"), _stream()))
+    return out
+
+
+def list_quality(lists, vectors, inv_norm, list_len=None, history=None, tables=None, exposure=None, sums=None,
+                 d=None):
+    """hrec_list_quality: per list (row of `lists`: int64 [n_rows, L <= 1024]
+    device candidate columns, the first list_len[r] (int32; None: L) entries;
+    a view with a row stride is fine) the intra-list diversity, the
+    unexpectedness against history = (rows int64 [n_rows] (-1: none), indptr
+    int64, cols int32) or None, and the means of tables (f64 [n_tab <= 4, n]
+    or None) over the list; every valid entry adds 1 to exposure (int64 [n];
+    None: a zeroed one is made) and the call adds onto sums (f64
+    [len(lq_sums(n_tab))]; None: zeroed). vectors f32 [n, >= d] with inv_norm
+    = row_inv_norms(vectors, d). Returns device (per_row f64 [n_rows, 2 +
+    n_tab] in lq_columns' order, row_n int32 of the same shape (m, g, counted
+    table entries), exposure, sums). The same bits on every call."""
+    name = "list_quality"
+    v_ptr, n, d, ld = _vector_rows(name, vectors, d)
+    dev = vectors.device
+    if not isinstance(lists, torch.Tensor) or lists.dim() != 2:
+        raise HrecError(f"{name}: lists must be a 2-D device tensor")
+    n_rows = int(lists.shape[0])
+    l_ptr, lists, l_ld = _rows_matrix(name, "lists", lists, torch.int64, n_rows)
+    list_n = int(lists.shape[1])
+    if inv_norm.numel() != n:
+        raise HrecError(f"{name}: inv_norm must hold one value per vector")
+    if list_len is not None and list_len.numel() != n_rows:
+        raise HrecError(f"{name}: list_len must have one entry per row")
+    n_tab = 0
+    if tables is not None:
+        if tables.dim() != 2 or (tables.shape[0] and tables.shape[1] != n):
+            raise HrecError(f"{name}: tables must be [n_tab, n]")
+        n_tab = int(tables.shape[0])
+    if history is not None:
+        if history[0].numel() != n_rows:
+            raise HrecError(f"{name}: hist_rows must hold one entry per row")
+        hist_args = (_dev(history[0], torch.int64, f"{name}: hist_rows"), *_excl_args(name, history[1], history[2]))
+    else:
+        hist_args = (None, None, None)
+    ncol = 2 + n_tab
+    if exposure is None:
+        exposure = torch.zeros(n, dtype=torch.int64, device=dev)
+    elif exposure.numel() != n:
+        raise HrecError(f"{name}: exposure must hold one counter per vector")
+    if sums is None:
+        sums = torch.zeros(2 * ncol, dtype=torch.float64, device=dev)
+    elif sums.numel() != 2 * ncol:
+        raise HrecError(f"{name}: sums must hold {2 * ncol} slots")
+    per_row = torch.empty((n_rows, ncol), dtype=torch.float64, device=dev)
+    row_n = torch.empty((n_rows, ncol), dtype=torch.int32, device=dev)
+    need = int(lib().hrec_list_quality_workspace_bytes(n_rows))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    _check("hrec_list_quality", lib().hrec_list_quality(
+        l_ptr, l_ld, list_n, _dev(list_len, torch.int32, "list_len"), n_rows, n, v_ptr, d, ld,
+        _dev(inv_norm, torch.float64, "inv_norm"), *hist_args,
+        _dev(tables if n_tab else None, torch.float64, "tables"), n_tab, _dev(exposure, torch.int64, "exposure"),
+        _dev(per_row, torch.float64, "per_row"), _dev(row_n, torch.int32, "row_n"), _dev(sums, torch.float64, "sums"),
+        _dev(ws, torch.uint8, "ws"), need, _stream()))
+    return per_row, row_n, exposure, sums
 
 
 # ------------------------------------------------------- multi-GPU (C-ABI)

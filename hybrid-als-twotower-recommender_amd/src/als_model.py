@@ -49,6 +49,12 @@ ALSModel.transform at :75) is replaced by libhrec's HIP kernels:
                       item's position among ALL items: expected percentile
                       rank, AUC, uncut MRR; not in the reference) ->
                       hrec_als_score per sub-batch + hrec_rank_positions
+  list_quality_metrics / evaluate_list_quality (what the lists look like as
+                      a whole: coverage, entropy and Gini of the exposure,
+                      personalization, novelty, intra-list diversity,
+                      unexpectedness; not in the reference) -> recommend's
+                      column lists, still on the device ->
+                      hrec_row_inv_norms + hrec_list_quality
 
 `initialize_spark` / `stop_spark` keep their names: they bind / release the
 HIP device session that plays the SparkSession's role.
@@ -214,7 +220,7 @@ class DeviceALSFactors:
             cols_sorted=True, device_keys=lambda: tuple(self._ids_device(s) for s in sides),
             what="user_ids and item_ids")
 
-    def recommend(self, side, rows, num, exclude=None):
+    def recommend(self, side, rows, num, exclude=None, _columns=False):
         """Top-`num` of the other side for each of `rows` (int64 row indices
         into `side`'s factor matrix, every one in range): device (ids int64
         [n, kk], scores f32 [n, kk]), kk = min(num, size of the other side).
@@ -237,7 +243,9 @@ class DeviceALSFactors:
         keeps); at every kk hrec_als_score_topk_excluding (the exact chain
         over every pair); hrec_als_score + hrec_mask_rows_f32 + hrec_topk.
         One flag per batch and level; one host read after the last batch of
-        the first level, a second only if that one found a flag."""
+        the first level, a second only if that one found a flag.
+        _columns (internal): return (row indices of the other side int64
+        [n, kk], lens or None) instead: the lists before the id gather."""
         num = ranked_lists.check_num(num, self.RECOMMEND_MAX)
         Q, F, Ft, bf, ids = self._recommend_operands(side)
         dev = Q.device
@@ -255,7 +263,7 @@ class DeviceALSFactors:
         lens = torch.zeros(n, dtype=torch.int32, device=dev) if excl else None
         outs = (out_i, out_v, lens) if excl else (out_i, out_v)
         if n == 0 or kk == 0:
-            return outs
+            return (out_i, lens) if _columns else outs
         if bool(((rows < 0) | (rows >= Q.shape[0])).any().item()):
             raise ValueError(f"recommend: a {side} row is outside [0, {Q.shape[0]})")
         B = int(self.RECOMMEND_BATCH)
@@ -290,6 +298,8 @@ class DeviceALSFactors:
             _hrec.topk_materialised(lambda s, e: _hrec.als_score(Q, rows[s:e], Ft, None, n_other, self.k),
                                     starts[b], min(starts[b] + B, n), n_other, kk, self.RECOMMEND_FALLBACK_BYTES,
                                     out_i, out_v, lens, (rows, indptr, cols) if excl else None)
+        if _columns:
+            return out_i, lens
         if not excl:
             return ids[out_i], out_v
         return (*ranked_lists.pad_lists(ids, out_i, out_v, lens, n_other), lens)
@@ -969,6 +979,67 @@ class ALSModel:
         ranking_metrics."""
         ranked_lists.check_metric_name(metric_name, self.RANKING_METRIC_NAMES)
         return float(self.ranking_metrics(data, k, label_col, min_rating, exclude)[metric_name])
+
+    # ------------------------------------------------------------ list quality
+    # What the served lists look like as a whole: coverage, concentration,
+    # novelty, diversity. No labels and no counterpart in the reference:
+    # failures raise.
+    LIST_QUALITY_METRIC_NAMES = ranked_lists.LIST_QUALITY_NAMES
+    LIST_QUALITY_ROWS = 1 << 16  # users of one recommend + hrec_list_quality sub-batch
+
+    def list_quality_metrics(self, k=10, users=None, exclude=None, history=None):
+        """The beyond-accuracy measures of the model's top-k item lists
+        (recommend_for_all_users(k, exclude) / recommend_for_user_subset(users,
+        k, exclude)), which never leave the device: {"catalogCoverage",
+        "distributionalCoverage", "gini", "personalization",
+        "intraListDiversity", "unexpectedness", "novelty", "averagePopularity",
+        "count", "novelty_unseen", "dropped"} (ranked_lists.list_quality has
+        the definitions). Cosines are taken between item factors. users: None
+        (every user of the model), a DataFrame with a userId column or an
+        array-like; ids the model does not know are left out and counted in
+        "dropped". history (optional): a DataFrame with userId and itemId
+        columns, typically the training frame (and the same one as exclude):
+        novelty = the mean self-information log2(Hsum / h_i) of the listed
+        items, h_i the frame's distinct pairs of item i; averagePopularity =
+        the mean of h_i / the frame's distinct users; unexpectedness = one
+        minus the mean cosine between a listed item and an item of the user's
+        own history. Without it those three are NaN."""
+        import pandas as pd
+
+        model = self._trained()
+        dev = model.U.device
+        k = ranked_lists.check_num(k, model.RECOMMEND_MAX, "k")
+        ids = np.asarray(model.user_ids, np.int64)
+        dropped = 0
+        if users is None:
+            rows = np.arange(ids.size, dtype=np.int64)
+        else:
+            if isinstance(users, pd.DataFrame):
+                users = users["userId"]
+            rows = model._lookup(ids, np.unique(_int_ids(np.asarray(users).reshape(-1), "userId")))
+            dropped = int((rows < 0).sum())
+            rows = rows[rows >= 0]
+        excl = self._exclusion("user", exclude) if exclude is not None else None
+        hist = tables = None
+        if history is not None:
+            hist = excl if history is exclude else self._exclusion("user", history)
+            tables = ranked_lists.history_tables(*ranked_lists.history_frame(history), model.item_ids, dev,
+                                                 cols_sorted=True)
+
+        def batches():
+            for lo in range(0, rows.size, self.LIST_QUALITY_ROWS):
+                r = torch.as_tensor(rows[lo: lo + self.LIST_QUALITY_ROWS], device=dev)
+                cols, lens = model.recommend("user", r, k, exclude=excl, _columns=True)
+                yield cols, lens, None if hist is None else (r, *hist)
+
+        res = ranked_lists.list_quality(batches, model.V, model.k, k, tables)
+        res["dropped"] = dropped
+        return res
+
+    def evaluate_list_quality(self, metric_name="catalogCoverage", k=10, users=None, exclude=None, history=None):
+        """One of list_quality_metrics' eight measures (a float)."""
+        ranked_lists.check_metric_name(metric_name, self.LIST_QUALITY_METRIC_NAMES)
+        return float(self.list_quality_metrics(k, users, exclude, history)[metric_name])
 
     # --------------------------------- positions in the full catalogue
     # Where every held-out item stands among ALL items of the model: what the

@@ -25,14 +25,16 @@ Not in the reference (failures raise): `evaluate_scores`, the same
 metrics for every user of a score matrix in one device pass (`_hrec.topk`
 followed by hrec_user_metrics), `summarize`, and the helpers
 HybridRecommendationSystem.evaluate_users shares with it (the actual-ratings
-CSR, the result frame).
+CSR, the result frame); and `evaluate_lists`, the label-free
+list-quality measures of any lists frame over any vector matrix
+(hrec_list_quality).
 """
 import os
 
 import numpy as np
 import torch
 
-from . import _hrec
+from . import _hrec, ranked_lists
 from .als_model import compute_f1_score  # noqa: F401  (D2)
 
 _BAND = 0.1  # the manuscript's relevance tolerance around the mean rating
@@ -209,6 +211,51 @@ class RecommenderEvaluator:
         ncol = 2 * len(ks) + 3
         host = (torch.cat(out) if out else torch.zeros((0, ncol + 1), dtype=torch.float64)).cpu().numpy()[order]
         return metrics_frame(users, host[:, :ncol], host[:, ncol], ks, has_rows)
+
+    @staticmethod
+    def evaluate_lists(lists, item_ids, vectors, history=None):
+        """The list-quality measures (not in the reference) of any lists
+        frame: `lists` has `userId` and `recommendations` (per user a list of
+        (itemId, rating) tuples: what the models' recommend_for_* methods
+        return); `vectors` [len(item_ids), d <= 256] (f32; array or device
+        tensor) holds the vector of candidate item_ids[j] the cosines are
+        taken between. Returns ranked_lists.list_quality's dict
+        ("catalogCoverage", "distributionalCoverage", "gini",
+        "personalization", "intraListDiversity", "unexpectedness", "novelty",
+        "averagePopularity", "count", "novelty_unseen"), with k = the longest
+        list of the frame; an itemId outside item_ids enters nothing. history
+        (optional): a DataFrame with userId and itemId columns, typically the
+        training frame; without it novelty, averagePopularity and
+        unexpectedness are NaN. One hrec_list_quality pass over the lists."""
+        _hrec.require_device()
+        iid = ranked_lists.int_ids(np.asarray(item_ids).reshape(-1), "item_ids")
+        if np.unique(iid).size != iid.size:
+            raise ValueError("evaluate_lists: item_ids must not repeat an id")
+        v = vectors if isinstance(vectors, torch.Tensor) else torch.as_tensor(np.asarray(vectors, np.float32))
+        if v.dim() != 2 or v.shape[0] != iid.size or not 1 <= v.shape[1] <= _hrec.LQ_MAX_D:
+            raise ValueError(f"evaluate_lists: vectors must be [len(item_ids), 1 .. {_hrec.LQ_MAX_D}]")
+        v = v.to(torch.float32).cuda().contiguous()
+        dev = v.device
+        cols, lens = ranked_lists.lists_frame_columns(lists, iid)
+        if cols.shape[1] > _hrec.LQ_LIST_MAX:
+            raise ValueError(f"evaluate_lists: a list is longer than {_hrec.LQ_LIST_MAX}")
+        hist = tables = None
+        if history is not None:
+            users = ranked_lists.int_ids(lists["userId"], "userId")
+            uniq = np.unique(users)
+            hu, hi = ranked_lists.history_frame(history)
+            indptr, hcols = ranked_lists.exclusion_csr(uniq, iid, hu, hi, dev, EVALUATE_ROWS,
+                                                       what="history: userId and itemId")
+            hist = (torch.as_tensor(np.searchsorted(uniq, users).astype(np.int64), device=dev), indptr, hcols)
+            tables = ranked_lists.history_tables(hu, hi, iid, dev)
+
+        def batches():
+            for lo in range(0, cols.shape[0], EVALUATE_ROWS):
+                sl = slice(lo, lo + EVALUATE_ROWS)
+                yield (torch.as_tensor(cols[sl], device=dev), torch.as_tensor(lens[sl], device=dev),
+                       None if hist is None else (hist[0][sl], *hist[1:]))
+
+        return ranked_lists.list_quality(batches, v, int(v.shape[1]), max(int(cols.shape[1]), 1), tables)
 
     @staticmethod
     def summarize(frame):

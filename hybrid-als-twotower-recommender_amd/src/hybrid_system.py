@@ -25,6 +25,9 @@ hrec_user_metrics over the same scores and lists).
 rank_of / full_ranking_metrics / evaluate_full_ranking place every held-out
 item among ALL candidates of the fused ranking (expected percentile rank,
 AUC, uncut reciprocal rank; DESIGN §26: hrec_rank_positions' fused source).
+list_quality_metrics / evaluate_list_quality say what the fused lists look
+like as a whole (coverage, Gini, novelty, diversity, unexpectedness; DESIGN
+§27: hrec_list_quality over the lists' columns, still on the device).
 """
 import itertools
 import os
@@ -419,7 +422,7 @@ class HybridRecommendationSystem:
                     lists_pass(s1, e1, a, t, 1)
         return f1, wins, idx, val, lens
 
-    def _recommend_device(self, users, cand, num, exclude=None, actual=None, f1_k=10):
+    def _recommend_device(self, users, cand, num, exclude=None, actual=None, f1_k=10, _columns=False):
         """Top-`num` fused candidates for each of `users` (TwoTowerModel.
         _query_users' array): device (raw itemIds int64 [n, kk], fused scores
         f64 [n, kk], lens int32 [n] or None when every list is full), kk =
@@ -427,7 +430,9 @@ class HybridRecommendationSystem:
         through hrec_hybrid_lists in sub-batches (mode 0); the sub-batches
         whose overflow flag is set — read back once, after the last one — are
         redone in mode 1. With `actual`: _adaptive_device, each user with
-        rows there fused by its own two F1@f1_k."""
+        rows there fused by its own two F1@f1_k. _columns (internal): return
+        (candidate frame rows int64 [n, kk], lens int32 [n]) instead: the
+        lists before the id gather."""
         num = ranked_lists.check_num(num, self.RECOMMEND_MAX, "num_items")
         f1_k = ranked_lists.check_num(f1_k, self.RECOMMEND_MAX, "f1_k")
         tt = self.twotower_model
@@ -435,13 +440,16 @@ class HybridRecommendationSystem:
         n, N = int(users.size), len(cand)
         kk = min(num, N)
         if n == 0 or kk == 0:
-            return ranked_lists.empty_lists(n, kk, torch.float64, dev, exclude is not None)
+            empty = ranked_lists.empty_lists(n, kk, torch.float64, dev, exclude is not None or _columns)
+            return empty[::2] if _columns else empty
         excl = tt._exclusion(users, cand, exclude) if exclude is not None else None
         fallback = self._als_fallback(users, cand.item_ids)
         als_wins = self.als_f1_score > self.twotower_f1_score
         if actual is not None:
             _, _, idx, val, lens = self._adaptive_device(users, cand, kk, excl, fallback,
                                                          self._labels(users, cand, actual), f1_k, als_wins)
+            if _columns:
+                return idx, lens
             ids, val = ranked_lists.pad_lists(cand.ids_dev, idx, val, lens, N)
             return ids, val, (None if exclude is None else lens)
         rows = torch.arange(n, dtype=torch.int64, device=dev)  # query q reads exclusion row q
@@ -462,6 +470,8 @@ class HybridRecommendationSystem:
             if over:
                 for s1, e1 in self._spans(s, e, N, 16):
                     run(s1, e1, 1)
+        if _columns:
+            return idx, lens
         ids, val = ranked_lists.pad_lists(cand.ids_dev, idx, val, lens, N)
         return ids, val, (None if exclude is None else lens)
 
@@ -521,6 +531,64 @@ class HybridRecommendationSystem:
         self._require_models()
         return self.recommend_for_users(np.arange(int(self.twotower_model.num_users), dtype=np.int64), item_features,
                                         num_items, exclude, actual, f1_k)
+
+    # What the fused lists look like as a whole: ALSModel.list_quality_metrics
+    # / evaluate_list_quality for recommend_for_users' lists. No counterpart
+    # in the reference: failures raise.
+    LIST_QUALITY_METRIC_NAMES = ranked_lists.LIST_QUALITY_NAMES
+    LIST_QUALITY_SIMILARITIES = ("twotower", "als")
+
+    def _similarity_vectors(self, cand, similarity):
+        """(vectors f32 device [candidates, >= d], d) the cosines are taken between."""
+        if similarity not in self.LIST_QUALITY_SIMILARITIES:
+            raise ValueError(f"similarity must be one of {', '.join(self.LIST_QUALITY_SIMILARITIES)} "
+                             f"(got {similarity!r})")
+        if similarity == "twotower":
+            return cand.vectors, (int(cand.vectors.shape[1]) if len(cand) else 1)
+        m = self.als_model.model
+        if m is None:
+            raise RuntimeError("the ALS model is not trained or loaded")
+        rows = torch.as_tensor(m._lookup(np.asarray(m.item_ids, np.int64), cand.item_ids), device=m.V.device)
+        vec = m.V[rows.clamp(min=0)] * (rows >= 0).unsqueeze(1)  # an item the ALS model does not know: the zero vector
+        return vec.contiguous(), m.k
+
+    def list_quality_metrics(self, item_features, k=10, users=None, exclude=None, history=None, actual=None, f1_k=10,
+                             similarity="twotower"):
+        """ALSModel.list_quality_metrics for the fused top-k lists over the
+        candidates of `item_features` (recommend_for_users(users,
+        item_features, k, exclude, actual, f1_k); users None: every user of
+        the two-tower table), still on the device. similarity: "twotower":
+        cosines between the candidates' item-tower vectors; "als": between the
+        ALS item factors gathered into candidate order, an item the ALS model
+        does not know being a zero vector (cosine 0 with everything). history:
+        a DataFrame with userId and itemId columns (typically the training
+        frame). "dropped" is 0: a user id outside the two-tower table raises
+        IndexError, and users the ALS model does not know are served through
+        its cold-start values as in recommend_for_users."""
+        self._require_models()
+        tt = self.twotower_model
+        cand = tt.candidates(item_features)
+        k = ranked_lists.check_num(k, self.RECOMMEND_MAX, "k")
+        users = tt._query_users(np.arange(int(tt.num_users), dtype=np.int64) if users is None else users)
+        dev = tt.model.device
+        vectors, d = self._similarity_vectors(cand, similarity)
+        hist, tables = tt._history(users, cand, history)
+
+        def batches():
+            cols, lens = self._recommend_device(users, cand, k, exclude, actual, f1_k, _columns=True)
+            rows = torch.arange(int(users.size), dtype=torch.int64, device=dev)  # query q reads history row q
+            yield cols, lens, None if hist is None else (rows, *hist)
+
+        res = ranked_lists.list_quality(batches, vectors, d, k, tables)
+        res["dropped"] = 0
+        return res
+
+    def evaluate_list_quality(self, item_features, metric_name="catalogCoverage", k=10, users=None, exclude=None,
+                              history=None, actual=None, f1_k=10, similarity="twotower"):
+        """One of list_quality_metrics' eight measures (a float)."""
+        ranked_lists.check_metric_name(metric_name, self.LIST_QUALITY_METRIC_NAMES)
+        return float(self.list_quality_metrics(item_features, k, users, exclude, history, actual, f1_k,
+                                               similarity)[metric_name])
 
     def evaluate_models(self, data, item_features, k=10):
         """evaluate_individual_models for every user of `data` (columns

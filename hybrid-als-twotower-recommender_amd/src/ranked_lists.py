@@ -319,6 +319,130 @@ def rank_frame(data, rank):
     return out
 
 
+# ------------------------------------------------------------- list quality
+# What the served lists look like as a whole (hrec_list_quality): how much of
+# the catalogue they reach, how concentrated the exposure is, how novel, how
+# diverse and how unexpected the lists are. No labels: nothing here says whether
+# a list is right.
+LIST_QUALITY_NAMES = ("catalogCoverage", "distributionalCoverage", "gini", "personalization", "intraListDiversity",
+                      "unexpectedness", "novelty", "averagePopularity")
+
+
+def history_frame(history):
+    """(users, items) int64 of a history frame (columns userId, itemId)."""
+    return int_ids(history["userId"], "userId"), int_ids(history["itemId"], "itemId")
+
+
+def history_tables(users, items, col_keys, dev, cols_sorted=False):
+    """The two per-candidate tables of a history frame's (users[p], items[p])
+    pairs, f64 device [2, n]: with h_i the distinct pairs of candidate i
+    (col_keys[i]; over all users of the frame) and Hsum their total, row 0 =
+    log2(Hsum / h_i) (the self-information of i; NaN where h_i = 0), row 1 =
+    h_i / the frame's distinct users. One sort of 64-bit keys on the device."""
+    n = int(np.asarray(col_keys).size)
+    u = torch.as_tensor(np.asarray(users, np.int64).reshape(-1), device=dev)
+    it = torch.as_tensor(np.asarray(items, np.int64).reshape(-1), device=dev)
+    h = torch.zeros(n, dtype=torch.int64, device=dev)
+    n_users = 0
+    if n and u.numel():
+        keys = torch.as_tensor(np.asarray(col_keys, np.int64).reshape(-1), device=dev)
+        sorted_keys, back = (keys, None) if cols_sorted else torch.sort(keys, stable=True)
+        pos = torch.searchsorted(sorted_keys, it).clamp_(max=n - 1)
+        ok = sorted_keys[pos] == it
+        uniq, urank = torch.unique(u, return_inverse=True)
+        n_users = int(uniq.numel())
+        col = pos[ok] if back is None else back[pos[ok]]
+        pair = torch.unique(urank[ok] * n + col)  # one key per distinct (user, candidate)
+        if pair.numel():
+            h = torch.bincount(torch.remainder(pair, n), minlength=n)
+    hf = h.to(torch.float64)
+    novelty = torch.where(h > 0, torch.log2(hf.sum() / hf.clamp(min=1.0)), torch.full_like(hf, float("nan")))
+    return torch.stack([novelty, hf / max(n_users, 1)]).contiguous()
+
+
+def list_quality(batches, vectors, d, k, tables=None):
+    """The list-quality measures of the lists batches() yields, one sub-batch
+    at a time: (columns int64 device [b, L <= 1024]: candidate columns, what a
+    top-k returns before the id gather; lens int32 [b] or None: every list
+    full; history: (rows int64 [b] (-1: none), indptr, cols) of an exclusion
+    CSR, or None). vectors f32 device [n, >= d]: the candidates' vectors, the
+    first d columns; tables: history_tables' pair or None; k: the list length
+    asked for. hrec_row_inv_norms once, hrec_list_quality per sub-batch with
+    the exposure counters and the sums accumulating on the device, then torch
+    ops on the [n] exposure vector and ONE host read. With c_i the exposure of
+    candidate i, T their total, U the lists with an entry and N = n:
+      catalogCoverage = #{c_i > 0} / N;
+      distributionalCoverage = -sum_{c_i > 0} (c_i / T) log2(c_i / T) (bits);
+      gini = sum_j (2 j - N - 1) c_(j) / (N T), c ascending, j = 1 .. N: 0 for
+        equal exposure, (N - 1) / N with all of it on one item;
+      personalization = 1 - [sum_i c_i (c_i - 1) / 2] / [U (U - 1) / 2 * k]: one
+        minus the mean overlap of two users' lists (NaN when U < 2);
+      intraListDiversity, unexpectedness, novelty, averagePopularity: the means
+        of the kernel's per-list columns over the lists where each is defined
+        (the last three NaN without history / tables);
+      count = U; novelty_unseen = the list entries whose item has no history
+        pair (left out of novelty).
+    The integer sums are exact (below 2^53). Nothing recommended: NaN metrics."""
+    dev = vectors.device
+    n = int(vectors.shape[0])
+    res = dict({name: float("nan") for name in LIST_QUALITY_NAMES}, count=0, novelty_unseen=0)
+    if n == 0:
+        return res
+    n_tab = 0 if tables is None else int(tables.shape[0])
+    ncol = 2 + n_tab
+    inv = _hrec.row_inv_norms(vectors, d)
+    exposure = torch.zeros(n, dtype=torch.int64, device=dev)
+    sums = torch.zeros(2 * ncol, dtype=torch.float64, device=dev)
+    users = torch.zeros((), dtype=torch.int64, device=dev)
+    for cols, lens, hist in batches():
+        if cols.shape[0] == 0:
+            continue
+        _, row_n, _, _ = _hrec.list_quality(cols, vectors, inv, list_len=lens, history=hist, tables=tables,
+                                            exposure=exposure, sums=sums, d=d)
+        users += (row_n[:, 0] > 0).sum()
+    c = exposure
+    total = c.sum()
+    j = torch.arange(1, n + 1, dtype=torch.int64, device=dev)
+    gini_num = ((2 * j - n - 1) * torch.sort(c).values).sum()
+    p = c[c > 0].to(torch.float64) / total.to(torch.float64)
+    entropy = -(p * torch.log2(p)).sum()
+    pairs = torch.div(c * (c - 1), 2, rounding_mode="floor").to(torch.float64).sum()
+    unseen = (c * torch.isnan(tables[0])).sum() if n_tab else torch.zeros_like(total)
+    ints = torch.stack([users, total, (c > 0).sum(), gini_num, unseen]).to(torch.float64)
+    host = torch.cat([ints, torch.stack([entropy, pairs]), sums]).tolist()  # one host read
+    n_users, total, reached, gini_num, unseen = (int(x) for x in host[:5])
+    entropy, pairs = host[5:7]
+    s = host[7:]
+    if n_users == 0:
+        return res
+    means = [s[i] / s[ncol + i] if s[ncol + i] > 0 else float("nan") for i in range(ncol)]
+    res.update(catalogCoverage=reached / n, distributionalCoverage=entropy, gini=gini_num / (n * total),
+               personalization=1.0 - pairs / (n_users * (n_users - 1) / 2 * k) if n_users >= 2 else float("nan"),
+               intraListDiversity=means[0], unexpectedness=means[1], count=n_users, novelty_unseen=unseen)
+    if n_tab >= 2:
+        res.update(novelty=means[2], averagePopularity=means[3])
+    return res
+
+
+def lists_frame_columns(lists, item_ids):
+    """(columns int64 numpy [n_lists, L], lens int32 numpy) of a lists frame's
+    `recommendations` column (lists of (itemId, rating) tuples) over the
+    candidates item_ids (int64, distinct): an id outside them becomes -1."""
+    recs = list(lists["recommendations"])
+    item_ids = np.asarray(item_ids, np.int64).reshape(-1)
+    width = max([len(r) for r in recs], default=0)
+    cols = np.full((len(recs), width), -1, np.int64)
+    lens = np.array([len(r) for r in recs], np.int32)
+    if width and item_ids.size:
+        order = np.argsort(item_ids, kind="stable")
+        sorted_ids = item_ids[order]
+        flat = np.array([int(i) for r in recs for i, _ in r], np.int64)
+        pos = np.minimum(np.searchsorted(sorted_ids, flat), item_ids.size - 1)
+        col = np.where(sorted_ids[pos] == flat, order[pos], -1)
+        cols[np.arange(width)[None, :] < lens[:, None]] = col
+    return cols, lens
+
+
 # ----------------------------------------------------------- list finishing
 def empty_lists(n, kk, dtype, dev, with_lens):
     """The (ids, scores, lens) of n lists of kk entries when either is 0."""

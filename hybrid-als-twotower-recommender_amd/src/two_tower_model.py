@@ -429,17 +429,20 @@ class TwoTowerModel:
             raise RuntimeError("the two-tower model is not built or loaded")
         return np.unique(_ids(np.asarray(users).reshape(-1), self.model.sizes["user_emb"], "user_in").astype(np.int64))
 
-    def _recommend_device(self, users, cand, num, exclude=None):
+    def _recommend_device(self, users, cand, num, exclude=None, _columns=False):
         """Top-`num` candidates for each of `users` (_query_users' array):
         device (raw itemIds int64 [n, kk], scores f32 [n, kk], lens int32 [n]
         or None when every list is full), kk = min(num, candidates). Past a
-        list's length: id 0, score NaN."""
+        list's length: id 0, score NaN. _columns (internal): return (candidate
+        frame rows int64 [n, kk], lens or None) instead: the lists before the
+        id gather."""
         num = ranked_lists.check_num(num, self.RECOMMEND_MAX, "num_items")
         dev = self.model.device
         n, N = int(users.size), int(cand.vectors.shape[0])
         kk = min(num, N)
         if n == 0 or kk == 0:
-            return ranked_lists.empty_lists(n, kk, torch.float32, dev, exclude is not None)
+            empty = ranked_lists.empty_lists(n, kk, torch.float32, dev, exclude is not None)
+            return empty[::2] if _columns else empty
         excl = self._exclusion(users, cand, exclude) if exclude is not None else None
         U = self.model.user_vectors(torch.as_tensor(users.astype(np.int32), device=dev))
         V = cand.vectors
@@ -457,6 +460,8 @@ class TwoTowerModel:
             _hrec.topk_materialised(lambda s, e: _hrec.tt_score(U[s:e].contiguous(), V), 0, n, N, kk,
                                     self.RECOMMEND_FALLBACK_BYTES, idx, val, lens,
                                     None if excl is None else (rows, *excl))
+        if _columns:
+            return idx, lens
         if lens is None:
             return cand.ids_dev[idx], val, None
         return (*ranked_lists.pad_lists(cand.ids_dev, idx, val, lens, N), lens)
@@ -515,6 +520,50 @@ class TwoTowerModel:
         the model's lists for the users of `data` (a float)."""
         ranked_lists.check_metric_name(metric_name, self.RANKING_METRIC_NAMES)
         return float(self.ranking_metrics(data, item_features, k, label_col, min_rating, exclude)[metric_name])
+
+    # ------------------------------------------------------------ list quality
+    # ALSModel.list_quality_metrics / evaluate_list_quality over a candidate
+    # frame. No counterpart in the reference: failures raise.
+    LIST_QUALITY_METRIC_NAMES = ranked_lists.LIST_QUALITY_NAMES
+
+    def _history(self, users, cand, history):
+        """(the queried users' history CSR: _exclusion's, the frame's two
+        tables) of a history frame, (None, None) without one."""
+        if history is None or len(cand) == 0:
+            return None, None
+        return (self._exclusion(users, cand, history),
+                ranked_lists.history_tables(*ranked_lists.history_frame(history), cand.item_ids, self.model.device))
+
+    def list_quality_metrics(self, item_features, k=10, users=None, exclude=None, history=None):
+        """ALSModel.list_quality_metrics for the model's top-k lists over the
+        candidates of `item_features` (recommend_for_users(users,
+        item_features, k, exclude); users None: every user of the table), still
+        on the device. Cosines are taken between the candidates' item-tower
+        vectors (TwoTowerCandidates.vectors). history: a DataFrame with userId
+        and itemId columns (typically the training frame); its items outside
+        the candidate frame enter nothing. The model has no coldStartStrategy:
+        "dropped" is 0 and a user id outside the table raises IndexError."""
+        cand = self.candidates(item_features)
+        k = ranked_lists.check_num(k, self.RECOMMEND_MAX, "k")
+        users = self._query_users(np.arange(int(self.num_users), dtype=np.int64) if users is None else users)
+        dev = self.model.device
+        hist, tables = self._history(users, cand, history)
+
+        def batches():
+            cols, lens = self._recommend_device(users, cand, k, exclude, _columns=True)
+            rows = torch.arange(int(users.size), dtype=torch.int64, device=dev)  # query q reads history row q
+            yield cols, lens, None if hist is None else (rows, *hist)
+
+        res = ranked_lists.list_quality(batches, cand.vectors, int(cand.vectors.shape[1]) if len(cand) else 1, k,
+                                        tables)
+        res["dropped"] = 0
+        return res
+
+    def evaluate_list_quality(self, item_features, metric_name="catalogCoverage", k=10, users=None, exclude=None,
+                              history=None):
+        """One of list_quality_metrics' eight measures (a float)."""
+        ranked_lists.check_metric_name(metric_name, self.LIST_QUALITY_METRIC_NAMES)
+        return float(self.list_quality_metrics(item_features, k, users, exclude, history)[metric_name])
 
     # --------------------------------- positions in the full catalogue
     # ALSModel.rank_of / full_ranking_metrics / evaluate_full_ranking over a

@@ -31,6 +31,9 @@
  *   Python RecommenderEvaluator (Precision@k / Recall@k, NDCG, MAE, RMSE
  *          per user) src/evaluation.py:19-149, for many
  *          users                                       -> hrec_user_metrics
+ *   Beyond-accuracy list measures (coverage, Gini, novelty, diversity,
+ *          unexpectedness; no reference line)          -> hrec_row_inv_norms,
+ *                                                          hrec_list_quality
  *   Keras  two-tower graph    src/two_tower_model.py:38-89 -> hrec_tt_*
  *   Keras  Dot + sorted(...)[:k] for many users        -> hrec_dot_topk
  *          the same minus a training frame's pairs
@@ -772,6 +775,67 @@ int hrec_rank_positions(int64_t n_rows, int64_t n, int source, const void* score
                         const int64_t* excl_indptr, const int32_t* excl_cols, int32_t* out_rank,
                         double* out_row, int32_t* out_row_n, double* sums_out, void* workspace,
                         size_t workspace_bytes, void* stream);
+
+/* What the served lists look like as a whole (additive to ABI 7): per list
+ * its intra-list diversity, its unexpectedness against the user's history and
+ * the means of per-item tables (novelty, popularity), and every item's
+ * exposure over all lists.
+ *
+ * hrec_row_inv_norms: out[j] (f64, j < n) = 1 / sqrt(sum_c (double)v_jc^2) of
+ * row j of vectors (f32 [n][ld], the first d columns), 0.0 when the sum is 0
+ * or not finite: such an item is a zero vector below, whatever its components
+ * are. 1 <= d <= 256, ld >= d, n < 2^31; n == 0 returns HREC_OK. One wave per
+ * row: lane-strided f64 partials, then a fixed xor tree.
+ *
+ * hrec_list_quality: lists [n_rows][lists_ld] int64 holds candidate COLUMNS
+ * (what every top-k here returns before the id gather: hrec_hybrid_lists'
+ * out_idx, a hrec_topk_* / hrec_dot_topk* / hrec_als_score_topk* result), row
+ * r's list in its first min(list_len[r], list_n) entries (list_len int32
+ * [n_rows]; NULL: list_n). 0 <= list_n <= 1024, lists_ld >= list_n. vectors
+ * f32 [n][ld] (1 <= d <= 256, ld >= d) and inv_norm f64 [n] (hrec_row_inv_norms
+ * of them) describe the n candidates, 1 <= n < 2^31.
+ * History (optional; a CSR shaped and addressed like the exclusion triple of
+ * hrec_hybrid_lists): row r reads hist_cols[hist_indptr[q] .. hist_indptr[q +
+ * 1]) with q = hist_rows[r]; q < 0, or all three pointers NULL: no history.
+ * item_tables f64 [n_tab][n], 0 <= n_tab <= HREC_LQ_MAX_TABLES (NULL when 0).
+ * An entry is valid when its position is below the row's length and its
+ * column is in [0, n); every other entry (-1 included) is ignored everywhere
+ * and never used as an index. The same holds for history columns (a history
+ * column that appears twice counts twice). The entries of one list are
+ * distinct items.
+ * With the valid list entries a = 1..m, the valid history entries h = 1..g
+ * and x_j = (double)v_j * inv_norm[j] componentwise (the zero vector where
+ * inv_norm[j] == 0), all arithmetic f64 and unfused:
+ *   S = sum_a x_a, Q = sum_a x_a.x_a, H = sum_h x_h;
+ *   intraListDiversity = 1 - (S.S - Q) / (m (m - 1)): one minus the mean cosine
+ *     over the pairs of distinct list entries; NaN when m < 2;
+ *   unexpectedness = 1 - (S.H) / (m g): one minus the mean cosine between a
+ *     list entry and a history entry; NaN when m == 0 or g == 0;
+ *   per table t the mean of item_tables[t][col_a] over the entries where it
+ *     is not NaN; NaN when there is none;
+ *   exposure[col_a] += 1 (int64 [n], in and out) for every valid list entry,
+ *     by integer atomics: the result does not depend on arrival order.
+ * Outputs: per_row f64 [n_rows][2 + n_tab] = diversity, unexpectedness, the
+ * table means; row_n int32 [n_rows][2 + n_tab] = m, g, then the counted
+ * entries per table. sums_out f64 [2 * (2 + n_tab)] (device, IN AND OUT): the
+ * call adds, per column, the sum over the rows where it is defined, then per
+ * column the count of those rows; zero it before the first call of a series.
+ * Lane l of a row's wave owns components l, l + 64, l + 128, l + 192 of S, H
+ * and its part of Q; a row ends in three wave reductions (fixed xor trees).
+ * Per-block partials in the workspace, added in a fixed order by a second
+ * launch, no floating-point atomics: equal inputs give equal bits on every
+ * call. n_rows == 0 returns HREC_OK and touches nothing.
+ * Workspace: hrec_list_quality_workspace_bytes(n_rows). */
+#define HREC_LQ_MAX_TABLES 4
+int hrec_row_inv_norms(const float* vectors, int64_t n, int d, int64_t ld, double* out,
+                       void* stream);
+size_t hrec_list_quality_workspace_bytes(int64_t n_rows);
+int hrec_list_quality(const int64_t* lists, int64_t lists_ld, int list_n, const int32_t* list_len,
+                      int64_t n_rows, int64_t n, const float* vectors, int d, int64_t ld,
+                      const double* inv_norm, const int64_t* hist_rows, const int64_t* hist_indptr,
+                      const int32_t* hist_cols, const double* item_tables, int n_tab,
+                      int64_t* exposure, double* per_row, int32_t* row_n, double* sums_out,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------ cold-start sim --
  * ALSModel._find_similar_items (src/als_model.py:93-104): out[q*n_items+j] =
