@@ -107,6 +107,8 @@ _SIGNATURES = {
     "hrec_list_quality_workspace_bytes": (_c_sz, [_c_i64]),
     "hrec_list_quality": (_c_i32, [_vp, _c_i64, _c_i32, _vp, _c_i64, _c_i64, _vp, _c_i32, _c_i64, _vp, _vp, _vp, _vp,
                                    _vp, _c_i32, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "hrec_mmr_rerank": (_c_i32, [_vp, _c_i64, _c_i32, _vp, _vp, _c_i32, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _c_i64, _vp,
+                                 _c_dbl, _c_i32, _vp, _vp, _vp, _vp]),
     "hrec_fuse_workspace_bytes": (_c_sz, [_c_i64, _c_i32]),
     "hrec_fuse_topk": (_c_i32, [_vp, _vp, _c_i32, _c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp,
                                 _c_sz, _vp]),
@@ -2002,6 +2004,46 @@ def list_quality(lists, vectors, inv_norm, list_len=None, history=None, tables=N
         _dev(per_row, torch.float64, "per_row"), _dev(row_n, torch.int32, "row_n"), _dev(sums, torch.float64, "sums"),
         _dev(ws, torch.uint8, "ws"), need, _stream()))
     return per_row, row_n, exposure, sums
+
+
+# ------------------------------------------------------------ MMR re-ranking
+MMR_POOL_MAX = 1024  # longest pool
+
+
+def mmr_rerank(pool, scores, vectors, inv_norm, lambda_, top_n, pool_len=None, d=None, want_value=False):
+    """hrec_mmr_rerank: greedy Maximal Marginal Relevance over every row of
+    `pool` (int64 [n_rows, P <= 1024] device candidate columns, best first, the
+    first pool_len[r] (int32; None: P) entries) with the ratings `scores` (f32
+    or f64 [n_rows, P]) at the same positions; views with a row stride are
+    fine. vectors f32 [n, >= d] with inv_norm = row_inv_norms(vectors, d).
+    Returns device (out_pos int32 [n_rows, top_n]: the selected positions in
+    the pool row in selection order, -1 past out_len; out_len int32 [n_rows];
+    out_value f64 [n_rows, top_n] or None). The same bits on every call."""
+    name = "mmr_rerank"
+    v_ptr, n, d, ld = _vector_rows(name, vectors, d)
+    dev = vectors.device
+    if not isinstance(pool, torch.Tensor) or pool.dim() != 2:
+        raise HrecError(f"{name}: pool must be a 2-D device tensor")
+    n_rows, pool_n = int(pool.shape[0]), int(pool.shape[1])
+    if not isinstance(scores, torch.Tensor) or scores.dtype not in (torch.float32, torch.float64) \
+            or tuple(scores.shape) != (n_rows, pool_n):
+        raise HrecError(f"{name}: scores must be a float32 or float64 device tensor of the pool's shape")
+    p_ptr, pool, p_ld = _rows_matrix(name, "pool", pool, torch.int64, n_rows)
+    s_ptr, scores, s_ld = _rows_matrix(name, "scores", scores, scores.dtype, n_rows)
+    if inv_norm.numel() != n:
+        raise HrecError(f"{name}: inv_norm must hold one value per vector")
+    if pool_len is not None and pool_len.numel() != n_rows:
+        raise HrecError(f"{name}: pool_len must have one entry per row")
+    top_n = int(top_n)
+    out_pos = torch.empty((n_rows, max(top_n, 0)), dtype=torch.int32, device=dev)
+    out_len = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    out_value = torch.empty((n_rows, max(top_n, 0)), dtype=torch.float64, device=dev) if want_value else None
+    _check("hrec_mmr_rerank", lib().hrec_mmr_rerank(
+        p_ptr, p_ld, pool_n, _dev(pool_len, torch.int32, "pool_len"), s_ptr, int(scores.dtype == torch.float64), s_ld,
+        n_rows, n, v_ptr, d, ld, _dev(inv_norm, torch.float64, "inv_norm"), float(lambda_), top_n,
+        _dev(out_pos, torch.int32, "out_pos"), _dev(out_len, torch.int32, "out_len"),
+        _dev(out_value, torch.float64, "out_value"), _stream()))
+    return out_pos, out_len, out_value
 
 
 # ------------------------------------------------------- multi-GPU (C-ABI)

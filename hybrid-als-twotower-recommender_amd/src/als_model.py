@@ -220,7 +220,7 @@ class DeviceALSFactors:
             cols_sorted=True, device_keys=lambda: tuple(self._ids_device(s) for s in sides),
             what="user_ids and item_ids")
 
-    def recommend(self, side, rows, num, exclude=None, _columns=False):
+    def recommend(self, side, rows, num, exclude=None, _columns=False, diversify=None):
         """Top-`num` of the other side for each of `rows` (int64 row indices
         into `side`'s factor matrix, every one in range): device (ids int64
         [n, kk], scores f32 [n, kk]), kk = min(num, size of the other side).
@@ -245,8 +245,23 @@ class DeviceALSFactors:
         One flag per batch and level; one host read after the last batch of
         the first level, a second only if that one found a flag.
         _columns (internal): return (row indices of the other side int64
-        [n, kk], lens or None) instead: the lists before the id gather."""
+        [n, kk], scores, lens or None) instead: the lists before the id gather.
+        diversify (optional, side "user" only): a ranked_lists.MMR. The top
+        max(pool, num) items are ranked as above (after exclude), then
+        hrec_mmr_rerank picks num of them by greedy Maximal Marginal Relevance
+        with cosines between item factors. The lists are in SELECTION order,
+        no longer descending by score; a score keeps the bits the plain list
+        has for that item."""
         num = ranked_lists.check_num(num, self.RECOMMEND_MAX)
+        if diversify is not None:
+            mmr = ranked_lists.check_mmr(diversify)
+            if side != "user":
+                raise ValueError("diversify re-ranks the item lists of users: side must be 'user'")
+            pool = self.recommend(side, rows, max(num, mmr.pool), exclude, _columns=True)
+            ids = self._recommend_operands(side)[4]
+            picked = ranked_lists.diversify(*pool, self.V, None, self.k, mmr, num)
+            out = ranked_lists.diversify_finish(ids, *picked, int(self.V.shape[0]), _columns, exclude is not None)
+            return out if _columns or exclude is not None else out[:2]
         Q, F, Ft, bf, ids = self._recommend_operands(side)
         dev = Q.device
         excl = exclude is not None
@@ -263,7 +278,7 @@ class DeviceALSFactors:
         lens = torch.zeros(n, dtype=torch.int32, device=dev) if excl else None
         outs = (out_i, out_v, lens) if excl else (out_i, out_v)
         if n == 0 or kk == 0:
-            return (out_i, lens) if _columns else outs
+            return (out_i, out_v, lens) if _columns else outs
         if bool(((rows < 0) | (rows >= Q.shape[0])).any().item()):
             raise ValueError(f"recommend: a {side} row is outside [0, {Q.shape[0]})")
         B = int(self.RECOMMEND_BATCH)
@@ -299,7 +314,7 @@ class DeviceALSFactors:
                                     starts[b], min(starts[b] + B, n), n_other, kk, self.RECOMMEND_FALLBACK_BYTES,
                                     out_i, out_v, lens, (rows, indptr, cols) if excl else None)
         if _columns:
-            return out_i, lens
+            return out_i, out_v, lens
         if not excl:
             return ids[out_i], out_v
         return (*ranked_lists.pad_lists(ids, out_i, out_v, lens, n_other), lens)
@@ -850,10 +865,12 @@ class ALSModel:
         """The device exclusion CSR of an `exclude` frame (columns userId, itemId)."""
         return self.model.exclusion(side, _int_ids(exclude["userId"], "userId"), _int_ids(exclude["itemId"], "itemId"))
 
-    def _recommend_frame(self, side, subset, num, exclude=None):
+    def _recommend_frame(self, side, subset, num, exclude=None, diversify=None):
         import pandas as pd
 
         model = self._trained()
+        if diversify is not None and side != "user":
+            raise ValueError("diversify re-ranks the item lists of users; the user lists of items are not diversified")
         col, ids = ("userId", model.user_ids) if side == "user" else ("itemId", model.item_ids)
         ids = np.asarray(ids, np.int64)
         if subset is None:
@@ -865,12 +882,13 @@ class ALSModel:
             rows = model._lookup(ids, keys)
             rows = rows[rows >= 0]  # ids the model does not know are left out (Spark's join)
         if exclude is None:
-            (rec_ids, scores), lens = model.recommend(side, rows, num), None
+            (rec_ids, scores), lens = model.recommend(side, rows, num, diversify=diversify), None
         else:
-            rec_ids, scores, lens = model.recommend(side, rows, num, exclude=self._exclusion(side, exclude))
+            rec_ids, scores, lens = model.recommend(side, rows, num, exclude=self._exclusion(side, exclude),
+                                                    diversify=diversify)
         return ranked_lists.lists_frame(col, ids[rows], rec_ids, scores, lens)
 
-    def recommend_for_all_users(self, num_items, exclude=None):
+    def recommend_for_all_users(self, num_items, exclude=None, diversify=None):
         """Spark's recommendForAllUsers: a DataFrame with one row per user
         of the model, `userId` ascending, and `recommendations`: the user's
         top num_items (1 .. 1024) items as (itemId: int, rating: float)
@@ -885,31 +903,41 @@ class ALSModel:
         full ranking without them, cut to num_items, so it is shorter than
         num_items only when fewer entries remain; a row with everything
         excluded keeps its row with an empty list. Pairs with an id the model
-        does not know, and repeated pairs, change nothing."""
-        return self._recommend_frame("user", None, num_items, exclude)
+        does not know, and repeated pairs, change nothing.
+        diversify (optional; here, in recommend_for_user_subset and in the
+        ranking and list-quality metrics below): a ranked_lists.MMR(lambda_,
+        pool). The model ranks max(pool, num_items) items (after exclude) and
+        greedy Maximal Marginal Relevance picks num_items of them, each pick
+        trading its rating (min-max scaled over the pool) against its largest
+        cosine, between item factors, to the picks before. The lists are then
+        in SELECTION order, no longer descending by rating; a tuple keeps the
+        rating bits the plain list has for that item. None: the plain ranking."""
+        return self._recommend_frame("user", None, num_items, exclude, diversify)
 
-    def recommend_for_all_items(self, num_users, exclude=None):
+    def recommend_for_all_items(self, num_users, exclude=None, diversify=None):
         """Spark's recommendForAllItems: per item (`itemId` ascending) its
-        top num_users users as (userId, rating) tuples."""
-        return self._recommend_frame("item", None, num_users, exclude)
+        top num_users users as (userId, rating) tuples. diversify is not
+        supported on the item side: anything but None raises ValueError."""
+        return self._recommend_frame("item", None, num_users, exclude, diversify)
 
-    def recommend_for_user_subset(self, users, num_items, exclude=None):
+    def recommend_for_user_subset(self, users, num_items, exclude=None, diversify=None):
         """Spark's recommendForUserSubset: recommend_for_all_users for the
         distinct ids of `users` (a DataFrame with a userId column, or an
         array-like of ids); ids unknown to the model are left out."""
-        return self._recommend_frame("user", users, num_items, exclude)
+        return self._recommend_frame("user", users, num_items, exclude, diversify)
 
-    def recommend_for_item_subset(self, items, num_users, exclude=None):
+    def recommend_for_item_subset(self, items, num_users, exclude=None, diversify=None):
         """Spark's recommendForItemSubset (a DataFrame with an itemId column,
-        or an array-like of ids)."""
-        return self._recommend_frame("item", items, num_users, exclude)
+        or an array-like of ids). diversify is not supported on the item side:
+        anything but None raises ValueError."""
+        return self._recommend_frame("item", items, num_users, exclude, diversify)
 
     # ----------------------------------------- RankingEvaluator / RankingMetrics
     RANKING_METRIC_NAMES = ("meanAveragePrecision", "meanAveragePrecisionAtK", "precisionAtK", "recallAtK",
                             "ndcgAtK")
     RANKING_HOST_ROWS = 1 << 16  # frames up to this many rows: the label CSR is built on the host
 
-    def ranking_metrics(self, data, k=10, label_col=None, min_rating=None, exclude=None):
+    def ranking_metrics(self, data, k=10, label_col=None, min_rating=None, exclude=None, diversify=None):
         """Spark's RankingMetrics (binary relevance) of the model's top-k item
         lists against `data` (columns userId, itemId): {"meanAveragePrecision",
         "meanAveragePrecisionAtK", "precisionAtK", "recallAtK", "ndcgAtK",
@@ -927,8 +955,13 @@ class ALSModel:
         typically the training frame of a held-out split; the lists are
         ranked without its pairs (recommend_for_all_users' exclude), each
         evaluated at its own length. An item of `data` that is also excluded
-        can never be hit and still counts in its user's set size."""
+        can never be hit and still counts in its user's set size.
+        diversify (optional): recommend_for_all_users' MMR; the metrics are
+        those of the diversified lists, in selection order, which go from
+        hrec_mmr_rerank into hrec_ranking_metrics on the device."""
         k = ranked_lists.check_num(k, _hrec.RANK_MAX, "k")
+        if diversify is not None:
+            ranked_lists.check_mmr(diversify)
         users, items = self._pair_ids(data)
         if min_rating is not None:
             keep = np.asarray(data[label_col or "average_review_rating"], np.float64) >= float(min_rating)
@@ -957,8 +990,8 @@ class ALSModel:
         def lists(r):
             """(ids, lens) of the rows' lists; lens None: every list is full."""
             if excl is None:
-                return model.recommend("user", r, k)[0], None
-            top, _, lens = model.recommend("user", r, k, exclude=excl)
+                return model.recommend("user", r, k, diversify=diversify)[0], None
+            top, _, lens = model.recommend("user", r, k, exclude=excl, diversify=diversify)
             return top, lens
 
         if n_known == n:
@@ -973,12 +1006,12 @@ class ALSModel:
         return res
 
     def evaluate_ranking(self, data, metric_name="meanAveragePrecision", k=10, label_col=None, min_rating=None,
-                         exclude=None):
+                         exclude=None, diversify=None):
         """Spark's RankingEvaluator(metricName=metric_name, k=k).evaluate of
-        the model's lists for the users of `data` (a float); exclude as in
-        ranking_metrics."""
+        the model's lists for the users of `data` (a float); exclude and
+        diversify as in ranking_metrics."""
         ranked_lists.check_metric_name(metric_name, self.RANKING_METRIC_NAMES)
-        return float(self.ranking_metrics(data, k, label_col, min_rating, exclude)[metric_name])
+        return float(self.ranking_metrics(data, k, label_col, min_rating, exclude, diversify)[metric_name])
 
     # ------------------------------------------------------------ list quality
     # What the served lists look like as a whole: coverage, concentration,
@@ -987,7 +1020,7 @@ class ALSModel:
     LIST_QUALITY_METRIC_NAMES = ranked_lists.LIST_QUALITY_NAMES
     LIST_QUALITY_ROWS = 1 << 16  # users of one recommend + hrec_list_quality sub-batch
 
-    def list_quality_metrics(self, k=10, users=None, exclude=None, history=None):
+    def list_quality_metrics(self, k=10, users=None, exclude=None, history=None, diversify=None):
         """The beyond-accuracy measures of the model's top-k item lists
         (recommend_for_all_users(k, exclude) / recommend_for_user_subset(users,
         k, exclude)), which never leave the device: {"catalogCoverage",
@@ -1003,10 +1036,14 @@ class ALSModel:
         items, h_i the frame's distinct pairs of item i; averagePopularity =
         the mean of h_i / the frame's distinct users; unexpectedness = one
         minus the mean cosine between a listed item and an item of the user's
-        own history. Without it those three are NaN."""
+        own history. Without it those three are NaN. diversify (optional):
+        recommend_for_all_users' MMR; the measures are those of the
+        diversified lists, which stay on the device."""
         import pandas as pd
 
         model = self._trained()
+        if diversify is not None:
+            ranked_lists.check_mmr(diversify)
         dev = model.U.device
         k = ranked_lists.check_num(k, model.RECOMMEND_MAX, "k")
         ids = np.asarray(model.user_ids, np.int64)
@@ -1029,17 +1066,18 @@ class ALSModel:
         def batches():
             for lo in range(0, rows.size, self.LIST_QUALITY_ROWS):
                 r = torch.as_tensor(rows[lo: lo + self.LIST_QUALITY_ROWS], device=dev)
-                cols, lens = model.recommend("user", r, k, exclude=excl, _columns=True)
+                cols, _, lens = model.recommend("user", r, k, exclude=excl, _columns=True, diversify=diversify)
                 yield cols, lens, None if hist is None else (r, *hist)
 
         res = ranked_lists.list_quality(batches, model.V, model.k, k, tables)
         res["dropped"] = dropped
         return res
 
-    def evaluate_list_quality(self, metric_name="catalogCoverage", k=10, users=None, exclude=None, history=None):
+    def evaluate_list_quality(self, metric_name="catalogCoverage", k=10, users=None, exclude=None, history=None,
+                              diversify=None):
         """One of list_quality_metrics' eight measures (a float)."""
         ranked_lists.check_metric_name(metric_name, self.LIST_QUALITY_METRIC_NAMES)
-        return float(self.list_quality_metrics(k, users, exclude, history)[metric_name])
+        return float(self.list_quality_metrics(k, users, exclude, history, diversify)[metric_name])
 
     # --------------------------------- positions in the full catalogue
     # Where every held-out item stands among ALL items of the model: what the

@@ -258,6 +258,53 @@ class RecommenderEvaluator:
         return ranked_lists.list_quality(batches, v, int(v.shape[1]), max(int(cols.shape[1]), 1), tables)
 
     @staticmethod
+    def diversify_lists(lists, item_ids, vectors, mmr, num):
+        """Greedy Maximal Marginal Relevance over any lists frame (not in the
+        reference): `lists`, `item_ids` and `vectors` as in evaluate_lists,
+        each list a pool of (itemId, rating) tuples, best first, of at most
+        1024 entries; mmr a ranked_lists.MMR (its lambda_ is used; the pool is
+        the list as given). Returns a frame with the same first column and
+        `recommendations`: per list min(num, its entries inside item_ids) of
+        its own tuples, unchanged, in SELECTION order (hrec_mmr_rerank: each
+        pick trades its rating, min-max scaled over the list, against its
+        largest cosine to the picks before). A tuple whose itemId is outside
+        item_ids is never picked. num > the longest list is clipped to it."""
+        import pandas as pd
+
+        _hrec.require_device()
+        mmr = ranked_lists.check_mmr(mmr)
+        num = ranked_lists.check_num(num, ranked_lists.MMR.POOL_MAX, "num")
+        iid = ranked_lists.int_ids(np.asarray(item_ids).reshape(-1), "item_ids")
+        if np.unique(iid).size != iid.size:
+            raise ValueError("diversify_lists: item_ids must not repeat an id")
+        v = vectors if isinstance(vectors, torch.Tensor) else torch.as_tensor(np.asarray(vectors, np.float32))
+        if v.dim() != 2 or v.shape[0] != iid.size or not 1 <= v.shape[1] <= _hrec.LQ_MAX_D:
+            raise ValueError(f"diversify_lists: vectors must be [len(item_ids), 1 .. {_hrec.LQ_MAX_D}]")
+        v = v.to(torch.float32).cuda().contiguous()
+        dev = v.device
+        recs = list(lists["recommendations"])
+        cols, lens = ranked_lists.lists_frame_columns(lists, iid)
+        if cols.shape[1] > ranked_lists.MMR.POOL_MAX:
+            raise ValueError(f"diversify_lists: a list is longer than {ranked_lists.MMR.POOL_MAX}")
+        key = lists.columns[0]
+        if cols.shape[1] == 0 or iid.size == 0:
+            return pd.DataFrame({key: lists[key].to_numpy(), "recommendations": [[] for _ in recs]})
+        scores = np.full(cols.shape, np.nan, np.float64)
+        scores[np.arange(cols.shape[1])[None, :] < lens[:, None]] = [float(s) for r in recs for _, s in r]
+        inv = _hrec.row_inv_norms(v)
+        kk = min(num, int(cols.shape[1]))
+        out = []
+        for lo in range(0, cols.shape[0], EVALUATE_ROWS):
+            sl = slice(lo, lo + EVALUATE_ROWS)
+            pos, out_len, _ = _hrec.mmr_rerank(torch.as_tensor(cols[sl], device=dev),
+                                               torch.as_tensor(scores[sl], device=dev), v, inv, mmr.lambda_, kk,
+                                               pool_len=torch.as_tensor(lens[sl], device=dev))
+            out.append(torch.cat([pos, out_len.unsqueeze(1)], dim=1))
+        host = torch.cat(out).cpu().numpy()
+        picked = [[r[p] for p in row[:row[-1]]] for r, row in zip(recs, host.tolist())]
+        return pd.DataFrame({key: lists[key].to_numpy(), "recommendations": picked})
+
+    @staticmethod
     def summarize(frame):
         """Per metric column of an evaluate_scores / evaluate_users frame: its
         mean over the users where it is defined (not NaN) and their count, as

@@ -422,7 +422,8 @@ class HybridRecommendationSystem:
                     lists_pass(s1, e1, a, t, 1)
         return f1, wins, idx, val, lens
 
-    def _recommend_device(self, users, cand, num, exclude=None, actual=None, f1_k=10, _columns=False):
+    def _recommend_device(self, users, cand, num, exclude=None, actual=None, f1_k=10, _columns=False, diversify=None,
+                          similarity="twotower"):
         """Top-`num` fused candidates for each of `users` (TwoTowerModel.
         _query_users' array): device (raw itemIds int64 [n, kk], fused scores
         f64 [n, kk], lens int32 [n] or None when every list is full), kk =
@@ -431,17 +432,25 @@ class HybridRecommendationSystem:
         whose overflow flag is set — read back once, after the last one — are
         redone in mode 1. With `actual`: _adaptive_device, each user with
         rows there fused by its own two F1@f1_k. _columns (internal): return
-        (candidate frame rows int64 [n, kk], lens int32 [n]) instead: the
-        lists before the id gather."""
+        (candidate frame rows int64 [n, kk], scores, lens int32 [n]) instead:
+        the lists before the id gather. diversify (optional): a
+        ranked_lists.MMR; the top max(pool, num) are ranked as above and
+        hrec_mmr_rerank picks num of them, in selection order, with cosines
+        between _similarity_vectors(cand, similarity)."""
         num = ranked_lists.check_num(num, self.RECOMMEND_MAX, "num_items")
         f1_k = ranked_lists.check_num(f1_k, self.RECOMMEND_MAX, "f1_k")
         tt = self.twotower_model
         dev = tt.model.device
         n, N = int(users.size), len(cand)
         kk = min(num, N)
+        if diversify is not None:
+            mmr = ranked_lists.check_mmr(diversify)
+            vectors, d = self._similarity_vectors(cand, similarity)
+            pool = self._recommend_device(users, cand, max(num, mmr.pool), exclude, actual, f1_k, _columns=True)
+            picked = ranked_lists.diversify(*pool, vectors, None, d, mmr, num)
+            return ranked_lists.diversify_finish(cand.ids_dev, *picked, N, _columns, exclude is not None)
         if n == 0 or kk == 0:
-            empty = ranked_lists.empty_lists(n, kk, torch.float64, dev, exclude is not None or _columns)
-            return empty[::2] if _columns else empty
+            return ranked_lists.empty_lists(n, kk, torch.float64, dev, exclude is not None or _columns)
         excl = tt._exclusion(users, cand, exclude) if exclude is not None else None
         fallback = self._als_fallback(users, cand.item_ids)
         als_wins = self.als_f1_score > self.twotower_f1_score
@@ -449,7 +458,7 @@ class HybridRecommendationSystem:
             _, _, idx, val, lens = self._adaptive_device(users, cand, kk, excl, fallback,
                                                          self._labels(users, cand, actual), f1_k, als_wins)
             if _columns:
-                return idx, lens
+                return idx, val, lens
             ids, val = ranked_lists.pad_lists(cand.ids_dev, idx, val, lens, N)
             return ids, val, (None if exclude is None else lens)
         rows = torch.arange(n, dtype=torch.int64, device=dev)  # query q reads exclusion row q
@@ -471,11 +480,12 @@ class HybridRecommendationSystem:
                 for s1, e1 in self._spans(s, e, N, 16):
                     run(s1, e1, 1)
         if _columns:
-            return idx, lens
+            return idx, val, lens
         ids, val = ranked_lists.pad_lists(cand.ids_dev, idx, val, lens, N)
         return ids, val, (None if exclude is None else lens)
 
-    def recommend_for_users(self, users, item_features, num_items, exclude=None, actual=None, f1_k=10):
+    def recommend_for_users(self, users, item_features, num_items, exclude=None, actual=None, f1_k=10,
+                            diversify=None, similarity="twotower"):
         """Top-n lists of the fused model for many users in one device pass:
         a DataFrame with `userId` (the distinct ids of `users`, ascending; a
         DataFrame with a userId column or an array-like) and `recommendations`:
@@ -519,18 +529,30 @@ class HybridRecommendationSystem:
         leaves the last evaluated user's scores there). Within a
         model's top f1_k equal scores keep frame order and NaN scores rank
         last in frame order; for non-finite two-tower scores the reference's
-        order is Python's unspecified one and is not reproduced."""
+        order is Python's unspecified one and is not reproduced.
+        diversify (optional; here and in the methods below): a
+        ranked_lists.MMR(lambda_, pool). The fused model ranks max(pool,
+        num_items) candidates (after exclude) and greedy Maximal Marginal
+        Relevance picks num_items of them, each pick trading its fused score
+        (min-max scaled over the pool) against its largest cosine to the picks
+        before; similarity chooses the vectors as in list_quality_metrics
+        ("twotower": the candidates' item-tower vectors, "als": the ALS item
+        factors). The lists are then in SELECTION order, no longer descending
+        by score; a tuple keeps the score bits the plain list has for that
+        item. None: the plain ranking (similarity is not read)."""
         self._require_models()
         cand = self.twotower_model.candidates(item_features)
         users = self.twotower_model._query_users(users)
-        ids, val, lens = self._recommend_device(users, cand, num_items, exclude, actual, f1_k)
+        ids, val, lens = self._recommend_device(users, cand, num_items, exclude, actual, f1_k, diversify=diversify,
+                                                similarity=similarity)
         return ranked_lists.lists_frame("userId", users, ids, val, lens)
 
-    def recommend_for_all_users(self, item_features, num_items, exclude=None, actual=None, f1_k=10):
+    def recommend_for_all_users(self, item_features, num_items, exclude=None, actual=None, f1_k=10, diversify=None,
+                                similarity="twotower"):
         """recommend_for_users for every user of the two-tower user table."""
         self._require_models()
         return self.recommend_for_users(np.arange(int(self.twotower_model.num_users), dtype=np.int64), item_features,
-                                        num_items, exclude, actual, f1_k)
+                                        num_items, exclude, actual, f1_k, diversify, similarity)
 
     # What the fused lists look like as a whole: ALSModel.list_quality_metrics
     # / evaluate_list_quality for recommend_for_users' lists. No counterpart
@@ -553,7 +575,7 @@ class HybridRecommendationSystem:
         return vec.contiguous(), m.k
 
     def list_quality_metrics(self, item_features, k=10, users=None, exclude=None, history=None, actual=None, f1_k=10,
-                             similarity="twotower"):
+                             similarity="twotower", diversify=None):
         """ALSModel.list_quality_metrics for the fused top-k lists over the
         candidates of `item_features` (recommend_for_users(users,
         item_features, k, exclude, actual, f1_k); users None: every user of
@@ -564,18 +586,23 @@ class HybridRecommendationSystem:
         a DataFrame with userId and itemId columns (typically the training
         frame). "dropped" is 0: a user id outside the two-tower table raises
         IndexError, and users the ALS model does not know are served through
-        its cold-start values as in recommend_for_users."""
+        its cold-start values as in recommend_for_users. diversify: the
+        measures of recommend_for_users' diversified lists; the selection and
+        the measures use the same `similarity` vectors."""
         self._require_models()
         tt = self.twotower_model
         cand = tt.candidates(item_features)
         k = ranked_lists.check_num(k, self.RECOMMEND_MAX, "k")
+        if diversify is not None:
+            ranked_lists.check_mmr(diversify)
         users = tt._query_users(np.arange(int(tt.num_users), dtype=np.int64) if users is None else users)
         dev = tt.model.device
         vectors, d = self._similarity_vectors(cand, similarity)
         hist, tables = tt._history(users, cand, history)
 
         def batches():
-            cols, lens = self._recommend_device(users, cand, k, exclude, actual, f1_k, _columns=True)
+            cols, _, lens = self._recommend_device(users, cand, k, exclude, actual, f1_k, _columns=True,
+                                                   diversify=diversify, similarity=similarity)
             rows = torch.arange(int(users.size), dtype=torch.int64, device=dev)  # query q reads history row q
             yield cols, lens, None if hist is None else (rows, *hist)
 
@@ -584,11 +611,11 @@ class HybridRecommendationSystem:
         return res
 
     def evaluate_list_quality(self, item_features, metric_name="catalogCoverage", k=10, users=None, exclude=None,
-                              history=None, actual=None, f1_k=10, similarity="twotower"):
+                              history=None, actual=None, f1_k=10, similarity="twotower", diversify=None):
         """One of list_quality_metrics' eight measures (a float)."""
         ranked_lists.check_metric_name(metric_name, self.LIST_QUALITY_METRIC_NAMES)
         return float(self.list_quality_metrics(item_features, k, users, exclude, history, actual, f1_k,
-                                               similarity)[metric_name])
+                                               similarity, diversify)[metric_name])
 
     def evaluate_models(self, data, item_features, k=10):
         """evaluate_individual_models for every user of `data` (columns
@@ -721,7 +748,7 @@ class HybridRecommendationSystem:
                 for i, m in enumerate(models)}
 
     def ranking_metrics(self, data, item_features, k=10, label_col=None, min_rating=None, exclude=None, actual=None,
-                        f1_k=10):
+                        f1_k=10, diversify=None, similarity="twotower"):
         """Spark's RankingMetrics (binary relevance) of the fused model's top-k
         lists over `item_features` against `data` (columns userId, itemId):
         the five RANKING_METRIC_NAMES plus "count", with TwoTowerModel.
@@ -730,21 +757,25 @@ class HybridRecommendationSystem:
         metric the mean over the `count` users, NaN when count is 0; each list
         evaluated at its own length). exclude, actual and f1_k as in
         recommend_for_users. The lists go from hrec_hybrid_lists into hrec_ranking_metrics without
-        leaving the device."""
+        leaving the device. diversify and similarity as in recommend_for_users:
+        the metrics of the diversified lists, in selection order."""
         self._require_models()
         tt = self.twotower_model
         cand = tt.candidates(item_features)
+        if diversify is not None:
+            ranked_lists.check_mmr(diversify)
         return ranked_lists.ranking_metrics(
             data, k, label_col, min_rating, tt.model.device, self.RANKING_HOST_ROWS, self.RANKING_METRIC_NAMES,
-            lambda users, k: self._recommend_device(tt._query_users(users), cand, k, exclude, actual, f1_k)[::2])
+            lambda users, k: self._recommend_device(tt._query_users(users), cand, k, exclude, actual, f1_k,
+                                                    diversify=diversify, similarity=similarity)[::2])
 
     def evaluate_ranking(self, data, item_features, metric_name="meanAveragePrecision", k=10, label_col=None,
-                         min_rating=None, exclude=None, actual=None, f1_k=10):
+                         min_rating=None, exclude=None, actual=None, f1_k=10, diversify=None, similarity="twotower"):
         """Spark's RankingEvaluator(metricName=metric_name, k=k).evaluate of
         the fused model's lists for the users of `data` (a float)."""
         ranked_lists.check_metric_name(metric_name, self.RANKING_METRIC_NAMES)
         return float(self.ranking_metrics(data, item_features, k, label_col, min_rating, exclude, actual,
-                                          f1_k)[metric_name])
+                                          f1_k, diversify, similarity)[metric_name])
 
     # --------------------------------- positions in the full catalogue
     FULL_RANKING_METRIC_NAMES = ranked_lists.FULL_RANK_NAMES

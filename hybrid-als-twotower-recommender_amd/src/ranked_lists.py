@@ -443,6 +443,69 @@ def lists_frame_columns(lists, item_ids):
     return cols, lens
 
 
+# ------------------------------------------------- diversity-aware re-ranking
+# Greedy Maximal Marginal Relevance (Carbonell and Goldstein 1998): the model
+# ranks a longer pool, hrec_mmr_rerank picks the final list from it so that
+# each pick trades its relevance against its similarity to the picks before.
+class MMR:
+    """The `diversify=` argument of the list APIs. lambda_ in [0, 1]: 1 keeps
+    the model's ranking, 0 looks at similarity alone (after the first pick);
+    pool in [1, 1024]: how many of the model's best candidates the selection
+    chooses from (at least the list length asked for is always ranked)."""
+
+    POOL_MAX = _hrec.MMR_POOL_MAX
+
+    def __init__(self, lambda_=0.7, pool=100):
+        lambda_ = float(lambda_)
+        if not 0.0 <= lambda_ <= 1.0:  # NaN fails too
+            raise ValueError(f"lambda_ must be in [0, 1] (got {lambda_})")
+        self.lambda_ = lambda_
+        self.pool = check_num(pool, self.POOL_MAX, "pool")
+
+    def __repr__(self):
+        return f"MMR(lambda_={self.lambda_}, pool={self.pool})"
+
+
+def check_mmr(mmr):
+    if not isinstance(mmr, MMR):
+        raise TypeError(f"diversify must be an MMR (got {type(mmr).__name__})")
+    return mmr
+
+
+def diversify(cols, scores, lens, vectors, inv, d, mmr, num):
+    """The MMR selection of `num` entries from every row's pool: cols int64
+    device [n, P <= 1024] candidate columns best first (what a top-k returns
+    before the id gather), scores f32 / f64 [n, P] their ratings, lens int32
+    [n] or None (every pool full). vectors f32 device [candidates, >= d], inv
+    = _hrec.row_inv_norms(vectors, d) (None: made here). Returns (cols [n,
+    kk], scores [n, kk], lens int32 [n]), kk = min(num, P), in SELECTION order
+    (not descending by score); a score keeps its bits; past a list's length
+    column -1 and score NaN. hrec_mmr_rerank, then two torch.gather."""
+    mmr = check_mmr(mmr)
+    n, pool_n = int(cols.shape[0]), int(cols.shape[1])
+    kk = min(int(num), pool_n)
+    if n == 0 or kk == 0:
+        return cols[:, :kk], scores[:, :kk], torch.zeros(n, dtype=torch.int32, device=cols.device)
+    if inv is None:
+        inv = _hrec.row_inv_norms(vectors, d)
+    pos, out_len, _ = _hrec.mmr_rerank(cols, scores, vectors, inv, mmr.lambda_, kk, pool_len=lens, d=d)
+    live = pos >= 0
+    at = pos.clamp(min=0).to(torch.int64)
+    out_cols = torch.where(live, torch.gather(cols, 1, at), torch.full_like(at, -1))
+    out_scores = torch.gather(scores, 1, at)
+    return out_cols, torch.where(live, out_scores, torch.full_like(out_scores, float("nan"))), out_len
+
+
+def diversify_finish(id_table, cols, scores, lens, n_cols, columns, with_lens):
+    """What a model's recommend returns for diversify()'s lists: the triple as
+    it is (columns), or (raw ids, scores, lens or None), padded as pad_lists
+    does."""
+    if columns:
+        return cols, scores, lens
+    ids, scores = pad_lists(id_table, cols.clone(), scores, lens, n_cols)
+    return ids, scores, (lens if with_lens else None)
+
+
 # ----------------------------------------------------------- list finishing
 def empty_lists(n, kk, dtype, dev, with_lens):
     """The (ids, scores, lens) of n lists of kk entries when either is 0."""

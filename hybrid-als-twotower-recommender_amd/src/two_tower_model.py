@@ -429,20 +429,28 @@ class TwoTowerModel:
             raise RuntimeError("the two-tower model is not built or loaded")
         return np.unique(_ids(np.asarray(users).reshape(-1), self.model.sizes["user_emb"], "user_in").astype(np.int64))
 
-    def _recommend_device(self, users, cand, num, exclude=None, _columns=False):
+    def _recommend_device(self, users, cand, num, exclude=None, _columns=False, diversify=None):
         """Top-`num` candidates for each of `users` (_query_users' array):
         device (raw itemIds int64 [n, kk], scores f32 [n, kk], lens int32 [n]
         or None when every list is full), kk = min(num, candidates). Past a
         list's length: id 0, score NaN. _columns (internal): return (candidate
-        frame rows int64 [n, kk], lens or None) instead: the lists before the
-        id gather."""
+        frame rows int64 [n, kk], scores, lens or None) instead: the lists
+        before the id gather. diversify (optional): a ranked_lists.MMR; the top
+        max(pool, num) are ranked as above and hrec_mmr_rerank picks num of
+        them (cosines between the candidates' vectors), in selection order."""
         num = ranked_lists.check_num(num, self.RECOMMEND_MAX, "num_items")
         dev = self.model.device
         n, N = int(users.size), int(cand.vectors.shape[0])
         kk = min(num, N)
+        if diversify is not None:
+            mmr = ranked_lists.check_mmr(diversify)
+            pool = self._recommend_device(users, cand, max(num, mmr.pool), exclude, _columns=True)
+            picked = ranked_lists.diversify(*pool, cand.vectors, None, int(cand.vectors.shape[1]) if N else 1, mmr,
+                                            num)
+            return ranked_lists.diversify_finish(cand.ids_dev, *picked, N, _columns, exclude is not None)
         if n == 0 or kk == 0:
             empty = ranked_lists.empty_lists(n, kk, torch.float32, dev, exclude is not None)
-            return empty[::2] if _columns else empty
+            return empty
         excl = self._exclusion(users, cand, exclude) if exclude is not None else None
         U = self.model.user_vectors(torch.as_tensor(users.astype(np.int32), device=dev))
         V = cand.vectors
@@ -461,12 +469,12 @@ class TwoTowerModel:
                                     self.RECOMMEND_FALLBACK_BYTES, idx, val, lens,
                                     None if excl is None else (rows, *excl))
         if _columns:
-            return idx, lens
+            return idx, val, lens
         if lens is None:
             return cand.ids_dev[idx], val, None
         return (*ranked_lists.pad_lists(cand.ids_dev, idx, val, lens, N), lens)
 
-    def recommend_for_users(self, users, item_features, num_items, exclude=None):
+    def recommend_for_users(self, users, item_features, num_items, exclude=None, diversify=None):
         """Top-n lists for many users in one device pass: a DataFrame with
         `userId` (the distinct ids of `users`, ascending; a DataFrame with a
         userId column or an array-like) and `recommendations`: the user's top
@@ -485,18 +493,27 @@ class TwoTowerModel:
         embedding_size 32 / 64 / 128 / 256 takes the fused matrix-core top-k
         (hrec_dot_topk / hrec_dot_topk_excluding); any other width, the
         default 50 included, the materialised hrec_tt_score chain (see the
-        note above)."""
+        note above).
+        diversify (optional; here and in the methods below): a
+        ranked_lists.MMR(lambda_, pool). The model ranks max(pool, num_items)
+        candidates (after exclude) and greedy Maximal Marginal Relevance picks
+        num_items of them, each pick trading its rating (min-max scaled over
+        the pool) against its largest cosine, between the candidates'
+        item-tower vectors, to the picks before. The lists are then in
+        SELECTION order, no longer descending by rating; a tuple keeps the
+        rating bits the plain list has for that item. None: the plain ranking."""
         cand = self.candidates(item_features)
         users = self._query_users(users)
-        ids, val, lens = self._recommend_device(users, cand, num_items, exclude)
+        ids, val, lens = self._recommend_device(users, cand, num_items, exclude, diversify=diversify)
         return ranked_lists.lists_frame("userId", users, ids, val, lens)
 
-    def recommend_for_all_users(self, item_features, num_items, exclude=None):
+    def recommend_for_all_users(self, item_features, num_items, exclude=None, diversify=None):
         """recommend_for_users for users 0 .. num_users - 1."""
         return self.recommend_for_users(np.arange(int(self.num_users), dtype=np.int64), item_features, num_items,
-                                        exclude)
+                                        exclude, diversify)
 
-    def ranking_metrics(self, data, item_features, k=10, label_col=None, min_rating=None, exclude=None):
+    def ranking_metrics(self, data, item_features, k=10, label_col=None, min_rating=None, exclude=None,
+                        diversify=None):
         """Spark's RankingMetrics (binary relevance) of the model's top-k
         lists over `item_features` against `data` (columns userId, itemId):
         ALSModel.RANKING_METRIC_NAMES' five metrics plus "count", with
@@ -508,18 +525,23 @@ class TwoTowerModel:
         the mean over the `count` users (NaN when count is 0). exclude as in
         recommend_for_users; each list is evaluated at its own length. A user
         id outside the table raises IndexError. The lists go from the top-k
-        into hrec_ranking_metrics without leaving the device."""
+        into hrec_ranking_metrics without leaving the device. diversify: the
+        metrics of recommend_for_users' diversified lists, in selection order."""
         cand = self.candidates(item_features)
+        if diversify is not None:
+            ranked_lists.check_mmr(diversify)
         return ranked_lists.ranking_metrics(
             data, k, label_col, min_rating, self.model.device, self.RANKING_HOST_ROWS, self.RANKING_METRIC_NAMES,
-            lambda users, k: self._recommend_device(self._query_users(users), cand, k, exclude)[::2])  # IndexError
+            lambda users, k: self._recommend_device(self._query_users(users), cand, k, exclude,
+                                                    diversify=diversify)[::2])  # IndexError
 
     def evaluate_ranking(self, data, item_features, metric_name="meanAveragePrecision", k=10, label_col=None,
-                         min_rating=None, exclude=None):
+                         min_rating=None, exclude=None, diversify=None):
         """Spark's RankingEvaluator(metricName=metric_name, k=k).evaluate of
         the model's lists for the users of `data` (a float)."""
         ranked_lists.check_metric_name(metric_name, self.RANKING_METRIC_NAMES)
-        return float(self.ranking_metrics(data, item_features, k, label_col, min_rating, exclude)[metric_name])
+        return float(self.ranking_metrics(data, item_features, k, label_col, min_rating, exclude,
+                                          diversify)[metric_name])
 
     # ------------------------------------------------------------ list quality
     # ALSModel.list_quality_metrics / evaluate_list_quality over a candidate
@@ -534,7 +556,7 @@ class TwoTowerModel:
         return (self._exclusion(users, cand, history),
                 ranked_lists.history_tables(*ranked_lists.history_frame(history), cand.item_ids, self.model.device))
 
-    def list_quality_metrics(self, item_features, k=10, users=None, exclude=None, history=None):
+    def list_quality_metrics(self, item_features, k=10, users=None, exclude=None, history=None, diversify=None):
         """ALSModel.list_quality_metrics for the model's top-k lists over the
         candidates of `item_features` (recommend_for_users(users,
         item_features, k, exclude); users None: every user of the table), still
@@ -542,15 +564,18 @@ class TwoTowerModel:
         vectors (TwoTowerCandidates.vectors). history: a DataFrame with userId
         and itemId columns (typically the training frame); its items outside
         the candidate frame enter nothing. The model has no coldStartStrategy:
-        "dropped" is 0 and a user id outside the table raises IndexError."""
+        "dropped" is 0 and a user id outside the table raises IndexError.
+        diversify: the measures of recommend_for_users' diversified lists."""
         cand = self.candidates(item_features)
         k = ranked_lists.check_num(k, self.RECOMMEND_MAX, "k")
+        if diversify is not None:
+            ranked_lists.check_mmr(diversify)
         users = self._query_users(np.arange(int(self.num_users), dtype=np.int64) if users is None else users)
         dev = self.model.device
         hist, tables = self._history(users, cand, history)
 
         def batches():
-            cols, lens = self._recommend_device(users, cand, k, exclude, _columns=True)
+            cols, _, lens = self._recommend_device(users, cand, k, exclude, _columns=True, diversify=diversify)
             rows = torch.arange(int(users.size), dtype=torch.int64, device=dev)  # query q reads history row q
             yield cols, lens, None if hist is None else (rows, *hist)
 
@@ -560,10 +585,10 @@ class TwoTowerModel:
         return res
 
     def evaluate_list_quality(self, item_features, metric_name="catalogCoverage", k=10, users=None, exclude=None,
-                              history=None):
+                              history=None, diversify=None):
         """One of list_quality_metrics' eight measures (a float)."""
         ranked_lists.check_metric_name(metric_name, self.LIST_QUALITY_METRIC_NAMES)
-        return float(self.list_quality_metrics(item_features, k, users, exclude, history)[metric_name])
+        return float(self.list_quality_metrics(item_features, k, users, exclude, history, diversify)[metric_name])
 
     # --------------------------------- positions in the full catalogue
     # ALSModel.rank_of / full_ranking_metrics / evaluate_full_ranking over a

@@ -34,7 +34,9 @@
  *   Beyond-accuracy list measures (coverage, Gini, novelty, diversity,
  *          unexpectedness; no reference line)          -> hrec_row_inv_norms,
  *                                                          hrec_list_quality
- *   Keras  two-tower graph    src/two_tower_model.py:38-89 -> hrec_tt_*
+ *   Greedy MMR re-ranking of a candidate pool
+ *          (no reference line)                        -> hrec_mmr_rerank
+ *   Keras  two-tower graph   src/two_tower_model.py:38-89 -> hrec_tt_*
  *   Keras  Dot + sorted(...)[:k] for many users        -> hrec_dot_topk
  *          the same minus a training frame's pairs
  *          (no reference line)                        -> hrec_dot_topk_excluding
@@ -836,6 +838,52 @@ int hrec_list_quality(const int64_t* lists, int64_t lists_ld, int list_n, const 
                       const int32_t* hist_cols, const double* item_tables, int n_tab,
                       int64_t* exposure, double* per_row, int32_t* row_n, double* sums_out,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* Diversity-aware re-ranking of a candidate pool (additive to ABI 7): greedy
+ * Maximal Marginal Relevance (Carbonell and Goldstein 1998), per list.
+ *
+ * hrec_mmr_rerank: pool [n_rows][pool_ld] int64 holds candidate COLUMNS, best
+ * first (a top-k result before the id gather, as in hrec_list_quality), row
+ * r's pool in its first min(pool_len[r], pool_n) entries (pool_len int32
+ * [n_rows]; NULL: pool_n). scores [n_rows][scores_ld] holds the models'
+ * ratings at the same positions, f32 (scores_f64 == 0) or f64 (1). vectors,
+ * d, ld, inv_norm and n are hrec_list_quality's. 1 <= top_n <= pool_n <= 1024,
+ * pool_ld >= pool_n, scores_ld >= pool_n, 1 <= d <= 256, ld >= d,
+ * 0 <= lambda <= 1, 1 <= n < 2^31.
+ * An entry is valid when its position is below the row's length and its
+ * column is in [0, n); every other entry (-1 included) is never selected and
+ * never used as an index. All arithmetic is f64 and unfused:
+ *   x_p = (double)v_col(p) * inv_norm[col(p)] componentwise (the zero vector
+ *     where inv_norm is 0, whatever the components are);
+ *   lo, hi = the extremes of the finite scores of the row's valid entries;
+ *   rel_p = (s_p - lo) / (hi - lo), 1.0 when hi == lo; a valid entry with a
+ *     non-finite score takes no part in lo / hi and has value -inf at every
+ *     step;
+ *   at step t, with S the positions selected so far,
+ *     value_p = lambda * rel_p - (1 - lambda) * max_{q in S} x_p . x_q
+ *     (no clipping at 0; while S is empty, lambda * rel_p);
+ *   step t selects the unselected valid position with the largest value,
+ *     equal values: the smaller position.
+ * Outputs: out_len[r] = min(top_n, valid entries of row r); out_pos int32
+ * [n_rows][top_n] = the selected POSITIONS in the pool row, in selection
+ * order, -1 past out_len; out_value f64 [n_rows][top_n] (optional) = the
+ * selected entry's value at its step, NaN past out_len. So the first pick is
+ * the best finite-scored valid entry, and lambda == 1 returns the valid
+ * positions in pool order.
+ * One block per list, one thread per pool position (up to four): a cosine is
+ * a private chain of d terms in four partial sums (component c into sum c mod
+ * 4, then (a0 + a1) + (a2 + a3)); rel, the running maximum and the selected
+ * flag stay in registers. The arg-max is a fixed reduction over (value,
+ * position): a wave xor tree, then the waves in order; no floating-point
+ * atomics: equal inputs give equal bits on every call. The pool's rows are
+ * staged in LDS once when pool_n * (d | 1) * 4 bytes fit 56 KiB, and re-read
+ * from global memory at every step otherwise. No workspace.
+ * n_rows == 0 returns HREC_OK and touches nothing. */
+int hrec_mmr_rerank(const int64_t* pool, int64_t pool_ld, int pool_n, const int32_t* pool_len,
+                    const void* scores, int scores_f64, int64_t scores_ld, int64_t n_rows,
+                    int64_t n, const float* vectors, int d, int64_t ld, const double* inv_norm,
+                    double lambda, int top_n, int32_t* out_pos, int32_t* out_len,
+                    double* out_value, void* stream);
 
 /* ------------------------------------------------------ cold-start sim --
  * ALSModel._find_similar_items (src/als_model.py:93-104): out[q*n_items+j] =

@@ -108,7 +108,7 @@ m = min(als.LIST_QUALITY_ROWS, n_users)
 rows = torch.arange(m, dtype=torch.int64, device=dev)
 say(f"{n_users} users x {n_items} candidates, top {TOP}, history {HIST} per user; one sub-batch = {m} users")
 # the lists and the histories: the ALS model's own top 10 and top 500 (unfiltered), as columns
-lists, _ = als.model.recommend("user", rows, TOP, _columns=True)
+lists = als.model.recommend("user", rows, TOP, _columns=True)[0]
 hist_cols = torch.sort(als.model.recommend("user", rows, HIST, _columns=True)[0], dim=1).values
 hist = (rows, torch.arange(0, (m + 1) * HIST, HIST, dtype=torch.int64, device=dev),
         hist_cols.to(torch.int32).reshape(-1).contiguous())
