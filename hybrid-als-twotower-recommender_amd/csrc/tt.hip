@@ -9,47 +9,17 @@
 // last axis, y = xhat*gamma + beta). Loss MSE, optimiser Adam (:84-88) with
 // TF 2.8's dense ResourceApplyAdam and sparse (IndexedSlices) update rules.
 // f32 throughout (the reference's Keras dtype).
-#include "common.h"
+#include "tt_ln.h"  // wave_sum, ln_row, adam_elem (shared with csrc/tt_fold_in.hip)
 
 namespace hrec {
 
 constexpr int kTR = 8;      // rows (samples / candidates) per workgroup: 32 workgroups at a batch of 256
 constexpr int kBlock = 256;
-constexpr float kLnEps = 1e-3f;
 
 struct TTDev {
   int d;
   const float *ue, *ie, *me, *ce, *w1, *b1, *w2, *b2, *gu, *bu, *gi, *bi;
 };
-
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, kWave);
-  return x;
-}
-
-// LayerNorm of one row held in LDS (length d), one wave. Writes y (and the
-// normalised row + 1/std when save != nullptr).
-__device__ __forceinline__ void ln_row(const float* __restrict__ x, int d, const float* __restrict__ gamma,
-                                       const float* __restrict__ beta, float* __restrict__ y,
-                                       float* __restrict__ xhat_out, float* __restrict__ rstd_out, int lane) {
-  float s = 0.f;
-  for (int c = lane; c < d; c += kWave) s += x[c];
-  const float mean = wave_sum(s) / (float)d;
-  float q = 0.f;
-  for (int c = lane; c < d; c += kWave) {
-    const float t = x[c] - mean;
-    q += t * t;
-  }
-  const float var = wave_sum(q) / (float)d;
-  const float rstd = 1.0f / sqrtf(var + kLnEps);
-  for (int c = lane; c < d; c += kWave) {
-    const float xh = (x[c] - mean) * rstd;
-    y[c] = xh * gamma[c] + beta[c];
-    if (xhat_out) xhat_out[c] = xh;
-  }
-  if (rstd_out && lane == 0) *rstd_out = rstd;
-}
 
 // K4: item tower for n rows. Optional saves for the backward pass:
 // z [n, d+32], xhat [n, d], rstd [n].
@@ -651,23 +621,6 @@ __global__ __launch_bounds__(64) void sparse_dedup_group_kernel(const SparseGrou
     if (on) T.gsum[(int64_t)s * dim + c] = acc;
   }
   if (lane == 0) T.mark[key] = s;
-}
-
-// One element of the whole-table Adam step (has_g: the row is in the batch;
-// g its summed gradient). The two fma are spelled out so every kernel that
-// updates a row (the sweep, the touched-rows kernel of the phased form)
-// rounds it identically.
-__device__ __forceinline__ void adam_elem(float& m, float& v, float& x, float g, bool has_g, float lr, float b1,
-                                          float omb1, float b2, float omb2, float eps) {
-  float me = m * b1;
-  float ve = v * b2;
-  if (has_g) {
-    me = __builtin_fmaf(g, omb1, me);
-    ve = __builtin_fmaf(g * g, omb2, ve);
-  }
-  m = me;
-  v = ve;
-  x = x - (lr * me) / (sqrtf(ve) + eps);
 }
 
 // blocks of kBlock threads x 4 elements (every dim % 4 == 0, 16-B aligned).

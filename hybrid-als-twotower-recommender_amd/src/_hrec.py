@@ -140,6 +140,8 @@ _SIGNATURES.update({
     "hrec_tt_pair_metrics_workspace_bytes": (_c_sz, [_c_i64]),
     "hrec_tt_pair_metrics": (_c_i32, [_vp, _c_i64, _vp, _c_i64, _c_i32, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _c_sz,
                                       _vp]),
+    "hrec_tt_fold_in_users": (_c_i32, [_vp, _c_i64, _c_i32, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i32, _vp] +
+                              [ctypes.c_float] * 5 + [_vp, _vp]),
     "hrec_tt_item_inputs_workspace_bytes": (_c_sz, [_c_i64]),
     "hrec_tt_item_inputs": (_c_i32, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _c_sz, _vp]),
@@ -1415,6 +1417,41 @@ def tt_pair_sums(user_vec, user_rows, item_vec, item_rows, labels, pred_out=None
         *args, _dev(labels, torch.float64, "labels"), _dev(pred_out, torch.float32, "pred_out"),
         _dev(sums, torch.float64, "sums"), _dev(ws, torch.uint8, "ws"), need, _stream()))
     return sums
+
+
+def tt_fold_in_users(emb, ln_gamma, ln_beta, item_vec, indptr, item_rows, ratings, step_lr, beta1, omb1, beta2, omb2,
+                     eps, want_loss=True):
+    """hrec_tt_fold_in_users: the first indptr.numel() - 1 rows of emb (f32
+    [>= n_rows, d], updated in place) fitted to their histories - CSR (indptr
+    int64 [n_rows + 1], item_rows int64 rows of item_vec [n_items, d], ratings
+    f32) - for step_lr.numel() steps (step_lr: f32 device, the sparse Adam step
+    size of each step), everything else frozen. Returns the f32 [n_rows, 2]
+    mean squared error of each row before and after (None without want_loss).
+    An item row outside item_vec is skipped; a row without a usable entry
+    keeps its bits and gets NaN losses. 1 <= d <= 256.
+    Precondition (not checked: indptr lives on the device): indptr is
+    non-decreasing from indptr[0] >= 0 to indptr[-1] <= item_rows.numel();
+    anything else makes the kernel read past item_rows and ratings."""
+    n_rows = indptr.numel() - 1
+    d = emb.shape[1]
+    if n_rows < 0 or emb.shape[0] < n_rows or item_vec.shape[1] != d or ln_gamma.numel() != d or ln_beta.numel() != d:
+        raise HrecError("tt_fold_in_users: emb / item_vec / LayerNorm shapes do not match")
+    if item_rows.numel() != ratings.numel():
+        raise HrecError("tt_fold_in_users: item_rows and ratings must have the same length")
+    dev = emb.device
+    loss = torch.empty((n_rows, 2), dtype=torch.float32, device=dev) if want_loss else None
+    if n_rows == 0:
+        return loss
+    if item_rows.numel() == 0:  # an empty tensor has no address; no entry is read
+        item_rows, ratings = item_rows.new_zeros(1), ratings.new_zeros(1)
+    steps = int(step_lr.numel())
+    _check("hrec_tt_fold_in_users", lib().hrec_tt_fold_in_users(
+        _dev(emb, torch.float32, "emb"), n_rows, d, _dev(ln_gamma, torch.float32, "ln_gamma"),
+        _dev(ln_beta, torch.float32, "ln_beta"), _dev(item_vec, torch.float32, "item_vec") if item_vec.shape[0] else None,
+        item_vec.shape[0], _dev(indptr, torch.int64, "indptr"), _dev(item_rows, torch.int64, "item_rows"),
+        _dev(ratings, torch.float32, "ratings"), steps, _dev(step_lr, torch.float32, "step_lr") if steps else None,
+        float(beta1), float(omb1), float(beta2), float(omb2), float(eps), _dev(loss, torch.float32, "loss"), _stream()))
+    return loss
 
 
 TT_INPUTS_IDS, TT_INPUTS_INF, TT_INPUTS_DUP = 1, 2, 4

@@ -94,13 +94,14 @@ class DeviceSession:
 class DeviceALSFactors:
     """The fitted model (Spark's ALSModel): ids + factor matrices on the device."""
 
-    def __init__(self, user_ids, item_ids, U, V, k):
+    def __init__(self, user_ids, item_ids, U, V, k, Vt=None):
+        """Vt (optional): the transpose an earlier model built of the same V (fold_in_users)."""
         self.user_ids = np.asarray(user_ids)   # sorted unique raw ids
         self.item_ids = np.asarray(item_ids)
         self.U = U                               # [n_users, kp] f32 device
         self.V = V                               # [n_items, kp] f32 device
         self.k = int(k)
-        self.Vt = _hrec.transpose(V) if V.shape[0] else V.t().contiguous()
+        self.Vt = Vt if Vt is not None else (_hrec.transpose(V) if V.shape[0] else V.t().contiguous())
         self._ids_dev = {}  # "user" / "item" -> the sorted ids on the device (_ids_device)
         self._rec_ops = {}  # "user" / "item" -> recommend()'s operands (_recommend_operands)
 
@@ -849,6 +850,97 @@ class ALSModel:
         transform(data): one of rmse, mse, mae, r2, var (a float)."""
         ranked_lists.check_metric_name(metric_name, self.METRIC_NAMES)
         return float(self.regression_metrics(data, label_col)[metric_name])
+
+    # ------------------------------------------------------------- fold-in
+    # New users into a fitted model without a refit (DESIGN §29). No
+    # counterpart in the reference or in Spark: failures raise.
+    def _solve_user_rows(self, model, indptr, indices, values):
+        """[n, kp] f32 device: the rows one user half-sweep of `train` gives
+        the CSR (indptr int64 [n + 1], indices int32 item rows of model.V,
+        values f32) against the fixed item factors: DeviceALS.user_half_sweep
+        itself, on one rank, with this instance's reg_param, implicit_prefs /
+        alpha and nonnegative, so the launch and its operands (the f64 source
+        copy, YtY of model.V) are the ones DeviceALS._launcher forms in a fit."""
+        n, n_items = int(indptr.numel()) - 1, int(model.V.shape[0])
+        dev = model.V.device
+        kw = {}
+        if self.implicit_prefs:
+            kw.update(implicit=True, alpha=float(self.alpha))
+        if self.nonnegative:
+            kw["nonnegative"] = True
+        no_ratings = DeviceCSR(torch.zeros(n_items + 1, dtype=torch.int64, device=dev),
+                               torch.empty(0, dtype=torch.int32, device=dev),
+                               torch.empty(0, dtype=torch.float32, device=dev), 0, n_items, n)
+        eng = DeviceALS(n, n_items, model.k, float(self.reg_param), DeviceCSR(indptr, indices, values, 0, n, n_items),
+                        no_ratings, **kw)
+        if eng.V.shape != model.V.shape:
+            raise RuntimeError("fold_in_users: the model's item factors do not have the engine's layout")
+        eng.V = eng.V_local = model.V  # the fit's source buffer, not a copy
+        eng.user_half_sweep()
+        return eng.U[:n]
+
+    def fold_in_users(self, data, replace=False):
+        """Give users the model has not seen a factor row from their ratings,
+        without a refit: each user's normal equations are solved against the
+        fixed item factors - exactly one row of train's user half-sweep, run
+        by the same launch, so a folded row has the bits train would have
+        produced for the same ratings against the same item factors. After the
+        call every method serves and evaluates these users as known users.
+        data: a frame with userId, itemId and average_review_rating, the
+        columns train takes. Rows whose item the model does not know are
+        dropped; within a user the remaining rows keep frame order (the f64
+        Gramian sums depend on it). A user left without a row gets no factor
+        row. replace=False: a user id the model already holds raises
+        ValueError before any device work; replace=True: its row is
+        overwritten by the solution from the given ratings alone. A row that
+        is not finite (singular equations at reg_param = 0) raises ValueError
+        and leaves the model as it was. Item factors, item ids, item_features
+        and global_mean do not change. One GPU; under a torch.distributed
+        world every rank does the same work, without collectives.
+        Returns {"users_added", "users_replaced", "users_skipped",
+        "ratings_used", "ratings_dropped"}."""
+        model = self._trained()
+        users, items = _int_ids(data["userId"], "userId"), _int_ids(data["itemId"], "itemId")
+        ratings = np.ascontiguousarray(np.asarray(data["average_review_rating"], dtype=np.float32))
+        uniq, inv = np.unique(users, return_inverse=True)
+        known = model._lookup(model.user_ids, uniq) >= 0
+        if known.any() and not replace:
+            raise ValueError(f"fold_in_users: {int(known.sum())} user id(s) are already in the model (the first: "
+                             f"{int(uniq[known][0])}); replace=True overwrites their rows")
+        out = {"users_added": 0, "users_replaced": 0, "users_skipped": int(uniq.size), "ratings_used": 0,
+               "ratings_dropped": int(users.size)}
+        if users.size == 0 or len(model.item_ids) == 0:
+            return out
+        dev = model.U.device
+        irow = model._lookup_device(items, "item")
+        keep = irow >= 0
+        inv_k = torch.as_tensor(np.ascontiguousarray(inv.reshape(-1)), device=dev)[keep]
+        counts = torch.bincount(inv_k, minlength=int(uniq.size))
+        has = (counts > 0).cpu().numpy()  # users with a rating on a known item
+        used = int(inv_k.numel())
+        out.update(users_skipped=int((~has).sum()), ratings_used=used, ratings_dropped=int(users.size) - used)
+        if not has.any():
+            return out
+        order = torch.sort(inv_k, stable=True).indices  # grouped by user, frame order inside a user
+        indptr = torch.zeros(int(has.sum()) + 1, dtype=torch.int64, device=dev)
+        indptr[1:] = torch.cumsum(counts[counts > 0], 0)
+        indices = irow[keep][order].to(torch.int32).contiguous()
+        values = torch.as_tensor(ratings, device=dev)[keep][order].contiguous()
+        rows = self._solve_user_rows(model, indptr, indices, values)
+        if not bool(torch.isfinite(rows).all().item()):
+            raise ValueError("fold_in_users: a new row is not finite: its normal equations are singular (reg_param = "
+                             "0 needs at least rank independent ratings per user); the model is unchanged")
+        new_ids = uniq[has]
+        ids = np.union1d(np.asarray(model.user_ids, np.int64), new_ids)
+        U = torch.zeros((ids.size, model.U.shape[1]), dtype=torch.float32, device=dev)
+        U[torch.as_tensor(np.searchsorted(ids, np.asarray(model.user_ids, np.int64)), device=dev)] = model.U
+        U[torch.as_tensor(np.searchsorted(ids, new_ids), device=dev)] = rows  # after the old rows: replace wins
+        # a fresh model over the same item factors: nothing keyed on the user side survives
+        self.model = DeviceALSFactors(ids.astype(np.asarray(model.user_ids).dtype, copy=False), model.item_ids, U,
+                                      model.V, model.k, Vt=model.Vt)
+        replaced = int((known & has).sum())
+        out.update(users_added=int(has.sum()) - replaced, users_replaced=replaced)
+        return out
 
     # ------------------------------------------------ recommendForAll / Subset
     # Spark's ALSModel.recommendForAllUsers / recommendForAllItems /

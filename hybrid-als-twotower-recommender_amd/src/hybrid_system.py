@@ -554,6 +554,25 @@ class HybridRecommendationSystem:
         return self.recommend_for_users(np.arange(int(self.twotower_model.num_users), dtype=np.int64), item_features,
                                         num_items, exclude, actual, f1_k, diversify, similarity)
 
+    def fold_in_users(self, data, item_features, replace=False, **two_tower_kwargs):
+        """Fold the users of `data` (userId, itemId, average_review_rating)
+        into both models without a refit: ALSModel.fold_in_users(data,
+        replace) solves their factor rows against the fixed item factors,
+        TwoTowerModel.fold_in_users(data, item_features, **two_tower_kwargs)
+        (steps=, learning_rate=) fits their embedding rows with everything
+        else frozen. Returns {"als": the ALS call's dict, "twotower": the
+        two-tower call's frame}. A folded user has a finite ALS row, so the
+        cold-start substitution no longer applies to it and every list and
+        metric call personalises both halves. No counterpart in the
+        reference: failures raise. The candidates are built (or their stamp
+        checked) and the user id range is checked before the ALS call, and a
+        ValueError of the ALS call leaves both models as they were."""
+        self._require_models()
+        item_features = self.twotower_model.candidates(item_features)
+        self.twotower_model._fold_in_user_ids(data)
+        return {"als": self.als_model.fold_in_users(data, replace=replace),
+                "twotower": self.twotower_model.fold_in_users(data, item_features, **two_tower_kwargs)}
+
     # What the fused lists look like as a whole: ALSModel.list_quality_metrics
     # / evaluate_list_quality for recommend_for_users' lists. No counterpart
     # in the reference: failures raise.

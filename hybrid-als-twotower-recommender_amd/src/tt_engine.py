@@ -89,6 +89,7 @@ class DeviceTwoTower:
         _hrec.require_device()
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.d = int(d)
+        self.seed = int(seed)
         self.sizes = {"user_emb": int(num_users), "item_emb": int(num_items), "man_emb": int(num_man),
                       "cat_emb": int(num_cat)}
         self.layout, self.n_dense = dense_layout(self.d)
@@ -208,6 +209,50 @@ class DeviceTwoTower:
             _hrec.adam_sparse_tables(tabs, *adam)
         self.iterations += 1
         return gd[self.n_dense:]
+
+    # ---------------------------------------------------------- fold-in
+    def grow_users(self, num_users):
+        """Extend the user table to num_users rows (no-op when it has them).
+        The new rows are Keras-init rows (uniform +-0.05) drawn from (seed, old
+        row count), so the same call on the same model gives the same rows;
+        their Adam slots are zero and their mark is -1. Existing rows keep
+        their bits; the parameter block is rebuilt over the new table."""
+        old, new = self.sizes["user_emb"], int(num_users)
+        if new <= old:
+            return
+        dev = self.device
+        rows = np.random.default_rng([int(self.seed), old]).uniform(-0.05, 0.05, size=(new - old, self.d))
+        self.tensors["user_emb"] = torch.cat([self.tensors["user_emb"],
+                                              torch.as_tensor(rows.astype(np.float32), device=dev)]).contiguous()
+        for slots in (self.m_tab, self.v_tab):
+            slots["user_emb"] = torch.cat([slots["user_emb"], torch.zeros((new - old, self.d), dtype=torch.float32,
+                                                                          device=dev)]).contiguous()
+        self.mark["user_emb"] = torch.cat([self.mark["user_emb"],
+                                           torch.full((new - old,), -1, dtype=torch.int32, device=dev)])
+        self.sizes["user_emb"] = new
+        self._refresh_params()
+
+    def fold_in_step_sizes(self, steps, learning_rate=None):
+        """f32 device [steps]: the sparse Adam step size of steps 1 .. steps
+        of a fresh optimiser, computed on the host as train_step computes its."""
+        opt = self.opt if learning_rate is None else AdamConfig(learning_rate, self.opt.b1, self.opt.b2, self.opt.eps)
+        lr = np.array([opt.coefficients(t)["sparse_lr"] for t in range(int(steps))], dtype=np.float32)
+        return torch.as_tensor(lr, device=self.device)
+
+    def fold_in_users(self, users, indptr, item_rows, ratings, item_vectors, steps, learning_rate=None):
+        """Fit the user_emb rows of `users` (int64 device, distinct, inside
+        the table) to their histories - CSR row q: users[q]'s (item_rows into
+        item_vectors, ratings) - with every other variable frozen
+        (hrec_tt_fold_in_users). Only those rows of user_emb change; the
+        table's Adam slots and `iterations` are not touched. Returns the f32
+        device [n, 2] loss before / after."""
+        emb = self.tensors["user_emb"].index_select(0, users).contiguous()
+        c = self.opt.coefficients(0)
+        loss = _hrec.tt_fold_in_users(emb, self.tensors["ln_user_gamma"], self.tensors["ln_user_beta"], item_vectors,
+                                      indptr, item_rows, ratings, self.fold_in_step_sizes(steps, learning_rate),
+                                      self.opt.b1, c["omb1"], self.opt.b2, c["omb2"], self.opt.eps)
+        self.tensors["user_emb"].index_copy_(0, users, emb)
+        return loss
 
     # ------------------------------------------------------------ state
     def state_dict(self):

@@ -723,6 +723,74 @@ class TwoTowerModel:
         ranked_lists.check_metric_name(metric_name, self.METRIC_NAMES)
         return float(self.regression_metrics(data, label_col, candidates)[metric_name])
 
+    # ------------------------------------------------------------- fold-in
+    # New users into a trained model without a refit. No
+    # counterpart in the reference: failures raise.
+    FOLD_IN_MAX_USER_ID = 1 << 24  # ids go through float32 (Keras Input(shape=(1,))): exact below this
+
+    @classmethod
+    def _fold_in_user_ids(cls, data):
+        """data's userId column through _ids' float32 round trip (int64); IndexError outside [0, 2^24)."""
+        users = np.asarray(data["userId"]).astype(np.float32).astype(np.int64)
+        if users.size and (users.min() < 0 or users.max() >= cls.FOLD_IN_MAX_USER_ID):
+            raise IndexError(f"user_in: id out of range [0, {cls.FOLD_IN_MAX_USER_ID})")
+        return users
+
+    def fold_in_users(self, data, item_features, steps=100, learning_rate=None):
+        """Fit the user-embedding row of every user of `data` to that user's
+        ratings with everything else frozen: `steps` Adam steps (a fresh
+        optimiser per row, learning_rate or the model's) on the row alone, the
+        user's whole history as one batch per step - what model.fit would do
+        to that row - in one hrec_tt_fold_in_users launch for all users.
+        data: userId, itemId, average_review_rating. item_features: a
+        candidate frame or candidates()'s object; each itemId is looked up in
+        it on the device and rows whose item it does not hold are dropped
+        (their number: the returned frame's attrs["ratings_dropped"]). User
+        ids take _ids' float32 round trip and must lie in [0, 2^24); an id
+        beyond the user table grows it (DeviceTwoTower.grow_users: seeded
+        Keras-init rows) and num_users with it. A row starts from what the
+        table holds for that user. Only those users' rows of user_emb change:
+        every other tensor, the Adam slots and `iterations` keep their bits, so
+        a candidates() object built before the call stays valid. A user
+        without a usable rating keeps its row and gets NaN losses.
+        Returns a frame of userId (ascending), n_ratings, loss_before and
+        loss_after (the mean squared error over the user's usable ratings)."""
+        if self.model is None:
+            raise RuntimeError("the two-tower model is not built or loaded")
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError(f"steps must be >= 0 (got {steps})")
+        cand = self.candidates(item_features)
+        users = self._fold_in_user_ids(data)
+        items = _int_ids(data["itemId"], "itemId")
+        ratings = np.ascontiguousarray(np.asarray(data["average_review_rating"], dtype=np.float32))
+        uniq, inv = np.unique(users, return_inverse=True)
+        eng, dev = self.model, self.model.device
+        if uniq.size == 0:
+            out = pd.DataFrame({"userId": uniq, "n_ratings": np.zeros(0, np.int64),
+                                "loss_before": np.zeros(0, np.float32), "loss_after": np.zeros(0, np.float32)})
+            out.attrs["ratings_dropped"] = 0
+            return out
+        if int(uniq[-1]) + 1 > eng.sizes["user_emb"]:
+            eng.grow_users(int(uniq[-1]) + 1)
+            self.num_users = eng.sizes["user_emb"]
+        # the history CSR: grouped by user, frame order inside a user; an item
+        # outside the candidate frame keeps its slot as row -1, which the kernel skips
+        inv_t = torch.as_tensor(np.ascontiguousarray(inv.reshape(-1)), device=dev)
+        order = torch.sort(inv_t, stable=True).indices
+        rows = cand.rows_of(torch.as_tensor(items, device=dev))
+        indptr = torch.zeros(uniq.size + 1, dtype=torch.int64, device=dev)
+        indptr[1:] = torch.cumsum(torch.bincount(inv_t, minlength=int(uniq.size)), 0)
+        n_ok = torch.bincount(inv_t[rows >= 0], minlength=int(uniq.size))
+        loss = eng.fold_in_users(torch.as_tensor(uniq, device=dev), indptr, rows[order].contiguous(),
+                                 torch.as_tensor(ratings, device=dev)[order].contiguous(), cand.vectors, steps,
+                                 learning_rate)
+        loss = loss.cpu().numpy()
+        n_ok = n_ok.cpu().numpy()
+        out = pd.DataFrame({"userId": uniq, "n_ratings": n_ok, "loss_before": loss[:, 0], "loss_after": loss[:, 1]})
+        out.attrs["ratings_dropped"] = int(users.size - n_ok.sum())
+        return out
+
     # --------------------------------------------------------- persistence
     def save_model(self, model_path="models/twotower.keras"):
         os.makedirs(os.path.dirname(model_path) or ".", exist_ok=True)
@@ -731,7 +799,9 @@ class TwoTowerModel:
         meta = np.array([self.num_users, self.num_items, self.num_manufacturers, self.num_categories,
                          self.embedding_size], dtype=np.int64)
         with open(model_path, "wb") as f:
-            np.savez(f, __meta__=meta, __lr__=np.float64(self.learning_rate), **state)
+            # __seed__: grow_users draws new user rows from (the engine's seed, the old row count)
+            np.savez(f, __meta__=meta, __lr__=np.float64(self.learning_rate), __seed__=np.int64(self.model.seed),
+                     **state)
         with open(f"{model_path}_scaler.pkl", "wb") as f:
             pickle.dump(self.scaler, f)
 
@@ -742,7 +812,8 @@ class TwoTowerModel:
         with open(f"{model_path}_scaler.pkl", "rb") as f:
             scaler = pickle.load(f)  # written by save_model above (own file)
         nu, ni, nm, nc, d = (int(x) for x in state["__meta__"])
-        loaded_model = cls(nu, ni, nm, nc, d, float(state["__lr__"]))
+        # a file written before the seed was saved: seed 0, the constructor's default
+        loaded_model = cls(nu, ni, nm, nc, d, float(state["__lr__"]), seed=int(state.get("__seed__", 0)))
         loaded_model.build_model(init={k: v for k, v in state.items() if not k.startswith("__")})
         loaded_model.model.iterations = int(state["__iterations__"])
         loaded_model.model.load_optimizer_state(state)

@@ -37,6 +37,8 @@
  *   Greedy MMR re-ranking of a candidate pool
  *          (no reference line)                        -> hrec_mmr_rerank
  *   Keras  two-tower graph   src/two_tower_model.py:38-89 -> hrec_tt_*
+ *   Keras  fit of one user-embedding row, everything else
+ *          frozen, for new users (no reference line)  -> hrec_tt_fold_in_users
  *   Keras  Dot + sorted(...)[:k] for many users        -> hrec_dot_topk
  *          the same minus a training frame's pairs
  *          (no reference line)                        -> hrec_dot_topk_excluding
@@ -1007,6 +1009,41 @@ int hrec_tt_pair_metrics(const float* user_vec, int64_t n_user_rows,
                          const int64_t* user_rows, const int64_t* item_rows, int64_t n,
                          const double* labels, float* pred_out, double* sums_out,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* Fold users into the two-tower model (csrc/tt_fold_in.hip): row u of emb
+ * [n_rows, d] (f32, row stride d; in: the start rows, out: the fitted rows) is
+ * fitted to its own history - the entries indptr[u] .. indptr[u + 1] of
+ * (item_rows, ratings), int64 indptr [n_rows + 1] - with every other variable
+ * frozen: what model.fit does to that user-embedding row when the user's whole
+ * history is one batch per step. ln_gamma / ln_beta [d]: the user tower's
+ * LayerNormalization; item_vec [n_items, d]: hrec_tt_item_forward's output.
+ * The usable history is the entries with 0 <= item_rows[j] < n_items (n of
+ * them; duplicates stay separate terms); the others are skipped and never
+ * turned into an address. For t = 1 .. steps, all in f32:
+ *   xh = (e - mean(e)) rsqrt(var(e) + 1e-3) (biased variance), u = xh gamma + beta
+ *   err_j = <u, item_vec[item_rows[j]]> - ratings[j], usable entries in CSR order
+ *   du = (2 / n) sum_j err_j item_vec[item_rows[j]],  dxh = du gamma
+ *   g = rstd (dxh - mean(dxh) - xh mean(dxh xh))
+ *   m = m beta1 + g one_minus_beta1;  v = v beta2 + g^2 one_minus_beta2
+ *   e -= step_lr[t - 1] m / (sqrt(v) + epsilon)            (m = v = 0 before t = 1)
+ * i.e. Keras' sparse Adam for a row touched at every step; step_lr (device f32
+ * [steps]) holds lr sqrt(1 - beta2^t) / (1 - beta1^t) per step.
+ * out_loss (optional, [n_rows][2]): mean_j err_j^2 at the start row and after
+ * the last step. n == 0 leaves the row as it was and writes NaN, NaN; steps ==
+ * 0 leaves every row as it was and writes the same loss twice. 1 <= d <= 256;
+ * emb and item_vec aligned as hrec_tt_predict_pairs asks for d. One wave per
+ * row, no atomics, every sum in a fixed order: equal inputs give equal bits.
+ * Rows of emb beyond n_rows are not touched; n_rows == 0 is a no-op. The
+ * caller guarantees a well-formed CSR: indptr non-decreasing, 0 <= indptr[0],
+ * indptr[n_rows] <= the length of item_rows and ratings (device data, not
+ * checked here). */
+int hrec_tt_fold_in_users(float* emb, int64_t n_rows, int d,
+                          const float* ln_gamma, const float* ln_beta,
+                          const float* item_vec, int64_t n_items,
+                          const int64_t* indptr, const int64_t* item_rows, const float* ratings,
+                          int steps, const float* step_lr,
+                          float beta1, float one_minus_beta1, float beta2, float one_minus_beta2,
+                          float epsilon, float* out_loss, void* stream);
 
 /* One minibatch of model.fit (src/two_tower_model.py:111): forward, MSE
  * loss, backward. grad_dense receives hrec_tt_grad_len(d) floats:
