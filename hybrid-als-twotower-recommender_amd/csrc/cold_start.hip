@@ -11,10 +11,11 @@
 // one cosine row per NaN item per call (every test user of the
 // reference's protocol is cold, so every candidate takes the fallback).
 //
-//   1. cold_norm_kernel: x_j = f_j / |f_j| (a zero norm -> 1), the
-//      arithmetic of cosine_kernel (below; both take the norm from
-//      cos_row_norm) and of sklearn's normalize: the same bits for every
-//      similarity;
+//   1. cold_norm_kernel: x_j = f_j / |f_j| (a norm below 10 * eps -> 1: such
+//      a row is left as it is, not scaled up to a unit vector), the arithmetic
+//      of cosine_kernel (below; both take the norm from cos_row_norm) and of
+//      sklearn's normalize (its _handle_zeros_in_scale): the same bits for
+//      every similarity;
 //   2. cold_pairs_kernel: a thread per query item q, a block per (256
 //      queries, item slice); the slice's rows staged in LDS (every thread reads
 //      the same row: a broadcast), sim(q, j) = sum_c x_qc x_jc as the
@@ -28,6 +29,8 @@
 //      / count, in rank order.
 // Work: n^2 (2 dim + 1) f64 operations, no HBM traffic beyond the n x dim
 // features per slice (L2-resident): VALU-bound (0.1 s at 10^6 items).
+#include <float.h>
+
 #include "common.h"
 
 namespace hrec {
@@ -38,19 +41,21 @@ constexpr int kColdMaxDim = 16;
 constexpr int kColdK = 3;       // _find_similar_items' k
 
 // |f| of a feature row as sklearn's normalize takes it (sequential non-FMA
-// f64 chain; callers keep contraction off), a zero norm replaced by 1.
+// f64 chain; callers keep contraction off): a norm below 10 * eps (2.2e-15,
+// an exact zero included) is replaced by 1, as _handle_zeros_in_scale does —
+// the rule of mm_range (hybrid_common.h) for the fusion's ranges.
 __device__ __forceinline__ double cos_row_norm(const double* __restrict__ f, int dim) {
 #pragma clang fp contract(off)
   double nr = 0.0;
   for (int c = 0; c < dim; ++c) nr = nr + f[c] * f[c];
   nr = sqrt(nr);
-  if (nr == 0.0) nr = 1.0;
+  if (nr < 10.0 * DBL_EPSILON) nr = 1.0;
   return nr;
 }
 
 // ALSModel._find_similar_items (src/als_model.py:93-104): sklearn
-// cosine_similarity([target], [other]) = dot(a/|a|, b/|b|) with a zero norm
-// replaced by 1. One thread per (query, item); the query's own row -> -inf so
+// cosine_similarity([target], [other]) = dot(a/|a|, b/|b|) with a norm below
+// 10 * eps replaced by 1. One thread per (query, item); the query's own row -> -inf so
 // it never ranks (the reference skips it).
 __global__ __launch_bounds__(256) void cosine_kernel(const double* __restrict__ feats, int64_t n_items, int dim,
                                                      const int64_t* __restrict__ qrows, double* __restrict__ out) {

@@ -847,7 +847,8 @@ def fuse_topk(als, tt, als_wins, top_k, want_fused=True, minmax=None):
 
 # ------------------------------------------------------------ cold start
 def cosine_sim(feats, query_rows):
-    """[n_query, n_items] f64 cosine similarities (self = -inf)."""
+    """[n_query, n_items] f64 cosine similarities (self = -inf), sklearn's
+    normalise-then-dot: a row norm below 10 * eps counts as 1."""
     n_items, dim = feats.shape
     out = torch.empty((query_rows.numel(), n_items), dtype=torch.float64, device=feats.device)
     _check("hrec_cosine_sim", lib().hrec_cosine_sim(
@@ -863,8 +864,9 @@ def cold_fallback(feats, ratings, want_idx=False):
     """The cold-start fallback of every item at once (hrec_cold_fallback,
     src/als_model.py:78-86,93-104): feats [n, dim] f64 (dim <= 16), ratings
     [n] f64 (the items' 'rating'), both device. Returns (mean f64 [n]: the
-    mean rating of the <= 3 most similar other items with cosine > 0.5, 0
-    where there is none; count int32 [n]; idx int32 [n, 3] of those items'
+    mean rating of the <= 3 most similar other items with cosine > 0.5
+    (cosine_sim's values: a row norm below 10 * eps counts as 1), 0 where
+    there is none; count int32 [n]; idx int32 [n, 3] of those items'
     rows, -1 padded, when want_idx)."""
     n, dim = feats.shape
     dev = feats.device

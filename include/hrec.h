@@ -890,7 +890,8 @@ int hrec_mmr_rerank(const int64_t* pool, int64_t pool_ld, int pool_n, const int3
 /* ------------------------------------------------------ cold-start sim --
  * ALSModel._find_similar_items (src/als_model.py:93-104): out[q*n_items+j] =
  * cosine(feats[query_rows[q]], feats[j]) with sklearn's normalise-then-dot
- * (zero norm -> 1); the query's own entry is -inf (the reference skips it).
+ * (a norm below 10 * DBL_EPSILON, zero included, -> 1: such a row is not
+ * scaled up); the query's own entry is -inf (the reference skips it).
  * feats: [n_items, dim] f64 row-major in item_features dict order. */
 int hrec_cosine_sim(const double* feats, int64_t n_items, int dim,
                     const int64_t* query_rows, int64_t n_query, double* out,

@@ -76,13 +76,16 @@ def compute_f1_score(actual, pred, k=10):
 
 
 def cosine(a, b):
-    """sklearn cosine_similarity([a], [b])[0][0]: normalise rows, then dot."""
+    """sklearn cosine_similarity([a], [b])[0][0]: normalise rows, then dot. A
+    norm below 10 * eps counts as 1 (normalize -> _handle_zeros_in_scale): a
+    row that small is not scaled up to a unit vector."""
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)
     na = np.sqrt(np.dot(a, a))
     nb = np.sqrt(np.dot(b, b))
-    na = 1.0 if na == 0 else na
-    nb = 1.0 if nb == 0 else nb
+    small = 10 * np.finfo(np.float64).eps
+    na = 1.0 if na < small else na
+    nb = 1.0 if nb < small else nb
     return float(np.dot(a / na, b / nb))
 
 

@@ -188,3 +188,118 @@ def test_hybrid_cold_user_array_path_matches_list_path(device, monkeypatch):
                 for attr in ("data_min_", "data_max_", "scale_", "min_"):
                     assert np.array_equal(getattr(x, attr), getattr(y, attr)), attr
     assert calls["fast"] >= 4  # the cold users stayed on the array path
+
+
+# ------------------------------------------------------------------------
+# Against an independent oracle (tests/cold_start_oracle.py: sklearn's own
+# cosine_similarity on the f64 rows, the reference's sort / filter / np.mean),
+# not against the library's other kernel: the tests above compare
+# hrec_cold_fallback with hrec_cosine_sim, which share their row norm. The
+# seeded cases — widths on each side of cold_pairs_kernel's <4> | <8> | <16>
+# switches, n one past the 256 tile, several slices, and rows with norms
+# around sklearn's 10 * eps threshold — are decided for every query
+# (tests/test_cold_start_oracle.py), so lists are compared exactly.
+import cold_start_oracle as co  # noqa: E402
+
+
+@pytest.mark.parametrize("case", co.CASES, ids=co.case_id)
+def test_cosine_sim_matches_sklearn(device, case):
+    """hrec_cosine_sim of every row against every row: within 2 tol(dim)
+    absolute of sklearn's matrix off the diagonal (tol(dim) = (dim + 4) 2^-52
+    a side: dim roundings of terms bounded by 1, two divisions, a square
+    root), exactly -inf on it."""
+    from src import _hrec
+
+    X, _ = co.case_inputs(case)
+    want = co.case_oracle(case).sim
+    mat = torch.as_tensor(X.copy(), device=device)  # the shared inputs are read-only
+    got = _hrec.cosine_sim(mat, torch.arange(case.n, dtype=torch.int64, device=device)).cpu().numpy()
+    assert got.shape == (case.n, case.n)
+    diag = np.eye(case.n, dtype=bool)
+    assert np.isneginf(got[diag]).all()
+    err = np.abs(np.where(diag, want, got) - want)
+    q, j = np.unravel_index(np.argmax(err), err.shape)
+    print(co.case_id(case), "max |got - sklearn|", err[q, j], "at", (int(q), int(j)), "got", got[q, j], "want",
+          want[q, j], "2 tol", 2 * co.tol(case.dim))
+    assert err.max() <= 2 * co.tol(case.dim)
+
+
+@pytest.mark.parametrize("case", co.CASES, ids=co.case_id)
+def test_cold_fallback_matches_oracle(device, case):
+    """hrec_cold_fallback: the kept rows of every query equal the oracle's list
+    (every query is decided: none is skipped), count is its length, mean is
+    np.mean of the list's ratings in order bit for bit, 0.0 for an empty list."""
+    from src import _hrec
+
+    X, ratings = co.case_inputs(case)
+    res = co.case_oracle(case)
+    mean, cnt, idx = _hrec.cold_fallback(torch.as_tensor(X.copy(), device=device),
+                                         torch.as_tensor(ratings.copy(), device=device), want_idx=True)
+    mean, cnt, idx = mean.cpu().numpy(), cnt.cpu().numpy(), idx.cpu().numpy()
+    got = [[int(j) for j in row if j >= 0] for row in idx]
+    wrong = [q for q in range(case.n) if got[q] != res.lists[q]]
+    print(co.case_id(case), "queries with a wrong list:", len(wrong), wrong[:20])
+    for q in wrong[:5]:
+        print("  query", q, "got", got[q], "want", res.lists[q])
+    assert not wrong
+    assert all(row[len(lst):].tolist() == [-1] * (3 - len(lst)) for row, lst in zip(idx, got))  # -1 pads the end only
+    assert cnt.tolist() == [len(x) for x in res.lists]
+    want_mean = np.array([0.0 if m is None else m for m in res.means], np.float64)
+    assert mean.dtype == np.float64 and np.array_equal(mean.view(np.int64), want_mean.view(np.int64))
+
+
+def test_predict_for_user_edge_rows_match_oracle(device, monkeypatch):
+    """API level, the edge case at dim 3 as ALSModel.item_features (dict order
+    != id order): predict_for_user for a cold user (every row NaN) and for a
+    known user over items the model does not know returns the oracle's values
+    and types — np.float64 means, the global_mean object where the list is
+    empty, as for the rows below sklearn's norm threshold — through the
+    fallback vector and through the per-item search (_fallback -> None)."""
+    from src.als_model import ALSModel, DeviceALSFactors
+
+    case = co.Case(513, 3, True)
+    assert case in co.EDGE_CASES
+    X, ratings = co.case_inputs(case)
+    res = co.case_oracle(case)
+    n = case.n
+    rng = np.random.default_rng(7)
+    ids = [int(i) for i in rng.permutation(10 * n)[:n]]
+    feats = {i: {"features": X[p].copy(), "rating": float(ratings[p])} for p, i in enumerate(ids)}
+    assert list(feats) != sorted(feats)
+    m = _model(feats, gm=np.float64(7.125))
+    edge = co.edge_rows(case)
+    # the model knows every second item, none of the designed rows
+    known = np.array(sorted(ids[p] for p in range(0, n, 2) if p not in edge.values()), np.int64)
+    V = torch.zeros((len(known), 16), dtype=torch.float32, device=device)
+    V[:, :8] = torch.as_tensor(rng.normal(size=(len(known), 8)).astype(np.float32))
+    U = torch.zeros((1, 16), dtype=torch.float32, device=device)
+    U[0, :8] = torch.as_tensor(rng.normal(size=8).astype(np.float32))
+    m.model = DeviceALSFactors(np.array([7]), known, U, V, 8)
+    row = {i: p for p, i in enumerate(ids)}
+    no_features = [10 ** 7, 10 ** 7 + 1]
+    query = [ids[p] for p in rng.permutation(n)] + no_features
+    known_set = set(known.tolist())
+
+    def check(out, uid):
+        assert [i for i, _ in out] == query
+        n_fallback = 0
+        for item, val in out:
+            if uid == 7 and item in known_set:
+                assert type(val) is float and np.isfinite(val)
+                continue
+            n_fallback += 1
+            want = res.means[row[item]] if item in row else None
+            if want is None:
+                assert val is m.global_mean, (uid, item, val)
+            else:
+                assert type(val) is np.float64 and val == want, (uid, item, val, want)
+        return n_fallback
+
+    for uid, n_want in ((10 ** 6, n + 2), (7, n - len(known) + 2)):
+        assert check(m.predict_for_user(uid, query), uid) == n_want
+        with monkeypatch.context() as mp:
+            mp.setattr(ALSModel, "_fallback", lambda self: None)
+            assert check(m.predict_for_user(uid, query), uid) == n_want
+    # the rows below the norm threshold come back with the global mean (the cold user asks for every one)
+    out = dict(m.predict_for_user(10 ** 6, [ids[edge[name]] for name in co.TINY]))
+    assert len(out) == len(co.TINY) and all(v is m.global_mean for v in out.values())

@@ -440,7 +440,9 @@ def test_als_score_topk_overflow_flag(device):
     (50_000, 100, 128, 12, 100, "normal"), (40_000, 200, 256, 8, 8, "scaled"), (3000, 64, 64, 5, 5, "normal"),
     (60_000, 64, 64, 10, 5, "unknown"), (60_000, 64, 64, 10, 5, "nan_item"), (60_000, 64, 64, 10, 5, "const"),
     (3000, 16, 16, 4, 1, "round_up"), (40_000, 16, 16, 4, 1, "round_up"), (40_000, 64, 64, 6, 3, "round_up"),
-    (60_000, 64, 64, 10, 8, "const"), (60_000, 64, 64, 10, 3, "nan_item")])
+    (60_000, 64, 64, 10, 8, "const"), (60_000, 64, 64, 10, 3, "nan_item"),
+    (40_000, 64, 64, 6, 3, "round_up_one_tile"), (40_000, 100, 128, 6, 3, "round_up_one_tile"),
+    (40_000, 200, 256, 4, 3, "round_up_one_tile"), (40_000, 64, 64, 6, 1, "round_up_one_tile")])
 def test_als_score_topk_pruned_matches_fused(device, n_items, k, kp, B, top_k, case):
     """hrec_als_score_topk_pruned (bf16 matrix-core bound, exact chain only
     for the pairs it keeps) returns the fused path's (ids, scores) bit for
@@ -450,7 +452,12 @@ def test_als_score_topk_pruned_matches_fused(device, n_items, k, kp, B, top_k, c
     (the fused path's empty candidate list), a NaN item (no finite bound:
     overflow -> the exact fallback), constant items (list overflow) and
     components whose bf16 roundings all go the same way (the bound's worst
-    case: 2^-8 relative per operand)."""
+    case: 2^-8 relative per operand) — with the tied best items in distinct
+    sample tiles ("round_up": no overflow on either path) and with three of
+    them inside the first 16 items, one wave tile at every operand width
+    (dk 64 / 128 / 256), where a bound taken from tile maxima under-counts
+    them ("round_up_one_tile": either flag may come out, the lists may not
+    differ from the exact stable top-k)."""
     h = _hrec()
     rng = np.random.default_rng(n_items + k)
     U = np.zeros((B, kp), np.float32)
@@ -466,14 +473,16 @@ def test_als_score_topk_pruned_matches_fused(device, n_items, k, kp, B, top_k, c
         V[777, 3] = np.nan
     if case == "const":
         V[:, :k] = 0.25
-    if case == "round_up":  # every bf16 rounding error aligned: 1 + 2^-8 + 2^-20 -> 1 + 2^-7,
+    if case in ("round_up", "round_up_one_tile"):
+        # every bf16 rounding error aligned: 1 + 2^-8 + 2^-20 -> 1 + 2^-7,
         # so s~ of the best items overshoots their chain by ~2^-7 ||u|| ||v|| (the sample bound then sits
         # right at the kk-th chain); four tied best items in distinct sample tiles (the last past the
-        # 32768-item sample), the rest far below
+        # 32768-item sample), the rest far below; "round_up_one_tile": three of the four inside one wave tile
         x = np.float32(1 + 2.0 ** -8 + 2.0 ** -20)
         U[:, :k] = x
         V[:, :k] = 0.5
-        V[[0, 100, 200, min(33_000, n_items - 1)], :k] = x
+        tied = [0, 100, 200] if case == "round_up" else [0, 5, 7]
+        V[tied + [min(33_000, n_items - 1)], :k] = x
     dU = torch.as_tensor(U, device=device)
     dV = torch.as_tensor(V, device=device)
     Vt = h.transpose(dV)
@@ -493,6 +502,16 @@ def test_als_score_topk_pruned_matches_fused(device, n_items, k, kp, B, top_k, c
     exp_i = _np_stable_topk(full, min(top_k, n_items))
     if case in ("nan_item", "const"):
         assert fp == 1
+    elif case == "round_up_one_tile":  # which flag comes out is not pinned; what the call returns is (below)
+        print("round_up_one_tile", (n_items, k, kp, B, top_k), "(fp, ff) =", (fp, ff))
+        assert top_k <= 8 and fp in (0, 1) and ff in (0, 1), (fp, ff)
+        if fp == 0 and ff == 0:
+            np.testing.assert_array_equal(pi.cpu().numpy(), fi.cpu().numpy())
+            np.testing.assert_array_equal(pv.cpu().numpy().view(np.int32), fv.cpu().numpy().view(np.int32))
+        # the fused call's unresolved answer is held to the exact top-k as well (the pruned one: below)
+        np.testing.assert_array_equal(fi.cpu().numpy()[known], exp_i)
+        np.testing.assert_array_equal(fv.cpu().numpy()[known].view(np.int32),
+                                      np.take_along_axis(full, exp_i, 1).view(np.int32))
     else:
         assert fp == ff == 0, (fp, ff)
         np.testing.assert_array_equal(pi.cpu().numpy(), fi.cpu().numpy())
@@ -508,6 +527,11 @@ def test_als_score_topk_pruned_matches_fused(device, n_items, k, kp, B, top_k, c
     got_i, got_v = pi.cpu().numpy()[known], pv.cpu().numpy()[known]
     np.testing.assert_array_equal(got_i, exp_i)
     np.testing.assert_array_equal(got_v.view(np.int32), np.take_along_axis(full, exp_i, 1).view(np.int32))
+    if case == "round_up_one_tile":
+        fi, fv = h.als_score_topk(dU, users, Vt, n_items, k, top_k)
+        np.testing.assert_array_equal(fi.cpu().numpy()[known], exp_i)
+        np.testing.assert_array_equal(fv.cpu().numpy()[known].view(np.int32),
+                                      np.take_along_axis(full, exp_i, 1).view(np.int32))
 
 
 _BF16_PATTERNS = np.array([
