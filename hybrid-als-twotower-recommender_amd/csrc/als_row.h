@@ -50,6 +50,20 @@
 #define HREC_ALS_POOL_ROT1DPP64 1  // as HREC_ALS_ROT1DPP64; 0 keeps 16 more VGPRs of rotated loads in flight and spills in the step loop
 #endif
 
+// The step's ds_bpermute addresses (same bits either way):
+#ifndef HREC_ALS_BPERM_IMM
+#define HREC_ALS_BPERM_IMM 3  // f32 sources: N opaque per-window copies of the lane's base + immediate offsets (0: the 16 sums hoisted into registers)
+#endif
+#ifndef HREC_ALS_BPERM_IMM64
+#define HREC_ALS_BPERM_IMM64 0  // as HREC_ALS_BPERM_IMM, f64 sources (1 and 2 spill inside the pooled kernel's step loop)
+#endif
+#ifndef HREC_ALS_RATING_CVT
+#define HREC_ALS_RATING_CVT 1  // f32 sources: a window's ratings converted to f64 once per lane, both halves permuted (0: permute the f32, convert per step)
+#endif
+#ifndef HREC_ALS_RATING_CVT64
+#define HREC_ALS_RATING_CVT64 1  // as HREC_ALS_RATING_CVT, f64 sources
+#endif
+
 namespace hrec {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -94,7 +108,10 @@ struct VecD {
 };
 __device__ __forceinline__ VecD struct_load_d(i4v rsrc, int vindex, int voffset) {
   const f4 lo = sbuf_load_f4(rsrc, vindex, voffset, 0, 0);
-  const f4 hi = sbuf_load_f4(rsrc, vindex, voffset + 16, 0, 0);
+  // soffset adds to the address like voffset (no swizzle; the range check is
+  // on vindex alone), as a constant of the instruction: both loads take the
+  // same (vindex, voffset) register pair
+  const f4 hi = sbuf_load_f4(rsrc, vindex, voffset, 16, 0);
   VecD v;
   v.x[0] = __hiloint2double(__float_as_int(lo.y), __float_as_int(lo.x));
   v.x[1] = __hiloint2double(__float_as_int(lo.w), __float_as_int(lo.z));
@@ -166,6 +183,10 @@ __device__ __forceinline__ double bcast(double v, int src) {
   const int hi = __builtin_amdgcn_readlane((int)(x >> 32), src);
   return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
 }
+
+// v_writelane_b32: `old` with lane `lane` replaced by the wave-uniform `src`
+// (this compiler has no builtin for it; declared like the buffer loads of common.h).
+__device__ int writelane_i32(int src, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
 
 // Orders this wave's LDS accesses around a point (one wave owns each LDS
 // slice; a wave's LDS operations complete in issue order).
@@ -295,7 +316,18 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
     ii = p < end ? iraw : -1;
     vv = p < end ? vraw : 0.f;
   };
-  auto bperm = [&](int win, int s) -> int { return __builtin_amdgcn_ds_bpermute(bp_addr + 16 * s, win); };
+  // bpw[u]: bp_addr, made opaque once per window below, so that the constant
+  // part of every step's address stays in the loop and folds into the
+  // instruction's offset field (hoisted, the 16 sums are 16 registers or an
+  // add per permute). One copy per use in the step — u = 0 the ring index,
+  // 1 the rotated loads' index, 2 the rating: a sum shared between two steps
+  // would be formed once, in the earlier one, and reach the later in a register.
+  constexpr int kBpImm = S64 ? HREC_ALS_BPERM_IMM64 : HREC_ALS_BPERM_IMM;  // copies (0: none, hoisted sums)
+  static_assert(kBpImm >= 0 && kBpImm <= 3, "one base per use at the most");
+  int bpw[3] = {bp_addr, bp_addr, bp_addr};
+  auto bperm = [&](int win, int s, int u = 0) -> int {
+    return __builtin_amdgcn_ds_bpermute(bpw[u < kBpImm ? u : (kBpImm > 0 ? kBpImm - 1 : 0)] + 16 * s, win);
+  };
   const int64_t nsteps = (n + 3) >> 2;
   int iw0, iw1;
   float rw0, rw1;
@@ -370,6 +402,13 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
     int iw2;
     float rw2;
     load_win(w + 2, iw2, rw2);
+    if constexpr (kBpImm == 3) asm volatile("" : "+v"(bpw[0]), "+v"(bpw[1]), "+v"(bpw[2]));
+    else if constexpr (kBpImm == 2) asm volatile("" : "+v"(bpw[0]), "+v"(bpw[1]));
+    else if constexpr (kBpImm == 1) asm volatile("" : "+v"(bpw[0]));
+    // kRatCvt: the current window's ratings as f64, converted here once per
+    // lane (exact for every float); a step then permutes the two halves
+    constexpr bool kRatCvt = (S64 ? HREC_ALS_RATING_CVT64 : HREC_ALS_RATING_CVT) != 0;
+    const long long rd0 = __double_as_longlong((double)rw0);
     bool stop = false;
     const int rem = __builtin_amdgcn_readfirstlane((int)(nsteps - 16 * w < 16 ? nsteps - 16 * w : 16));
 #pragma unroll
@@ -393,14 +432,18 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
           apair[t] = (double)rotA[s % PR].x[t];
           ar2[t] = (double)rotB[s % PR].x[t];
         }
-        const int vr = (s + PR < 16) ? bperm(iw0, s + PR) : bperm(iw1, s + PR - 16);
+        const int vr = (s + PR < 16) ? bperm(iw0, s + PR, 1) : bperm(iw1, s + PR - 16, 1);
         if constexpr (!kRot1Dpp) rot1[s % PR] = rot_load(vr, voff1);
         rotA[s % PR] = pair_load(vr, voff + hoff);
         rotB[s % PR] = pair_load(vr, voff2 + hoff);
       }
       nidx = (s + 1 + PF < 16) ? bperm(iw0, s + 1 + PF) : bperm(iw1, s + 1 + PF - 16);
-      const float rf = __int_as_float(__builtin_amdgcn_ds_bpermute(bp_addr + 16 * s, __float_as_int(rw0)));
-      const double rv = (double)rf;
+      double rv;
+      if constexpr (kRatCvt) {
+        rv = __hiloint2double(bperm((int)(rd0 >> 32), s, 2), bperm((int)rd0, s, 2));
+      } else {
+        rv = (double)__int_as_float(bperm(__float_as_int(rw0), s, 2));
+      }
       if (MODE == 1 && (s % HREC_ALS_CH1) == 0) {
 #pragma unroll
         for (int p = 0; p < NPAIR; ++p) fa[p] = f4{0.f, 0.f, 0.f, 0.f};
@@ -624,9 +667,12 @@ __device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1
   constexpr int KP = 16 * NT;
   constexpr int NPAIR = NT * (NT + 1) / 2;
   double* __restrict__ colbuf = scratch;    // two 64-entry row buffers (16-B aligned)
-  double* __restrict__ dsh = colbuf + 128;  // pivots d_r
-  double* __restrict__ rdsh = dsh + KP;     // 1 / d_r
+  double* __restrict__ dsh = colbuf + 128;  // pivots d_r (the KP doubles behind them are not used)
   const int sub = lane >> 4, col = lane & 15;
+  // kp 64: every lane of the wave owns a column, so the tests against KP are
+  // true at compile time (a caller may pass a lane the compiler cannot bound)
+  constexpr bool kFull = KP == 64;
+  const bool incol = kFull || lane < KP;
   STAMP_DECL;
   STAMP(0);
   if constexpr (HREC_ALS_ABLATE == 1) {  // timing-only: Gramian without factor/solve
@@ -638,7 +684,7 @@ __device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1
     return;
   }
   // A = Ut^T D Ut with Ut unit upper triangular, stored column-packed in LDS
-  // (Ut[tri(c) + r], r <= c), pivots d_r in dsh and 1/d_r in rdsh. A x = b is
+  // (Ut[tri(c) + r], r <= c), pivots d_r in dsh (and on lane r). A x = b is
   //   Ut^T w = b,  v = D^-1 w,  Ut x = v
   // and each of the 2 x KP substitution steps is one broadcast + one masked fma.
   // (Spark's dppsv factors A = U^T U with U = D^1/2 Ut: the same solution.)
@@ -649,6 +695,10 @@ __device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1
   // panel's critical chain — the same operands in the same (pv ascending)
   // order as a separate substitution loop, so the same bits.
   double bs = 0.0;
+  // dcap: lane pv's copy of its pivot d_pv (every pivot is wave-uniform, so a
+  // v_writelane puts it there without a lane test or a branch); a panel's 16
+  // go to dsh in one store after the panel — dq[] below is their first reader
+  double dcap = 0.0;
 #pragma unroll
   for (int J = 0; J < NT; ++J) {
     // (a) block row J -> LDS (only q <= c: the upper triangle); LDSG: every
@@ -667,10 +717,10 @@ __device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1
       }
       wave_lds_sync();
     }
-    if (J == 0) bs = lane < KP ? bsh[lane] : 0.0;
+    if (J == 0) bs = incol ? bsh[lane] : 0.0;
     // (b) lane c >= 16J owns column c of block row J
     const int c = lane;
-    const bool own = c >= 16 * J && c < KP;
+    const bool own = c >= 16 * J && incol;
     double a[16];
 #pragma unroll
     for (int m = 0; m < 16; ++m) {
@@ -688,15 +738,17 @@ __device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1
     for (int i = 0; i < 16; ++i) {
       const int pv = 16 * J + i;
       double* cb = colbuf + 64 * (i & 1);
-      if (c < KP) cb[c] = a[i];  // A[pv][c] (lane pv: the pivot)
+      if (incol) cb[c] = a[i];  // A[pv][c] (lane pv: the pivot)
       // 1 / piv: v_rcp_f64 (~2^-24 relative) + one Newton step
       const double r0 = __builtin_amdgcn_rcp(piv);
       const double r = fma(r0, fma(-piv, r0, 1.0), r0);
       const double ut = a[i] * r;  // Ut[pv][c]
       if (own && c > pv) Up[tri(c) + pv] = ut;
-      if (c == pv) {
-        dsh[pv] = piv;
-        rdsh[pv] = r;
+      {
+        const long long pb = __double_as_longlong(piv), db = __double_as_longlong(dcap);
+        const int lo = writelane_i32((int)pb, pv, (int)db);
+        const int hi = writelane_i32((int)(pb >> 32), pv, (int)(db >> 32));
+        dcap = __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
       }
       {
         const double wq = bcast(bs, pv);
@@ -713,6 +765,7 @@ __device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1
         }
       }
     }
+    if (own) dsh[c] = dcap;  // lanes of later panels: 0.0, replaced after their own panel
     wave_lds_sync();
     // (e) Ut_JK (K > J) back into tile registers, with a D_J-scaled copy;
     // (f) trailing update A_KM -= Ut_JK^T D_J Ut_JM on the f64 matrix cores
@@ -760,8 +813,10 @@ __device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1
     }
   }
   STAMP(3);  // phase 3: factorisation
-  const int lc = lane < KP ? lane : KP - 1;
-  const double myrd = rdsh[lc];
+  // 1 / d_lane: the pivot loop's r, formed again by the same two steps on the
+  // same value (lanes >= KP: not used)
+  const double rd0 = __builtin_amdgcn_rcp(dcap);
+  const double myrd = fma(rd0, fma(-dcap, rd0, 1.0), rd0);
   if constexpr (HREC_ALS_ABLATE == 3) {  // timing-only: factor without the substitutions
     if (lane < KP) out[lane] = (float)(myrd + Up[tri(lane)]);
     return;
@@ -770,12 +825,12 @@ __device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1
   // back     Ut x = v     (step q: lanes c < q subtract Ut[c][q] * x_q)
 #pragma unroll HREC_ALS_SOLVE_UNROLL
   for (int q = KP - 1; q >= 0; --q) {
-    const double u = Up[tri(q) + (lane < KP ? lane : 0)];  // Ut[lane][q] for lane < q
+    const double u = Up[tri(q) + (incol ? lane : 0)];  // Ut[lane][q] for lane < q
     const double xq = bcast(bi, q);
     if (lane < q) bi = fma(-u, xq, bi);
   }
   STAMP(4);  // phase 4: triangular solves
-  if (lane < KP) out[NT * (lane & 15) + (lane >> 4)] = (float)bi;
+  if (incol) out[NT * (lane & 15) + (lane >> 4)] = (float)bi;
   wave_lds_sync();  // the next row on this wave reuses the LDS slice
 }
 
