@@ -109,6 +109,8 @@ _SIGNATURES = {
                                    _vp, _c_i32, _vp, _vp, _vp, _vp, _vp, _c_sz, _vp]),
     "hrec_mmr_rerank": (_c_i32, [_vp, _c_i64, _c_i32, _vp, _vp, _c_i32, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _c_i64, _vp,
                                  _c_dbl, _c_i32, _vp, _vp, _vp, _vp]),
+    "hrec_als_explain": (_c_i32, [_vp, _c_i64, _c_i32, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i32, _c_i32,
+                                  _c_dbl, _c_i32, _c_dbl, _vp, _c_i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hrec_fuse_workspace_bytes": (_c_sz, [_c_i64, _c_i32]),
     "hrec_fuse_topk": (_c_i32, [_vp, _vp, _c_i32, _c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp,
                                 _c_sz, _vp]),
@@ -2083,6 +2085,62 @@ def mmr_rerank(pool, scores, vectors, inv_norm, lambda_, top_n, pool_len=None, d
         _dev(out_pos, torch.int32, "out_pos"), _dev(out_len, torch.int32, "out_len"),
         _dev(out_value, torch.float64, "out_value"), _stream()))
     return out_pos, out_len, out_value
+
+
+# ------------------------------------------------- ALS explanations
+EXPLAIN_MAX_TOP = 32  # largest top_m (HREC_EXPLAIN_MAX_TOP)
+EXPLAIN_LIST_MAX = 1024  # longest list of one kernel row
+
+
+def als_explain(lists, history, item_factors, k, reg_param, top_m, implicit=False, alpha=0.0, yty=None,
+                list_len=None, want_row=True):
+    """hrec_als_explain: per row of `lists` (int64 [n_rows, L <= 1024] device
+    item-factor rows, the first list_len[r] (int32; None: L) entries; a view
+    with a row stride is fine) and per entry i, the prediction y_i . A^-1 b
+    split into one term per entry of the row's history = (rows int64 [n_rows]
+    (-1: none), indptr int64, cols int32 item-factor rows, vals f32 ratings).
+    item_factors f32 [n_items, kp]; implicit needs yty = als_gramian of them.
+    Returns device (total f64 [n_rows, L], pos int32 [n_rows, L, top_m]:
+    positions within the row's history segment, -1 past len; val f64 of the
+    same shape, NaN past len; len int32 [n_rows, L]; row f32 [n_rows, kp]: the
+    row's own solve, or None). The same bits on every call."""
+    name = "als_explain"
+    if not isinstance(lists, torch.Tensor) or lists.dim() != 2:
+        raise HrecError(f"{name}: lists must be a 2-D device tensor")
+    if not isinstance(item_factors, torch.Tensor) or item_factors.dim() != 2:
+        raise HrecError(f"{name}: item_factors must be a 2-D device tensor")
+    n_rows, list_n = int(lists.shape[0]), int(lists.shape[1])
+    n_items, kp = int(item_factors.shape[0]), int(item_factors.shape[1])
+    dev = item_factors.device
+    l_ptr, lists, l_ld = _rows_matrix(name, "lists", lists, torch.int64, n_rows)
+    if list_len is not None and list_len.numel() != n_rows:
+        raise HrecError(f"{name}: list_len must have one entry per row")
+    h_rows, h_indptr, h_cols, h_vals = history
+    if h_rows.numel() != n_rows:
+        raise HrecError(f"{name}: hist_rows must hold one entry per row")
+    if h_cols.numel() != h_vals.numel():
+        raise HrecError(f"{name}: hist_cols and hist_vals must have one entry per rating")
+    if h_cols.numel() == 0:  # stand-in entries, never read
+        h_cols = torch.zeros(1, dtype=torch.int32, device=dev)
+        h_vals = torch.zeros(1, dtype=torch.float32, device=dev)
+    if implicit and (yty is None or tuple(yty.shape) != (kp, kp)):
+        raise HrecError(f"{name}: implicit needs yty [kp, kp]")
+    top_m = int(top_m)
+    tm = max(top_m, 0)
+    total = torch.empty((n_rows, list_n), dtype=torch.float64, device=dev)
+    pos = torch.empty((n_rows, list_n, tm), dtype=torch.int32, device=dev)
+    val = torch.empty((n_rows, list_n, tm), dtype=torch.float64, device=dev)
+    length = torch.empty((n_rows, list_n), dtype=torch.int32, device=dev)
+    row = torch.empty((n_rows, kp), dtype=torch.float32, device=dev) if want_row else None
+    _check("hrec_als_explain", lib().hrec_als_explain(
+        l_ptr, l_ld, list_n, _dev(list_len, torch.int32, "list_len"), n_rows,
+        _dev(h_rows, torch.int64, "hist_rows"), _dev(h_indptr, torch.int64, "hist_indptr"),
+        _dev(h_cols, torch.int32, "hist_cols"), _dev(h_vals, torch.float32, "hist_vals"),
+        _dev(item_factors, torch.float32, "item_factors"), n_items, int(k), kp, float(reg_param), int(bool(implicit)),
+        float(alpha), _dev(yty if implicit else None, torch.float64, "yty"), top_m,
+        _dev(total, torch.float64, "out_total"), _dev(pos, torch.int32, "out_pos"), _dev(val, torch.float64, "out_val"),
+        _dev(length, torch.int32, "out_len"), _dev(row, torch.float32, "out_row"), _stream()))
+    return total, pos, val, length, row
 
 
 # ------------------------------------------------------- multi-GPU (C-ABI)

@@ -55,6 +55,11 @@ ALSModel.transform at :75) is replaced by libhrec's HIP kernels:
                       unexpectedness; not in the reference) -> recommend's
                       column lists, still on the device ->
                       hrec_row_inv_norms + hrec_list_quality
+  explain / explain_recommendations (a prediction as a sum of one term per
+                      item of the user's history, y_i^T A_u^-1 y_j weighted by
+                      the rating; not in the reference) -> the pairs grouped
+                      into lists, or recommend's column lists, still on the
+                      device -> hrec_als_explain
 
 `initialize_spark` / `stop_spark` keep their names: they bind / release the
 HIP device session that plays the SparkSession's role.
@@ -940,6 +945,179 @@ class ALSModel:
                                       model.V, model.k, Vt=model.Vt)
         replaced = int((known & has).sum())
         out.update(users_added=int(has.sum()) - replaced, users_replaced=replaced)
+        return out
+
+    # --------------------------------------------------------- explanations
+    # Why a prediction is what it is (Hu, Koren and Volinsky 2008,
+    # section 5; `implicit`'s explain). A user row solves its normal equations,
+    # x_u = A_u^-1 b_u, so y_i . x_u = sum_j beta_j (y_i^T A_u^-1 y_j) over the
+    # user's history: one term per rated item. No counterpart in the reference
+    # or in Spark: failures raise.
+    @staticmethod
+    def _explain_top(top):
+        top = int(top)
+        if not 1 <= top <= _hrec.EXPLAIN_MAX_TOP:
+            raise ValueError(f"top must be in [1, {_hrec.EXPLAIN_MAX_TOP}] (got {top})")
+        return top
+
+    def _explain_setup(self, history, top):
+        """(model, top, history CSR pieces, counts) of an explain call."""
+        model = self._trained()
+        if self.nonnegative:
+            raise ValueError("explain: a nonnegative=True row is an NNLS solution, not A^-1 b: the prediction is not "
+                             "a sum over the history")
+        if int(model.U.shape[1]) > 64:
+            raise ValueError(f"explain supports rank <= 64 (got rank {model.k})")
+        top = self._explain_top(top)
+        h_users, h_items = _int_ids(history["userId"], "userId"), _int_ids(history["itemId"], "itemId")
+        ratings = np.asarray(history["average_review_rating"], dtype=np.float32)
+        dev = model.U.device
+        irow = model._lookup_device(h_items, "item") if h_items.size else torch.zeros(0, dtype=torch.int64, device=dev)
+        uniq, indptr, cols, vals, dropped = ranked_lists.rated_history_csr(h_users, h_items, ratings, irow, dev)
+        counts = (indptr[1:] - indptr[:-1]).cpu().numpy()
+        entry_ids = np.asarray(model.item_ids, np.int64)[cols.cpu().numpy()] if cols.numel() else np.zeros(0, np.int64)
+        yty = _hrec.als_gramian(model.V, model.k) if self.implicit_prefs and model.V.shape[0] else None
+        info = {"ratings_used": int(cols.numel()), "ratings_dropped": int(dropped)}
+        return model, top, uniq, indptr, cols, vals, counts, entry_ids, yty, info
+
+    def _history_segment(self, uniq, counts, user_ids):
+        """Each user id's row of the history CSR, -1 where it has no usable history (host int64)."""
+        user_ids = np.asarray(user_ids, np.int64)
+        if uniq.size == 0:
+            return np.full(user_ids.shape, -1, np.int64)
+        p = np.clip(np.searchsorted(uniq, user_ids), 0, uniq.size - 1)
+        return np.where((uniq[p] == user_ids) & (counts[p] > 0), p, -1).astype(np.int64)
+
+    def _explain_run(self, model, lists, list_len, hist_rows, u_rows, csr, yty, top):
+        U_rows = model.U[u_rows.clamp(min=0)]
+        return ranked_lists.explain_lists(lists, list_len, hist_rows, csr, model.V, model.k, float(self.reg_param), top,
+                                          implicit=bool(self.implicit_prefs), alpha=float(self.alpha), yty=yty,
+                                          U_rows=U_rows)
+
+    def explain(self, data, history, top=5):
+        """Explain the predictions of `data`'s (userId, itemId) pairs by the
+        user's history. history: a frame with userId, itemId and
+        average_review_rating, typically the training frame or the frame given
+        to fold_in_users; its rows whose item the model does not know are
+        dropped, the others keep frame order inside a user (as in
+        fold_in_users). Returns a copy of `data` (every row kept) with
+          prediction: transform's f32 prediction, with its bits;
+          explained: f64, the sum of ALL the history's contributions - the
+            prediction again, up to the f32 rounding of the stored user row,
+            when `history` is what the row was fitted on;
+          contributions: up to `top` (1 .. 32) (itemId, contribution) tuples of
+            the user's own history, largest first; equal contributions keep
+            the earlier history row first.
+        A pair whose user or item the model does not know, or whose user has no
+        usable history, gets explained NaN and an empty list. With this
+        instance's reg_param, implicit_prefs / alpha (implicit: only ratings
+        > 0 contribute). nonnegative=True and rank > 64 raise ValueError. The
+        pairs are grouped per user on the device into lists of at most 1024
+        (one kernel row each, hrec_als_explain).
+        frame.attrs["explain"] = {"ratings_used", "ratings_dropped",
+        "users_without_history", "max_refit_gap"}: max_refit_gap is the largest
+        |A^-1 b - stored row| component over the explained users - f32 rounding
+        when `history` is what the rows were fitted on, large when it is not.
+        One GPU; under a torch.distributed world every rank does the same
+        work, without collectives."""
+        model, top, uniq, indptr, cols, vals, counts, entry_ids, yty, info = self._explain_setup(history, top)
+        users, items = _int_ids(data["userId"], "userId"), _int_ids(data["itemId"], "itemId")
+        dev = model.U.device
+        n = int(users.size)
+        pred = model.predict_pairs(users, items).cpu().numpy() if n else np.zeros(0, np.float32)
+        urow, irow = (model._lookup(model.user_ids, users), model._lookup(model.item_ids, items))
+        seg = self._history_segment(uniq, counts, users)
+        known_users = np.unique(users[urow >= 0])
+        info["users_without_history"] = int((self._history_segment(uniq, counts, known_users) < 0).sum())
+        explained = np.full(n, np.nan, np.float64)
+        contributions = [[] for _ in range(n)]
+        ok = (urow >= 0) & (irow >= 0) & (seg >= 0)
+        info["max_refit_gap"] = 0.0
+        if ok.any():
+            L_MAX = _hrec.EXPLAIN_LIST_MAX
+            idx = torch.as_tensor(np.nonzero(ok)[0], device=dev)
+            seg_d = torch.as_tensor(seg, device=dev)[idx]
+            order = torch.sort(seg_d, stable=True).indices  # grouped by user, frame order inside a user
+            idx, seg_s = idx[order], seg_d[order]
+            useg, cnt = torch.unique_consecutive(seg_s, return_counts=True)
+            start = torch.cumsum(cnt, 0) - cnt
+            rows_per = (cnt + L_MAX - 1) // L_MAX  # kernel rows of each user
+            row0 = torch.cumsum(rows_per, 0) - rows_per
+            group = torch.repeat_interleave(torch.arange(useg.numel(), device=dev), cnt)
+            within = torch.arange(idx.numel(), device=dev) - start[group]
+            krow = row0[group] + within // L_MAX
+            slot = within % L_MAX
+            R, L = int(rows_per.sum().item()), int(min(L_MAX, int(cnt.max().item())))
+            lists = torch.full((R, L), -1, dtype=torch.int64, device=dev)
+            lists[krow, slot] = torch.as_tensor(irow, device=dev)[idx]
+            hist_rows = torch.repeat_interleave(useg, rows_per)
+            u_rows = torch.zeros(R, dtype=torch.int64, device=dev)
+            u_rows[krow] = torch.as_tensor(urow, device=dev)[idx]
+            total, pos, val, length, gap = self._explain_run(model, lists, None, hist_rows, u_rows,
+                                                             (indptr, cols, vals), yty, top)
+            at = idx.cpu().numpy()
+            explained[at] = total[krow, slot].cpu().numpy()
+            seg_start = indptr[seg_s].cpu().numpy()
+            tuples = ranked_lists.explain_tuples(pos[krow, slot].cpu().numpy(), val[krow, slot].cpu().numpy(),
+                                                 length[krow, slot].cpu().numpy(), seg_start, entry_ids)
+            for p, t in zip(at.tolist(), tuples):
+                contributions[p] = t
+            info["max_refit_gap"] = float(gap.item())
+        out = data.copy()
+        out["prediction"] = pred
+        out["explained"] = explained
+        out["contributions"] = contributions
+        out.attrs["explain"] = info
+        return out
+
+    def explain_recommendations(self, users, num_items, history, top=5, exclude=None):
+        """recommend_for_user_subset with the reasons: a DataFrame with one
+        row per known user of `users`, `userId` ascending, `recommendations`:
+        (itemId, rating, [(itemId, contribution), ...]) tuples - the ids and
+        rating bits of recommend_for_user_subset(users, num_items, exclude),
+        each with explain's contributions for that pair - and `explained`: per
+        list entry explain's f64 sum (NaN for a user without usable history,
+        whose tuples carry empty lists). history, top and
+        frame.attrs["explain"] are explain's; exclude works as everywhere else
+        (exclude=history is the usual call). The top-k's column matrix goes
+        into hrec_als_explain without leaving the device."""
+        import pandas as pd
+
+        model, top, uniq, indptr, cols, vals, counts, entry_ids, yty, info = self._explain_setup(history, top)
+        ids = np.asarray(model.user_ids, np.int64)
+        if isinstance(users, pd.DataFrame):
+            users = users["userId"]
+        keys = np.unique(_int_ids(np.asarray(users).reshape(-1), "userId"))
+        rows = model._lookup(ids, keys)
+        rows = rows[rows >= 0]
+        dev = model.U.device
+        excl = None if exclude is None else self._exclusion("user", exclude)
+        lists, scores, lens = model.recommend("user", rows, num_items, exclude=excl, _columns=True)
+        seg = self._history_segment(uniq, counts, ids[rows])
+        info["users_without_history"] = int((seg < 0).sum())
+        info["max_refit_gap"] = 0.0
+        n, kk = int(lists.shape[0]), int(lists.shape[1])
+        lens_h = np.full(n, kk, np.int64) if lens is None else lens.cpu().numpy().astype(np.int64)
+        item_ids = np.asarray(model.item_ids, np.int64)
+        recs, expl = [[] for _ in range(n)], [[] for _ in range(n)]
+        if n and kk:
+            total, pos, val, length, gap = self._explain_run(
+                model, lists, lens, torch.as_tensor(seg, device=dev), torch.as_tensor(rows, device=dev),
+                (indptr, cols, vals), yty, top)
+            info["max_refit_gap"] = float(gap.item())
+            seg_start = np.repeat(indptr[torch.as_tensor(np.maximum(seg, 0), device=dev)].cpu().numpy(), kk)
+            tuples = ranked_lists.explain_tuples(pos.reshape(n * kk, top).cpu().numpy(),
+                                                 val.reshape(n * kk, top).cpu().numpy(),
+                                                 length.reshape(n * kk).cpu().numpy(), seg_start, entry_ids)
+            cols_h = lists.cpu().numpy()
+            rec_ids = item_ids[np.clip(cols_h, 0, max(item_ids.size - 1, 0))].tolist()
+            sc, tot = scores.cpu().numpy().tolist(), total.cpu().numpy().tolist()
+            for r in range(n):
+                m = int(lens_h[r])
+                recs[r] = [(rec_ids[r][e], sc[r][e], tuples[r * kk + e]) for e in range(m)]
+                expl[r] = tot[r][:m]
+        out = pd.DataFrame({"userId": ids[rows], "recommendations": recs, "explained": expl})
+        out.attrs["explain"] = info
         return out
 
     # ------------------------------------------------ recommendForAll / Subset

@@ -532,3 +532,76 @@ def lists_frame(key_col, keys, ids, val, lens=None):
     if lens is not None:  # each list cut to its length
         recs = [rec[:m] for rec, m in zip(recs, lens.cpu().numpy().tolist())]
     return pd.DataFrame({key_col: keys, "recommendations": recs})
+
+
+# ------------------------------------------------------- ALS explanations
+# Why an ALS prediction is what it is (hrec_als_explain): a user
+# row solves its normal equations, so a prediction is a sum of one term per
+# entry of the user's history.
+EXPLAIN_ROWS = 1 << 16  # kernel rows of one hrec_als_explain call
+
+
+def rated_history_csr(users, items, ratings, item_rows, dev):
+    """The rated history of a frame as a CSR over its distinct users: (user
+    ids int64 numpy, sorted; indptr int64 device [n_users + 1]; cols int32
+    device: item-factor rows; vals f32 device; dropped: the rows whose item is
+    unknown). item_rows: int64 device, each row's item-factor row or -1. Rows
+    of an unknown item are dropped; inside a user the others keep frame order,
+    as in ALSModel.fold_in_users (the f64 sums depend on it)."""
+    uniq, inv = np.unique(np.asarray(users, np.int64).reshape(-1), return_inverse=True)
+    keep = item_rows >= 0
+    inv_k = torch.as_tensor(np.ascontiguousarray(inv.reshape(-1)), device=dev)[keep]
+    counts = torch.bincount(inv_k, minlength=int(uniq.size)) if uniq.size else torch.zeros(0, dtype=torch.int64,
+                                                                                          device=dev)
+    order = torch.sort(inv_k, stable=True).indices
+    indptr = torch.zeros(int(uniq.size) + 1, dtype=torch.int64, device=dev)
+    indptr[1:] = torch.cumsum(counts, 0)
+    cols = item_rows[keep][order].to(torch.int32).contiguous()
+    vals = torch.as_tensor(np.ascontiguousarray(np.asarray(ratings, np.float32).reshape(-1)),
+                           device=dev)[keep][order].contiguous()
+    return uniq, indptr, cols, vals, int(item_rows.numel()) - int(inv_k.numel())
+
+
+def explain_lists(lists, list_len, hist_rows, csr, V, k, reg_param, top, implicit=False, alpha=0.0, yty=None,
+                  U_rows=None):
+    """hrec_als_explain over the rows of `lists` (int64 device [R, L <= 1024]
+    item-factor rows; list_len int32 [R] or None) in sub-batches of
+    EXPLAIN_ROWS: device (total f64 [R, L], pos int32 [R, L, top], val f64,
+    len int32 [R, L], gap). hist_rows int64 [R]: each row's segment of csr =
+    (indptr, cols, vals), -1: none. U_rows (optional, f32 [R, kp]): the stored
+    factor row of each kernel row's user; gap is then the largest |row's own
+    solve - stored row| over the rows with an explanation (a device scalar,
+    0 when there is none)."""
+    dev = V.device
+    R, L = int(lists.shape[0]), int(lists.shape[1])
+    total = torch.empty((R, L), dtype=torch.float64, device=dev)
+    pos = torch.empty((R, L, top), dtype=torch.int32, device=dev)
+    val = torch.empty((R, L, top), dtype=torch.float64, device=dev)
+    length = torch.empty((R, L), dtype=torch.int32, device=dev)
+    gap = torch.zeros((), dtype=torch.float32, device=dev)
+    for s in range(0, R, EXPLAIN_ROWS):
+        sl = slice(s, min(s + EXPLAIN_ROWS, R))
+        t, p, v, n, row = _hrec.als_explain(
+            lists[sl], (hist_rows[sl].contiguous(), *csr), V, k, reg_param, top, implicit=implicit, alpha=alpha,
+            yty=yty, list_len=None if list_len is None else list_len[sl].contiguous(), want_row=U_rows is not None)
+        total[sl], pos[sl], val[sl], length[sl] = t, p, v, n
+        if U_rows is not None and L:
+            used = (n > 0).any(dim=1)
+            d = (row - U_rows[sl]).abs().amax(dim=1)
+            d = torch.where(used, d, torch.zeros_like(d))
+            if d.numel():
+                gap = torch.maximum(gap, d.max())
+    return total, pos, val, length, gap
+
+
+def explain_tuples(pos, val, length, seg_start, entry_ids):
+    """Host: per list entry its [(itemId, contribution), ...], largest first.
+    pos / val / length: numpy [n, top] / [n, top] / [n] of n list entries;
+    seg_start int64 [n]: where the entry's history segment starts in entry_ids
+    (the raw item id of every history entry, int64 numpy)."""
+    n, top = pos.shape
+    live = np.arange(top)[None, :] < length[:, None]
+    where = np.where(live, seg_start[:, None] + pos, 0)
+    ids = entry_ids[where] if entry_ids.size else np.zeros_like(where)
+    ids_l, val_l, len_l = ids.tolist(), val.tolist(), length.tolist()
+    return [list(zip(i[:m], v[:m])) for i, v, m in zip(ids_l, val_l, len_l)]

@@ -36,6 +36,8 @@
  *                                                          hrec_list_quality
  *   Greedy MMR re-ranking of a candidate pool
  *          (no reference line)                        -> hrec_mmr_rerank
+ *   ALS predictions explained by the user's history
+ *          (no reference line)                        -> hrec_als_explain
  *   Keras  two-tower graph   src/two_tower_model.py:38-89 -> hrec_tt_*
  *   Keras  fit of one user-embedding row, everything else
  *          frozen, for new users (no reference line)  -> hrec_tt_fold_in_users
@@ -886,6 +888,68 @@ int hrec_mmr_rerank(const int64_t* pool, int64_t pool_ld, int pool_n, const int3
                     int64_t n, const float* vectors, int d, int64_t ld, const double* inv_norm,
                     double lambda, int top_n, int32_t* out_pos, int32_t* out_len,
                     double* out_value, void* stream);
+
+/* ALS predictions explained by the user's history (additive to ABI 7; Hu,
+ * Koren and Volinsky 2008, section 5). A user row is the solution of its
+ * normal equations, x = A^-1 b with b = sum_j beta_j y_j over the history, so
+ * a prediction is a sum of one term per history entry:
+ *   y_i . x = sum_j c_ij,   c_ij = beta_j * (y_i^T A^-1 y_j).
+ *
+ * hrec_als_explain: lists [n_rows][lists_ld] int64 holds candidate COLUMNS
+ * (rows of item_factors; a top-k result before the id gather, as in
+ * hrec_list_quality), row r's list in its first min(list_len[r], list_n)
+ * entries (list_len int32 [n_rows]; NULL: list_n). 0 <= list_n <= 1024,
+ * lists_ld >= list_n.
+ * History: a CSR addressed like hrec_list_quality's, plus ratings: row r reads
+ * hist_cols (int32 rows of item_factors) and hist_vals (f32 ratings) at
+ * [hist_indptr[q], hist_indptr[q + 1]) with q = hist_rows[r]; q < 0: no
+ * history. Several rows may name the same q (how a user with more than 1024
+ * pairs is split). History columns outside [0, n_items) are an error of the
+ * caller's (the half-sweeps' contract for CSR indices).
+ * item_factors f32 [n_items][kp], kp = 16, 32 or 64, 1 <= k <= kp, padding
+ * columns zero; reg_param >= 0; implicit 0 or 1; alpha >= 0; yty =
+ * hrec_als_gramian of the same factors (required when implicit, ignored
+ * otherwise); 1 <= top_m <= HREC_EXPLAIN_MAX_TOP.
+ * Per row, with n history entries (duplicates stay separate terms):
+ *   implicit == 0: A = sum_j y_j y_j^T + reg_param n I, beta_j = r_j; every
+ *     entry is eligible (hrec_als_half_sweep's A and b);
+ *   implicit == 1: c1_j = alpha |r_j|, A = yty + sum_j c1_j y_j y_j^T +
+ *     reg_param n_pos I, beta_j = 1 + c1_j where r_j > 0 and 0 otherwise;
+ *     the entries with r_j > 0 (n_pos of them) are eligible
+ *     (hrec_als_half_sweep_implicit's A and b).
+ * Sources are converted to f64 and accumulated in f64 on the matrix cores,
+ * A = Ut^T D Ut once per row (the half-sweep's own pipeline). For each valid
+ * list entry i: A w_i = y_i by two f64 substitutions, then per history entry
+ * c_ij = beta_j * (w_i . y_j), the dot an f64 fma chain over the components in
+ * ascending order.
+ * Outputs (positions are POSITIONS WITHIN THE ROW'S HISTORY SEGMENT):
+ *   out_total f64 [n_rows][list_n]: sum of c_ij over the eligible j — lane l
+ *     of the row's wave adds entries l, l + 64, ... in order, then a fixed xor
+ *     tree over the 64 partials;
+ *   out_pos int32 / out_val f64 [n_rows][list_n][top_m]: the top_m largest
+ *     c_ij of the eligible entries, descending, equal values: the earlier
+ *     position first; past out_len, -1 and NaN;
+ *   out_len int32 [n_rows][list_n] = min(top_m, eligible entries);
+ *   out_row f32 [n_rows][kp] (optional, NULL skips it): the row's own solve
+ *     A^-1 b, in the half-sweep's layout with its padding zeros — the bits
+ *     the half-sweep stores for the same CSR row; zero for a row without
+ *     history or (implicit) without a rating > 0.
+ * A list entry past the row's length or outside [0, n_items) (-1 included) is
+ * never used as an index and gets out_len 0, out_total NaN, positions -1 and
+ * values NaN. So does every entry of a row without history, without an
+ * eligible entry, or whose factorisation is unusable (a pivot that is not
+ * positive and finite, or a non-finite x: reg_param = 0 with singular
+ * equations).
+ * One wave per row. No floating-point atomics and fixed orders throughout:
+ * equal inputs give equal bits on every call. No workspace. n_rows == 0 or
+ * list_n == 0 returns HREC_OK and touches nothing. */
+#define HREC_EXPLAIN_MAX_TOP 32
+int hrec_als_explain(const int64_t* lists, int64_t lists_ld, int list_n, const int32_t* list_len,
+                     int64_t n_rows, const int64_t* hist_rows, const int64_t* hist_indptr,
+                     const int32_t* hist_cols, const float* hist_vals, const float* item_factors,
+                     int64_t n_items, int k, int kp, double reg_param, int implicit, double alpha,
+                     const double* yty, int top_m, double* out_total, int32_t* out_pos,
+                     double* out_val, int32_t* out_len, float* out_row, void* stream);
 
 /* ------------------------------------------------------ cold-start sim --
  * ALSModel._find_similar_items (src/als_model.py:93-104): out[q*n_items+j] =
