@@ -91,7 +91,7 @@ __device__ __forceinline__ void explain_merge(double v, bool live, int pos0, int
                                               int& lp) {
   const double ninf = -__builtin_inf();
   for (;;) {
-    if (L == top_m) live = live && v > bcast(lv, top_m - 1);
+    if (L == top_m) live = live && v > lane_read(lv, top_m - 1);
     if (__ballot(live) == 0) break;
     double bv = live ? v : ninf;
     int bl = live ? lane : kWave;
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(64) void als_explain_kernel(const ExplainParams P) 
       double z[4];
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        const int c = __builtin_amdgcn_readlane(gv, (p0 + s) & (kExGroup - 1));
+        const int c = lane_read(gv, (p0 + s) & (kExGroup - 1));
         z[s] = (c >= 0 && incol) ? (double)P.items[(int64_t)c * KP + phys] : 0.0;
       }
       // forward  Ut^T z = y   (step pv: lanes c > pv subtract Ut[pv][c] * z_pv)
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(64) void als_explain_kernel(const ExplainParams P) 
         const double u = act ? lds[tri(lane) + pv] : 0.0;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-          const double zq = bcast(z[s], pv);
+          const double zq = lane_read(z[s], pv);
           if (act) z[s] = fma(-u, zq, z[s]);
         }
       }
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(64) void als_explain_kernel(const ExplainParams P) 
         const double u = lds[tri(c) + (act ? lane : 0)];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-          const double wq = bcast(z[s], c);
+          const double wq = lane_read(z[s], c);
           if (act) z[s] = fma(-u, wq, z[s]);
         }
       }
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(64) void als_explain_kernel(const ExplainParams P) 
       }
     }
     for (int t = 0; t < gn; ++t) psh[t * kWave + lane] = 0.0;
-    wave_lds_sync();
+    wave_lds_fence();
 
     // ---- the history, 64 entries per window
     int64_t elig_before = 0;
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(64) void als_explain_kernel(const ExplainParams P) 
         if (lane < L) topv[t * kExTopMax + lane] = lv, topp[t * kExTopMax + lane] = lp;
       }
       elig_before += ne;
-      wave_lds_sync();
+      wave_lds_fence();
     }
 
     // ---- the group's outputs
@@ -280,7 +280,7 @@ __global__ __launch_bounds__(64) void als_explain_kernel(const ExplainParams P) 
         continue;
       }
       double tot = psh[t * kWave + lane];
-#pragma unroll
+#pragma unroll  // written out: wave_xor_sum here changes the generated code
       for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off, kWave);
       if (lane == 0) {
         P.out_total[o] = Lf > 0 ? tot : nan;
@@ -291,7 +291,7 @@ __global__ __launch_bounds__(64) void als_explain_kernel(const ExplainParams P) 
         P.out_val[o * top_m + lane] = lane < Lf ? topv[t * kExTopMax + lane] : nan;
       }
     }
-    wave_lds_sync();  // the next group rewrites w, the partials and the lists
+    wave_lds_fence();  // the next group rewrites w, the partials and the lists
   }
 }
 

@@ -7,28 +7,8 @@
 namespace hrec {
 
 // ---- non-negative least squares (Spark's nonnegative = true) ---------------
-// Sum over the wave of one double per lane, wave-uniform: rotations inside
-// each 16-lane row (DPP), then the four row sums by v_readlane.
-__device__ __forceinline__ double wave_sum(double v) {
-  v += row_ror<8>(v);
-  v += row_ror<4>(v);
-  v += row_ror<2>(v);
-  v += row_ror<1>(v);
-  return (bcast(v, 0) + bcast(v, 16)) + (bcast(v, 32) + bcast(v, 48));
-}
-
-__device__ __forceinline__ double wave_min(double v) {
-  v = fmin(v, row_ror<8>(v));
-  v = fmin(v, row_ror<4>(v));
-  v = fmin(v, row_ror<2>(v));
-  v = fmin(v, row_ror<1>(v));
-  return fmin(fmin(bcast(v, 0), bcast(v, 16)), fmin(bcast(v, 32), bcast(v, 48)));
-}
-
-// A wave-uniform condition as a scalar, so that the branch on it is a scalar
-// branch (every lane computed it from broadcast values).
-__device__ __forceinline__ bool uniform(bool c) { return __builtin_amdgcn_readfirstlane((int)c) != 0; }
-
+// The wave's sums and minimum are wave_row_sum / wave_row_min (csrc/wave.h:
+// wave-uniform, the DPP-row order); the branches on them go through uniform().
 // y_lane = sum_j arow[j] v[j]: the lane's row of A from registers, v from LDS
 // as wave-uniform 16-B reads (a broadcast: no bank conflicts); four chains.
 template <int KP>
@@ -79,7 +59,7 @@ __device__ __forceinline__ int nnls_row(int lane, d4 (&acc)[NT * (NT + 1) / 2], 
       }
     }
   }
-  wave_lds_sync();
+  wave_lds_fence();
   const bool live = lane < KP && NT * col + sub < k;  // sub = the tile T of lane q = 16 T + m when lane < KP
   const int me = lane < KP ? lane : 0;
   double arow[KP];
@@ -94,25 +74,25 @@ __device__ __forceinline__ int nnls_row(int lane, d4 (&acc)[NT * (NT + 1) / 2], 
   };
   for (; iterno < iter_max; ++iterno) {
     if (lane < KP) xb[lane] = x;
-    wave_lds_sync();
+    wave_lds_fence();
     const double res = live ? symv<KP>(arow, xb) - b : 0.0;
     const double grad = (res > 0.0 && x == 0.0) ? 0.0 : res;
-    const double ngrad = wave_sum(grad * grad);
-    const double nx = wave_sum(x * x);
+    const double ngrad = wave_row_sum(grad * grad);
+    const double nx = wave_row_sum(x * x);
     const bool cg = iterno > last_wall + 1;  // wave-uniform
     const double dirc = cg ? fma(ngrad / last_norm, last_dir, grad) : grad;
     if (lane < KP) {
       gb[lane] = grad;
       db[lane] = dirc;
     }
-    wave_lds_sync();
+    wave_lds_fence();
     const double ag = live ? symv<KP>(arow, gb) : 0.0;
-    double step = wave_sum(grad * res) / (wave_sum(ag * grad) + 1e-20);
+    double step = wave_row_sum(grad * res) / (wave_row_sum(ag * grad) + 1e-20);
     double dir = grad, ndir = ngrad;
     if (cg) {
       const double ad = live ? symv<KP>(arow, db) : 0.0;
-      const double dstep = wave_sum(dirc * res) / (wave_sum(ad * dirc) + 1e-20);
-      const double ndirc = wave_sum(dirc * dirc);
+      const double dstep = wave_row_sum(dirc * res) / (wave_row_sum(ad * dirc) + 1e-20);
+      const double ndirc = wave_row_sum(dirc * dirc);
       if (!uniform(stop(dstep, ndirc, nx))) {  // else: reject the CG step, dir = grad
         dir = dirc;
         ndir = ndirc;
@@ -124,7 +104,7 @@ __device__ __forceinline__ int nnls_row(int lane, d4 (&acc)[NT * (NT + 1) / 2], 
     // entry that fails its test against the shrunken step has a ratio
     // x_i / dir_i no smaller than that step, so the result is the minimum of
     // the ratios over the entries that pass the test against the INITIAL step.
-    step = fmin(step, wave_min(step * dir > x ? x / dir : __builtin_inf()));
+    step = fmin(step, wave_row_min(step * dir > x ? x / dir : __builtin_inf()));
     const bool hit = step * dir > x * (1.0 - 1e-14);
     x = hit ? 0.0 : x - step * dir;
     if (__ballot(hit) != 0ull) last_wall = iterno;
@@ -132,7 +112,7 @@ __device__ __forceinline__ int nnls_row(int lane, d4 (&acc)[NT * (NT + 1) / 2], 
     last_norm = ngrad;
   }
   if (lane < KP) out[NT * col + sub] = (float)x;
-  wave_lds_sync();  // the next row on this wave reuses the LDS slice
+  wave_lds_fence();  // the next row on this wave reuses the LDS slice
   return iterno;
 }
 

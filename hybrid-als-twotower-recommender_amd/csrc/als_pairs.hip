@@ -75,7 +75,7 @@ __global__ __launch_bounds__(kPairBlock) void als_pairs_kernel(
     srow[w][0][lane] = mu;
     srow[w][1][lane] = mv;
     fetch_ids(t + t_step, ur, ir, y);
-    pair_wave_sync();
+    wave_lds_fence();
     float acc = 0.f;
     for (int c0 = 0; c0 < k; c0 += CW) {
 #pragma unroll
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(kPairBlock) void als_pairs_kernel(
           o[3] = a[i].w * b[i].w;
         }
       }
-      pair_wave_sync();
+      wave_lds_fence();
       const int kc = k - c0 < CW ? k - c0 : CW;
       const float* __restrict__ mine = tile + lane * STR;
       int c = 0;
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(kPairBlock) void als_pairs_kernel(
         for (int e = 0; e < 8; ++e) acc = acc + x[e];
       }
       for (; c < kc; ++c) acc = acc + mine[c];
-      pair_wave_sync();  // the next chunk / tile overwrites the products
+      wave_lds_fence();  // the next chunk / tile overwrites the products
     }
     const float pred = known ? acc : __builtin_nanf("");
     if (p < n) {
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(kPairBlock) void als_pairs_kernel(
   // lanes (xor tree), then the four waves in wave order: a fixed order
 #pragma unroll
   for (int i = 0; i < HREC_PAIR_SUMS; ++i) {
-#pragma unroll
+#pragma unroll  // written out: wave_xor_sum here changes the generated code
     for (int off = 32; off > 0; off >>= 1) s[i] += __shfl_xor(s[i], off, kWave);
     if (lane == 0) red[w][i] = s[i];
   }

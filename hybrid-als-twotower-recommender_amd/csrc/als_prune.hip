@@ -1,7 +1,10 @@
+#include <float.h>
+
 #include "cascade.h"
 #include "exclusion.h"
-#include "hybrid_common.h"
+#include "order.h"  // bf16_rne, f32_up / f32_down
 #include "score.h"
+#include "wave.h"  // lanes_below, wave_xor_max
 
 using namespace hrec;
 
@@ -51,17 +54,6 @@ constexpr int kPruneSample = 8192;
 // no faster)
 constexpr int kPruneSampleUB = 64;
 
-__device__ __forceinline__ float pr_up(double x) {
-  float f = (float)x;
-  if ((double)f < x) f = nextafterf(f, INFINITY);
-  return f;
-}
-__device__ __forceinline__ float pr_down(double x) {
-  float f = (float)x;
-  if ((double)f > x) f = nextafterf(f, -INFINITY);
-  return f;
-}
-
 // Item operand: bf16 rows [N][dk] (zero beyond k) and the largest row norm
 // rounded up (+inf for a non-finite value), one thread per row.
 __global__ __launch_bounds__(256) void als_items_bf16_kernel(const float* __restrict__ V, int64_t ldv, int64_t N,
@@ -81,12 +73,8 @@ __global__ __launch_bounds__(256) void als_items_bf16_kernel(const float* __rest
     }
   }
   const double nrm = sqrt(ss) * (1.0 + 1e-6);
-  unsigned f = __float_as_uint((bad || !(nrm < 0x1p60)) ? INFINITY : pr_up(nrm));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned o = (unsigned)__shfl_xor((int)f, off, kWave);
-    f = o > f ? o : f;  // non-negative floats order as their bits
-  }
+  unsigned f = __float_as_uint((bad || !(nrm < 0x1p60)) ? INFINITY : f32_up(nrm));
+  f = wave_xor_max(f);  // non-negative floats order as their bits
   if ((threadIdx.x & 63) == 0) atomicMax(max_norm, f);
 }
 
@@ -131,10 +119,10 @@ __device__ __forceinline__ void pr_bounds(int b, double t, const double* __restr
   float t1 = INFINITY, t2 = INFINITY;  // unknown user / no bound: nothing passes
   if (e == e) {
     const double lo1 = t - e;
-    const double lo2 = (double)pr_down(lo1) - e;
+    const double lo2 = (double)f32_down(lo1) - e;
     if (isfinite(t) && isfinite(e) && isfinite(lo2)) {
-      t1 = pr_down(lo1);
-      t2 = pr_down(lo2);
+      t1 = f32_down(lo1);
+      t2 = f32_down(lo2);
       if (!isfinite(t2)) t2 = -FLT_MAX;  // below every finite f32 score
       if (!isfinite(t1)) t1 = -FLT_MAX;
     } else {

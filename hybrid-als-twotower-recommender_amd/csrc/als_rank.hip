@@ -26,7 +26,7 @@
 // machine. The sums over rows: each wave adds its rows in ascending order,
 // the block adds its four waves in wave order into one partial, a second
 // launch adds the partials in a fixed order (no floating-point atomics).
-#include "common.h"
+#include "wave.h"  // wave_lds_fence, wave_xor_sum
 
 namespace hrec {
 
@@ -35,12 +35,6 @@ constexpr int kRankMaxBlocks = 2048;  // grid cap: the rows beyond are taken in 
 constexpr int kRankLdsLabels = 512;   // label rows up to this many entries are searched in LDS
 constexpr int kRankMax = 1024;        // largest k and list length
 constexpr int kRankBatch = 8;         // label loads per lane in flight (64 * 8 = one LDS slice)
-
-__device__ __forceinline__ void rank_wave_sync() {  // a wave's LDS operations complete in issue order
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Blocks of a launch over n rows: a function of n alone (one partial layout,
 // one summation order per n).
@@ -119,10 +113,10 @@ __global__ __launch_bounds__(kRankBlock) void ranking_metrics_kernel(
         }
       }
     }
-#pragma unroll
+#pragma unroll  // written out: wave_xor_sum here changes the generated code
     for (int off = 32; off > 0; off >>= 1) distinct += __shfl_xor(distinct, off, kWave);
     if (desc) *unsorted = 1;  // every writer stores the same value
-    rank_wave_sync();
+    wave_lds_fence();
     const int64_t* a = staged ? slab[w] : row;
     const int64_t m = distinct;
 
@@ -152,7 +146,7 @@ __global__ __launch_bounds__(kRankBlock) void ranking_metrics_kernel(
         }
       }
     }
-    rank_wave_sync();  // the next row overwrites the LDS copy
+    wave_lds_fence();  // the next row overwrites the LDS copy
     double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     if (m > 0) {
       const int64_t mk = m < k ? m : (int64_t)k;
@@ -196,8 +190,7 @@ __global__ __launch_bounds__(64 * HREC_RANK_SUMS) void ranking_reduce_kernel(con
   const int lane = threadIdx.x & 63, i = threadIdx.x >> 6;
   double v = 0.0;
   for (int64_t b = lane; b < n_blocks; b += 64) v += partials[b * HREC_RANK_SUMS + i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+  v = wave_xor_sum(v);
   if (lane == 0) sums[i] = v;
 }
 

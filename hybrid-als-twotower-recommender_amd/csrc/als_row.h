@@ -4,7 +4,7 @@
 #pragma once
 #include <type_traits>
 
-#include "common.h"
+#include "wave.h"  // row_ror, lane_read, wave_lds_fence
 
 // Occupancy target of the half-sweep (waves per SIMD; caps VGPRs at 168 for
 // 3) and the pipeline chunk (steps of 4 ratings) per accumulation mode.
@@ -166,35 +166,9 @@ __device__ unsigned long long g_als_stamps[8];
 #define STAMP_DECL
 #endif
 
-// x of lane (l & 48) | ((l + 16 - N) & 15): a rotation inside each 16-lane
-// row (DPP row_ror:N on both halves of the double).
-template <int N>
-__device__ __forceinline__ double row_ror(double x) {
-  const long long v = __double_as_longlong(x);
-  const int lo = __builtin_amdgcn_mov_dpp((int)v, 0x120 + N, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_mov_dpp((int)(v >> 32), 0x120 + N, 0xf, 0xf, false);
-  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-}
-
-// Wave-uniform broadcast of lane `src`'s double (two v_readlane_b32).
-__device__ __forceinline__ double bcast(double v, int src) {
-  const long long x = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)x, src);
-  const int hi = __builtin_amdgcn_readlane((int)(x >> 32), src);
-  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-}
-
 // v_writelane_b32: `old` with lane `lane` replaced by the wave-uniform `src`
 // (this compiler has no builtin for it; declared like the buffer loads of common.h).
 __device__ int writelane_i32(int src, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
-
-// Orders this wave's LDS accesses around a point (one wave owns each LDS
-// slice; a wave's LDS operations complete in issue order).
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Per-wave LDS slice of the half-sweep (doubles).
 template <int KP>
@@ -258,7 +232,7 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
       for (int rr = 0; rr < 4; ++rr) acc[p][rr] = (sub + 4 * rr == col) ? 1.0 + reg * (double)n : 0.0;
     if constexpr (kAcq) bsh = acquire() + RowLds<KP>::kUpPad + 128 + 2 * KP;
     if (lane < KP) bsh[lane] = 1.0;
-    wave_lds_sync();
+    wave_lds_fence();
     return;
   }
   f4 fa[NPAIR];
@@ -511,10 +485,10 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
         stage[r * 16 + c] = dg[I][sh];
         stage[c * 16 + r] = dg[I][sh];
       }
-      wave_lds_sync();
+      wave_lds_fence();
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) acc[p][rr] = stage[(sub + 4 * rr) * 16 + col];
-      wave_lds_sync();
+      wave_lds_fence();
     }
   }
   } else {
@@ -615,10 +589,10 @@ __device__ __forceinline__ void gram_row(int64_t beg, int64_t end, int lane, con
     for (int p = 0; p < NPAIR; ++p) {
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) stage[(4 * sub + rr) * 16 + col] = acc[p][rr];
-      wave_lds_sync();
+      wave_lds_fence();
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) acc[p][rr] = stage[(sub + 4 * rr) * 16 + col];
-      wave_lds_sync();
+      wave_lds_fence();
     }
   }
   STAMP(2);  // phase 2: b + layout
@@ -679,7 +653,7 @@ __device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1
     double sum = 0.0;
 #pragma unroll
     for (int p = 0; p < NPAIR; ++p) sum += acc[p][0] + acc[p][1] + acc[p][2] + acc[p][3];
-    wave_lds_sync();
+    wave_lds_fence();
     if (lane < KP) out[lane] = (float)(sum + bsh[lane]);
     return;
   }
@@ -715,7 +689,7 @@ __device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1
           }
         }
       }
-      wave_lds_sync();
+      wave_lds_fence();
     }
     if (J == 0) bs = incol ? bsh[lane] : 0.0;
     // (b) lane c >= 16J owns column c of block row J
@@ -733,7 +707,7 @@ __device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1
     //     pivot is formed on its own lane ahead of that round trip (its update
     //     needs only the lane's own entries), so the per-pivot critical path is
     //     rcp -> Newton -> scale -> fma -> readlane.
-    double piv = bcast(a[0], 16 * J);
+    double piv = lane_read(a[0], 16 * J);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int pv = 16 * J + i;
@@ -751,12 +725,12 @@ __device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1
         dcap = __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
       }
       {
-        const double wq = bcast(bs, pv);
+        const double wq = lane_read(bs, pv);
         if (own && c > pv) bs = fma(-ut, wq, bs);
       }
       if (i < 15) {
-        piv = bcast(fma(-a[i], ut, a[i + 1]), pv + 1);
-        wave_lds_sync();
+        piv = lane_read(fma(-a[i], ut, a[i + 1]), pv + 1);
+        wave_lds_fence();
 #pragma unroll
         for (int m0 = (i + 1) & ~1; m0 < 16; m0 += 2) {
           const double2 u = *reinterpret_cast<const double2*>(cb + 16 * J + m0);
@@ -766,7 +740,7 @@ __device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1
       }
     }
     if (own) dsh[c] = dcap;  // lanes of later panels: 0.0, replaced after their own panel
-    wave_lds_sync();
+    wave_lds_fence();
     // (e) Ut_JK (K > J) back into tile registers, with a D_J-scaled copy;
     // (f) trailing update A_KM -= Ut_JK^T D_J Ut_JM on the f64 matrix cores
     if (J + 1 < NT) {
@@ -809,7 +783,7 @@ __device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1
           }
         }
       }
-      if constexpr (LDSG) wave_lds_sync();  // the next panel reads what other lanes stored
+      if constexpr (LDSG) wave_lds_fence();  // the next panel reads what other lanes stored
     }
   }
   STAMP(3);  // phase 3: factorisation
@@ -826,12 +800,12 @@ __device__ __forceinline__ void factor_row_impl(int lane, d4 (&acc)[NT * (NT + 1
 #pragma unroll HREC_ALS_SOLVE_UNROLL
   for (int q = KP - 1; q >= 0; --q) {
     const double u = Up[tri(q) + (incol ? lane : 0)];  // Ut[lane][q] for lane < q
-    const double xq = bcast(bi, q);
+    const double xq = lane_read(bi, q);
     if (lane < q) bi = fma(-u, xq, bi);
   }
   STAMP(4);  // phase 4: triangular solves
   if (incol) out[NT * (lane & 15) + (lane >> 4)] = (float)bi;
-  wave_lds_sync();  // the next row on this wave reuses the LDS slice
+  wave_lds_fence();  // the next row on this wave reuses the LDS slice
 }
 
 template <int NT>

@@ -36,7 +36,7 @@
 // 16 x 16 triangle; owners of (J, K) subtract U_JK^T w_J from b_K), v = w / D,
 // then U x = v from the last block up (owners of (J, M) subtract U_JM x_M
 // from v_J). Spark's dppsv factors A = R^T R with R = D^(1/2) U: the same x.
-#include "common.h"
+#include "wave.h"  // lane_read, dpp64, wave_lds_fence
 
 #ifndef HREC_WIDE_WAVES
 #define HREC_WIDE_WAVES(NT) 8
@@ -110,28 +110,6 @@ __device__ __forceinline__ void pair_ij(int p, int& I, int& J) {
   }
   I = i;
   J = i + p;
-}
-
-__device__ __forceinline__ double wbcast(double v, int src) {
-  const long long x = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)x, src);
-  const int hi = __builtin_amdgcn_readlane((int)(x >> 32), src);
-  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-}
-
-// A double moved across lanes by one DPP pattern (two 32-bit v_mov_dpp).
-template <int CTRL>
-__device__ __forceinline__ double dpp64(double x) {
-  const long long v = __double_as_longlong(x);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(v >> 32), CTRL, 0xf, 0xf, false);
-  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-}
-
-__device__ __forceinline__ void wave_sync_lds() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // Backward substitution: the wave that runs block M's chain also applies its
@@ -271,7 +249,7 @@ __global__ __launch_bounds__(WideShape<NT>::THREADS) void als_half_sweep_wide_ke
     int ix[S::F4_PER_T], iu[S::F4_PER_T];
     load_idx(win, ix);
 #pragma unroll
-    for (int q = 0; q < S::F4_PER_T; ++q) iu[q] = kUniRow ? __builtin_amdgcn_readlane(ix[0], q) : ix[q];
+    for (int q = 0; q < S::F4_PER_T; ++q) iu[q] = kUniRow ? lane_read(ix[0], q) : ix[q];
     load_rows(win, iu);
   };
   auto store_window = [&](int b) {
@@ -310,7 +288,7 @@ __global__ __launch_bounds__(WideShape<NT>::THREADS) void als_half_sweep_wide_ke
       // would wait for it)
       int ixc[S::F4_PER_T];
 #pragma unroll
-      for (int q = 0; q < S::F4_PER_T; ++q) ixc[q] = kUniRow ? __builtin_amdgcn_readlane(ixn[0], q) : ixn[q];
+      for (int q = 0; q < S::F4_PER_T; ++q) ixc[q] = kUniRow ? lane_read(ixn[0], q) : ixn[q];
       if (win + 2 < nwin) load_idx(win + 2, ixn);
       load_rows(win + 1, ixc);
     }
@@ -411,13 +389,13 @@ __global__ __launch_bounds__(WideShape<NT>::THREADS) void als_half_sweep_wide_ke
 #pragma unroll
       for (int m = 0; m < 16; ++m) a[m] = pc[m * LD];
       if (lane < 32) tri[w][16 + lane + 16 * (lane >> 4)] = 0.0;  // entries 16..31 of both buffers
-      wave_sync_lds();
+      wave_lds_fence();
 #pragma unroll 1
       for (int i = 0; i < 16; ++i) {
         // a[] is kept shifted: a[0] is always the column's row 16 J + i, so
         // the rolled loop indexes registers at compile time only
         const double ai = a[0];
-        const double piv = wbcast(ai, i);  // lane i: column 16 J + i, row 16 J + i
+        const double piv = lane_read(ai, i);  // lane i: column 16 J + i, row 16 J + i
         const double r0 = __builtin_amdgcn_rcp(piv);
         const double rp = fma(r0, fma(-piv, r0, 1.0), r0);
         const double ut = ai * rp;  // U[16 J + i][c]
@@ -431,7 +409,7 @@ __global__ __launch_bounds__(WideShape<NT>::THREADS) void als_half_sweep_wide_ke
           dsh[16 * J + i] = piv;
           rdsh[16 * J + i] = rp;
         }
-        wave_sync_lds();
+        wave_lds_fence();
         double u[15];
 #pragma unroll
         for (int j = 0; j < 15; ++j) u[j] = cbw[i + 1 + j];
@@ -442,14 +420,14 @@ __global__ __launch_bounds__(WideShape<NT>::THREADS) void als_half_sweep_wide_ke
       // earlier block already subtracted its part) by wave 0, which has just
       // written U_JJ to udg; v_J = w_J / D
       if (w == 0) {
-        wave_sync_lds();
+        wave_lds_fence();
         double tc[16];  // column `lane` of U_JJ
 #pragma unroll
         for (int q = 0; q < 16; ++q) tc[q] = udg[q * 17 + col];
         double bi = lane < 16 ? bsh[16 * J + lane] : 0.0;
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const double wq = wbcast(bi, q);
+          const double wq = lane_read(bi, q);
           if (lane > q && lane < 16) bi = fma(-tc[q], wq, bi);
         }
         if (lane < 16) {
@@ -599,7 +577,7 @@ __global__ __launch_bounds__(WideShape<NT>::THREADS) void als_half_sweep_wide_ke
       }
 #pragma unroll
       for (int q = 15; q >= 0; --q) {
-        const double xq = wbcast(bi, q);
+        const double xq = lane_read(bi, q);
         if (lane < q) bi = fma(-tr[q], xq, bi);
       }
       if (lane < 16) xsh[16 * M + lane] = bi;

@@ -43,7 +43,7 @@ constexpr int kColdK = 3;       // _find_similar_items' k
 // |f| of a feature row as sklearn's normalize takes it (sequential non-FMA
 // f64 chain; callers keep contraction off): a norm below 10 * eps (2.2e-15,
 // an exact zero included) is replaced by 1, as _handle_zeros_in_scale does —
-// the rule of mm_range (hybrid_common.h) for the fusion's ranges.
+// the rule of mm_range (csrc/hybrid_common.h) for the fusion's ranges.
 __device__ __forceinline__ double cos_row_norm(const double* __restrict__ f, int dim) {
 #pragma clang fp contract(off)
   double nr = 0.0;

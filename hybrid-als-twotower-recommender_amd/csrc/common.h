@@ -19,12 +19,6 @@ int check_launch(const char* what);
 
 constexpr int kWave = 64;
 
-// The lanes below this one that are set in a __ballot mask: a lane's rank
-// among the lanes that voted yes.
-__device__ __forceinline__ int lanes_below(uint64_t mask) {
-  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
 // Leading dimensions of factor matrices: 16/32/64 (one wave per row in the
 // half-sweep) and 96/128/192/256 (one workgroup per row, csrc/als_wide.hip).
 inline bool hrec_factor_ld_ok(int kp) {

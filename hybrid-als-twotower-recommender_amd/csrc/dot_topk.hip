@@ -28,7 +28,7 @@
 #include <type_traits>
 
 #include "cascade.h"
-#include "hybrid_common.h"
+#include "order.h"  // bf16_rne
 
 namespace hrec {
 

@@ -260,9 +260,7 @@ __device__ __forceinline__ void fuse_segment_one(
     const int mpos = nmine > 0 ? be * 64 + lane : -1;
     ck[64 + lane] = bk;
     ce[64 + lane] = mpos;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_fence();
     int rank = 0;
 #pragma unroll 8
     for (int q = 0; q < 64; ++q) {
@@ -275,13 +273,10 @@ __device__ __forceinline__ void fuse_segment_one(
     const uint64_t hit = __ballot(mpos >= 0 && rank == target);
     if (hit) {
       const int src = __builtin_ctzll(hit);
-      t.k = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(bk >> 32), src) << 32) |
-            (uint32_t)__builtin_amdgcn_readlane((int)bk, src);
-      t.i = seg0 + __builtin_amdgcn_readlane(mpos, src);
+      t.k = lane_read(bk, src);
+      t.i = seg0 + lane_read(mpos, src);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_fence();
   }
   // 2. candidates: items not worse than t (no t: fewer than kk items, take all)
   int nc = 0;
@@ -305,9 +300,7 @@ __device__ __forceinline__ void fuse_segment_one(
   }
   const int64_t obase = r * segs * KK + seg * KK;
   if (!overflow) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_fence();
     // each candidate's rank among the nc candidates = its output slot
     const uint64_t mk = lane < nc ? ck[lane] : 0;
     const int mp = lane < nc ? ce[lane] : 0;
@@ -429,9 +422,7 @@ __global__ __launch_bounds__(256) void fuse_filter_kernel(
     if (lane == 0) *overflow = 1;
     return;
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_fence();
   // each candidate's rank among the nc (key desc, position asc) = its slot
   const uint64_t mk = lane < nc ? ck_sh[wv][lane] : 0;
   const int mp = lane < nc ? ce_sh[wv][lane] : 0;

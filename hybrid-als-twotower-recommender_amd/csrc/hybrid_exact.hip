@@ -46,7 +46,6 @@
 //   Users with non-finite or huge norms, too many live groups or candidates,
 //   or whose kk best include a NaN or fewer than kk items, rescore every
 //   group in 2c (the order of NaN items is by item id over the whole shard).
-#include "common.h"
 #include "hybrid_common.h"
 
 namespace hrec {
@@ -91,16 +90,6 @@ struct HxShape {
   static constexpr int kBlocksPerCU = UB == 256 ? 1 : 2;
 };
 
-__device__ __forceinline__ float hx_up(double x) {  // the smallest float >= x
-  float f = (float)x;
-  if ((double)f < x) f = nextafterf(f, INFINITY);
-  return f;
-}
-__device__ __forceinline__ float hx_down(double x) {  // the largest float <= x
-  float f = (float)x;
-  if ((double)f > x) f = nextafterf(f, -INFINITY);
-  return f;
-}
 __device__ __forceinline__ float hx_u2f(uint32_t u) { return __uint_as_float(u); }
 
 // Split bf16 of x: hi = bf16(x), lo = bf16(x - hi) (x - hi is exact in f32).
@@ -172,12 +161,8 @@ __global__ __launch_bounds__(256) void hx_prepare_kernel(const float* __restrict
     }
   }
   const double nrm = sqrt(ss) * (1.0 + 1e-6);
-  unsigned f = __float_as_uint((bad || !(nrm < kHxHuge)) ? INFINITY : hx_up(nrm));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned o = (unsigned)__shfl_xor((int)f, off, kWave);
-    f = o > f ? o : f;  // non-negative floats order as their bits
-  }
+  unsigned f = __float_as_uint((bad || !(nrm < kHxHuge)) ? INFINITY : f32_up(nrm));
+  f = wave_xor_max(f);  // non-negative floats order as their bits
   if ((threadIdx.x & 63) == 0) atomicMax(&norms[m], f);
 }
 
@@ -316,8 +301,8 @@ __global__ __launch_bounds__(HxShape<DK>::kThreads, DK == 64 ? HxShape<DK>::kBlo
       }
       // the two lane halves hold the two halves of the group: one
       // v_permlane32_swap per register pair folds them for both models
-      const auto X = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx[0]), __float_as_uint(mx[1]), false, false);
-      const auto Y = __builtin_amdgcn_permlane32_swap(__float_as_uint(mn[0]), __float_as_uint(mn[1]), false, false);
+      const lane_u2 X = half_swap(mx[0], mx[1]);
+      const lane_u2 Y = half_swap(mn[0], mn[1]);
       const float hi = fmaxf(hx_u2f(X[0]), hx_u2f(X[1]));  // lanes < 32: ALS, lanes >= 32: two-tower
       const float lo = fminf(hx_u2f(Y[0]), hx_u2f(Y[1]));
       const int b = b0 + 32 * ch + c;
@@ -525,18 +510,18 @@ struct HxWave {
 // fminf / fmaxf over the block (512 threads), 4 values
 __device__ __forceinline__ void hx_block_minmax(float& lo_a, float& hi_a, float& lo_t, float& hi_t,
                                                 float (*sred)[4], int lane, int wv) {
-  lo_a = fminf(lo_a, hp_dpp32<0xB1>(lo_a)), hi_a = fmaxf(hi_a, hp_dpp32<0xB1>(hi_a));
-  lo_t = fminf(lo_t, hp_dpp32<0xB1>(lo_t)), hi_t = fmaxf(hi_t, hp_dpp32<0xB1>(hi_t));
-  lo_a = fminf(lo_a, hp_dpp32<0x4E>(lo_a)), hi_a = fmaxf(hi_a, hp_dpp32<0x4E>(hi_a));
-  lo_t = fminf(lo_t, hp_dpp32<0x4E>(lo_t)), hi_t = fmaxf(hi_t, hp_dpp32<0x4E>(hi_t));
-  lo_a = fminf(lo_a, hp_dpp32<0x141>(lo_a)), hi_a = fmaxf(hi_a, hp_dpp32<0x141>(hi_a));
-  lo_t = fminf(lo_t, hp_dpp32<0x141>(lo_t)), hi_t = fmaxf(hi_t, hp_dpp32<0x141>(hi_t));
-  lo_a = fminf(lo_a, hp_dpp32<0x140>(lo_a)), hi_a = fmaxf(hi_a, hp_dpp32<0x140>(hi_a));
-  lo_t = fminf(lo_t, hp_dpp32<0x140>(lo_t)), hi_t = fmaxf(hi_t, hp_dpp32<0x140>(hi_t));
-  lo_a = fminf(lo_a, hp_xor16(lo_a)), hi_a = fmaxf(hi_a, hp_xor16(hi_a));
-  lo_t = fminf(lo_t, hp_xor16(lo_t)), hi_t = fmaxf(hi_t, hp_xor16(hi_t));
-  lo_a = fminf(lo_a, hp_xor32(lo_a)), hi_a = fmaxf(hi_a, hp_xor32(hi_a));
-  lo_t = fminf(lo_t, hp_xor32(lo_t)), hi_t = fmaxf(hi_t, hp_xor32(hi_t));
+  lo_a = fminf(lo_a, dpp32<0xB1>(lo_a)), hi_a = fmaxf(hi_a, dpp32<0xB1>(hi_a));
+  lo_t = fminf(lo_t, dpp32<0xB1>(lo_t)), hi_t = fmaxf(hi_t, dpp32<0xB1>(hi_t));
+  lo_a = fminf(lo_a, dpp32<0x4E>(lo_a)), hi_a = fmaxf(hi_a, dpp32<0x4E>(hi_a));
+  lo_t = fminf(lo_t, dpp32<0x4E>(lo_t)), hi_t = fmaxf(hi_t, dpp32<0x4E>(hi_t));
+  lo_a = fminf(lo_a, dpp32<0x141>(lo_a)), hi_a = fmaxf(hi_a, dpp32<0x141>(hi_a));
+  lo_t = fminf(lo_t, dpp32<0x141>(lo_t)), hi_t = fmaxf(hi_t, dpp32<0x141>(hi_t));
+  lo_a = fminf(lo_a, dpp32<0x140>(lo_a)), hi_a = fmaxf(hi_a, dpp32<0x140>(hi_a));
+  lo_t = fminf(lo_t, dpp32<0x140>(lo_t)), hi_t = fmaxf(hi_t, dpp32<0x140>(hi_t));
+  lo_a = fminf(lo_a, xor16(lo_a)), hi_a = fmaxf(hi_a, xor16(hi_a));
+  lo_t = fminf(lo_t, xor16(lo_t)), hi_t = fmaxf(hi_t, xor16(hi_t));
+  lo_a = fminf(lo_a, xor32(lo_a)), hi_a = fmaxf(hi_a, xor32(hi_a));
+  lo_t = fminf(lo_t, xor32(lo_t)), hi_t = fmaxf(hi_t, xor32(hi_t));
   __syncthreads();  // sred's previous readers are done
   if (lane == 0) sred[wv][0] = lo_a, sred[wv][1] = hi_a, sred[wv][2] = lo_t, sred[wv][3] = hi_t;
   __syncthreads();
@@ -572,21 +557,19 @@ __device__ int hx_merge(HpList<KK>& L, bool from_lists, HxMergeLds& M, double* r
     for (int e = 0; e < KK; ++e) wn += __popcll(__ballot(L.i[e] != INT64_MAX));
     if (wn > 8) {  // wave-uniform
       L.wave_top(kk, lane, rv + wv * KK, ri + wv * KK);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // lane 0's LDS writes -> the wave's reads
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_fence();  // lane 0's LDS writes -> the wave's reads
       if (lane < kk && ri[wv * KK + lane] != INT64_MAX) {
         const int p = atomicAdd(&M.n, 1);
         const double v = rv[wv * KK + lane];
         const int64_t i = ri[wv * KK + lane];
-        M.mk[p] = hp_order_key(v, i), M.mi[p] = i, M.mv[p] = v;
+        M.mk[p] = slot_order_key(v, i), M.mi[p] = i, M.mv[p] = v;
       }
     } else {
 #pragma unroll
       for (int e = 0; e < KK; ++e) {
         if (L.i[e] != INT64_MAX) {
           const int p = atomicAdd(&M.n, 1);
-          M.mk[p] = hp_order_key(L.v[e], L.i[e]), M.mi[p] = L.i[e], M.mv[p] = L.v[e];
+          M.mk[p] = slot_order_key(L.v[e], L.i[e]), M.mi[p] = L.i[e], M.mv[p] = L.v[e];
         }
       }
     }
@@ -745,7 +728,7 @@ __global__ __launch_bounds__(kHxThreads2) void hx_pre_kernel(HxArgs a) {
     int64_t bg = INT64_MAX;
     for (int g = 64 * wv + lane; g < G; g += 64 * 8) {
       const float4 x = st_row[g];
-      const double u = hp_fuse(sc0, hx_up((double)x.x + Ea), hx_up((double)x.z + Et), w0, w1);
+      const double u = hp_fuse(sc0, f32_up((double)x.x + Ea), f32_up((double)x.z + Et), w0, w1);
       if (bg == INT64_MAX || better(u, g, bu, bg)) {
         bu = u;
         bg = g;
@@ -793,10 +776,10 @@ __global__ __launch_bounds__(kHxThreads2) void hx_pre_kernel(HxArgs a) {
     // a. the groups that can hold an exact extreme
     const bool all_a = rok && bad_a, all_t = bad_t;
     const bool use_a = rok && !bad_a && AMX >= AMN, use_t = !bad_t && TMX >= TMN;
-    const float a_hi = use_a ? hx_down((double)AMX - 2.0 * Ea) : INFINITY;
-    const float a_lo = use_a ? hx_up((double)AMN + 2.0 * Ea) : -INFINITY;
-    const float t_hi = use_t ? hx_down((double)TMX - 2.0 * Et) : INFINITY;
-    const float t_lo = use_t ? hx_up((double)TMN + 2.0 * Et) : -INFINITY;
+    const float a_hi = use_a ? f32_down((double)AMX - 2.0 * Ea) : INFINITY;
+    const float a_lo = use_a ? f32_up((double)AMN + 2.0 * Ea) : -INFINITY;
+    const float t_hi = use_t ? f32_down((double)TMX - 2.0 * Et) : INFINITY;
+    const float t_lo = use_t ? f32_up((double)TMN + 2.0 * Et) : -INFINITY;
     const bool every = all_a || all_t;
     if (every && tid == 0) *a.flag = 1;
     auto pred = [&](int g) {
@@ -816,12 +799,12 @@ __global__ __launch_bounds__(kHxThreads2) void hx_pre_kernel(HxArgs a) {
       W.scan(j, ok, sa, tf);
       if (ok) lo_a = fminf(lo_a, sa), hi_a = fmaxf(hi_a, sa);
       float pm = ok ? tf : -INFINITY, pn = ok ? tf : INFINITY;
-      pm = fmaxf(pm, hp_dpp32<0xB1>(pm)), pn = fminf(pn, hp_dpp32<0xB1>(pn));
-      pm = fmaxf(pm, hp_dpp32<0x4E>(pm)), pn = fminf(pn, hp_dpp32<0x4E>(pn));
-      pm = fmaxf(pm, hp_dpp32<0x141>(pm)), pn = fminf(pn, hp_dpp32<0x141>(pn));
-      pm = fmaxf(pm, hp_dpp32<0x140>(pm)), pn = fminf(pn, hp_dpp32<0x140>(pn));
-      pm = fmaxf(pm, hp_xor16(pm)), pn = fminf(pn, hp_xor16(pn));
-      pm = fmaxf(pm, hp_xor32(pm)), pn = fminf(pn, hp_xor32(pn));
+      pm = fmaxf(pm, dpp32<0xB1>(pm)), pn = fminf(pn, dpp32<0xB1>(pn));
+      pm = fmaxf(pm, dpp32<0x4E>(pm)), pn = fminf(pn, dpp32<0x4E>(pn));
+      pm = fmaxf(pm, dpp32<0x141>(pm)), pn = fminf(pn, dpp32<0x141>(pn));
+      pm = fmaxf(pm, dpp32<0x140>(pm)), pn = fminf(pn, dpp32<0x140>(pn));
+      pm = fmaxf(pm, xor16(pm)), pn = fminf(pn, xor16(pn));
+      pm = fmaxf(pm, xor32(pm)), pn = fminf(pn, xor32(pn));
       const bool cand = ok && (every || (double)tf + Ef >= (double)pm - Ef || (double)tf - Ef <= (double)pn + Ef ||
                                tf != tf);
       W.exact_rounds(__ballot(cand), j, sa, [&](int64_t, float, float tx, int) {
@@ -895,14 +878,14 @@ __global__ __launch_bounds__(kHxThreads2) void hx_pre_kernel(HxArgs a) {
   }
   auto ub_of = [&](int g) {
     const float4 x = st_row[g];
-    return hp_fuse(sc, hx_up((double)x.x + Ea), hx_up((double)x.z + Et), w0, w1);
+    return hp_fuse(sc, f32_up((double)x.x + Ea), f32_up((double)x.z + Et), w0, w1);
   };
   // tau: a seed's fused score is bounded below by its exact ALS score and its
   // fma chain - Ef, so the kk-th best of those bounds (distinct items) is a
   // lower bound of the shard's kk-th best fused score
   HpList<KK> L;
   L.reset();
-  if (s_ok) L.insert(hp_fuse(sc, s_sa, hx_down((double)s_tf - Ef), w0, w1), s_j);
+  if (s_ok) L.insert(hp_fuse(sc, s_sa, f32_down((double)s_tf - Ef), w0, w1), s_j);
   const int seed_bad = hx_merge<KK>(L, true, M, rv, ri, kk, lane, wv, tid, b, 0, nullptr, nullptr);
   const double tau = seed_bad ? -INFINITY : M.tau;  // -inf: fewer than kk numeric seeds (every group qualifies)
   HX_STAMP(3);
@@ -1021,7 +1004,7 @@ __global__ __launch_bounds__(256) void hx_pairs_kernel(HxArgs a) {
     const bool ok = W.item_of(e.y, e.z, j);
     float sa, tf;
     W.scan(j, ok, sa, tf);
-    const bool pass = ok && hp_fuse(sc, sa, hx_up((double)tf + r.Ef), a.w0, a.w1) >= r.tau;
+    const bool pass = ok && hp_fuse(sc, sa, f32_up((double)tf + r.Ef), a.w0, a.w1) >= r.tau;
     const uint64_t m = __ballot(pass);
     const int n = __popcll(m);
     double* pv = a.cv + (int64_t)p * kHxSlots;

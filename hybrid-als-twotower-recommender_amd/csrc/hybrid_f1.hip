@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void hf_finish_kernel(const int64_t* __restric
       if (out_top) out_top[(row * 2 + m) * kk + p] = c;
       tp[m] += (c >= 0 && excl_contains(label_cols, x.lo, x.hi, c)) ? 1 : 0;
     }
-#pragma unroll
+#pragma unroll  // written out: wave_xor_sum here changes the generated code
     for (int off = 32; off > 0; off >>= 1) tp[m] += __shfl_xor(tp[m], off, kWave);
   }
   if (lane != 0) return;

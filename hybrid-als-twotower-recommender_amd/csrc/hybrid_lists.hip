@@ -12,7 +12,7 @@
 //      topk_rows ranks the lists by (value, column);
 //   3. mode 1: hl_pass_kernel<1> writes every fused value and its column (-1
 //      where excluded) and topk_rows ranks the whole rows.
-// Keys are hp_order_key's: 0 = excluded / empty, 1 = NaN, numbers above.
+// Keys are slot_order_key's: 0 = excluded / empty, 1 = NaN, numbers above.
 // hrec_hybrid_lists_rowwise is the same body with the fusion weights chosen
 // per row (row_wins, hrec_hybrid_model_f1's output) instead of per call.
 #include "exclusion.h"
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(kHlBoundBlock) void hl_bound_kernel(
     int c = 0;
 #pragma unroll
     for (int e = 0; e < kHlBoundPer; ++e) c += key[e] >= cand ? 1 : 0;
-#pragma unroll
+#pragma unroll  // written out: wave_xor_sum here changes the generated code
     for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, kWave);
     if ((tid & 63) == 0) atomicAdd(&cn[b], c);
     __syncthreads();
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256) void hl_pass_kernel(
   const int nvalid = (int)((n - seg0) < kHlSeg ? (n - seg0) : kHlSeg);
   uint32_t* bm = bm_sh[wv];
   if (lane < kHlSeg / 32) bm[lane] = 0;
-  hl_wave_sync();
+  wave_lds_fence();
   const ExclSeg x = excl_segment(excl_rows, excl_indptr, r);
   if (x.lo < x.hi) {
     // from the first column >= seg0; columns past the segment (or past n) end the walk unused
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void hl_pass_kernel(
                      if (c >= seg0) atomicOr(&bm[(c - seg0) >> 5], 1u << ((c - seg0) & 31));
                    });
   }
-  hl_wave_sync();
+  wave_lds_fence();
   const HpScale sc = coef[r];
   const auto [w0, w1] = hl_weights(row_wins, als_wins, r);
   const uint64_t tk = (MODE == 0 && bound) ? bound[r] : 0ull;

@@ -38,7 +38,6 @@
 #include <float.h>
 #include <math.h>
 
-#include "common.h"
 #include "hybrid_common.h"
 
 namespace hrec {
@@ -79,12 +78,6 @@ __device__ unsigned long long g_hp_stamps[2][kHpStampBlocks][8];
 #define HP_STAMP(i)
 #define HP_STAMP_OUT(kid)
 #endif
-
-__device__ __forceinline__ void wave_sync_lds() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // 1. bf16 user operands [2][B][dk]: the ALS rows gathered by als_rows (a row
 // outside [0, n_als_rows) reads as NaN, as hyb_scores_kernel stages it) and
@@ -220,18 +213,18 @@ __global__ __launch_bounds__(256) void hp_bound_kernel(const float* __restrict__
     }
     // wave min / max without LDS permutes: DPP within rows (quad swaps, half-
     // row and row mirrors), then the row / half swaps of gfx950
-    lo = fminf(lo, hp_dpp32<0xB1>(lo));
-    hi = fmaxf(hi, hp_dpp32<0xB1>(hi));
-    lo = fminf(lo, hp_dpp32<0x4E>(lo));
-    hi = fmaxf(hi, hp_dpp32<0x4E>(hi));
-    lo = fminf(lo, hp_dpp32<0x141>(lo));
-    hi = fmaxf(hi, hp_dpp32<0x141>(hi));
-    lo = fminf(lo, hp_dpp32<0x140>(lo));
-    hi = fmaxf(hi, hp_dpp32<0x140>(hi));
-    lo = fminf(lo, hp_xor16(lo));
-    hi = fmaxf(hi, hp_xor16(hi));
-    lo = fminf(lo, hp_xor32(lo));
-    hi = fmaxf(hi, hp_xor32(hi));
+    lo = fminf(lo, dpp32<0xB1>(lo));
+    hi = fmaxf(hi, dpp32<0xB1>(hi));
+    lo = fminf(lo, dpp32<0x4E>(lo));
+    hi = fmaxf(hi, dpp32<0x4E>(hi));
+    lo = fminf(lo, dpp32<0x141>(lo));
+    hi = fmaxf(hi, dpp32<0x141>(hi));
+    lo = fminf(lo, dpp32<0x140>(lo));
+    hi = fmaxf(hi, dpp32<0x140>(hi));
+    lo = fminf(lo, xor16(lo));
+    hi = fmaxf(hi, xor16(hi));
+    lo = fminf(lo, xor32(lo));
+    hi = fmaxf(hi, xor32(hi));
     if (lane == 0) {
       red[wv][0] = lo;
       red[wv][1] = hi;
@@ -377,15 +370,13 @@ __global__ __launch_bounds__(256) void hp_bound_kernel(const float* __restrict__
         const double hn = (tau - w1 * (double)tn_max) / w0 - 1e-9;
         double x = (hn - sc.amin_) / sc.ascale;
         x -= 1e-6 * (fabs(x) + ((double)amax - (double)amin));
-        th = (float)x;
-        if ((double)th > x) th = nextafterf(th, -INFINITY);
+        th = f32_down(x);
       } else {  // heavy = two-tower (w1): t_n >= (tau - w0 a_n) / w1
         const double an_max = (double)lmx * sc.ascale + sc.amin_;
         const double hn = (tau - w0 * an_max) / w1 - 1e-9;
         double x = (hn - (double)sc.tmin_) / (double)sc.tscale;
         x -= 1e-6 * (fabs(x) + ((double)tmax - (double)tmin));
-        th = (float)x;
-        if ((double)th > x) th = nextafterf(th, -INFINITY);
+        th = f32_down(x);
       }
     }
     // the group's heavy maximum is below its bound: nothing of it survives

@@ -16,7 +16,7 @@
 // (id, position) otherwise); coo_to_csr: a hand-written stable LSD radix sort
 // of the dense row codes (below); plus O(n) integer passes. HBM-bound.
 
-#include "common.h"
+#include "wave.h"  // wave_lds_fence
 
 namespace hrec {
 
@@ -412,6 +412,7 @@ __device__ __forceinline__ unsigned long long umin64(unsigned long long a, unsig
 
 // block-wide min over kMinThreads values; every thread gets the result
 __device__ __forceinline__ unsigned long long block_min64(unsigned long long m, unsigned long long* sh) {
+  // written out: wave_xor_min (csrc/wave.h) here changes the generated code
   for (int off = 32; off >= 1; off >>= 1) m = umin64(m, __shfl_xor(m, off, 64));
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   __syncthreads();
@@ -746,13 +747,9 @@ __global__ __launch_bounds__(kSortThreads) void sort_downsweep_kernel(
       const int rank = __popcll(peers & lt);
       const uint32_t before = active ? wh[w][dg] : 0;
       rk[r] = before + (uint32_t)rank;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_fence();
       if (active && rank == 0) wh[w][dg] = (uint16_t)(before + __popcll(peers));
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_fence();
     }
     __syncthreads();
     // 2. offsets in the tile's digit-sorted order: digits ascending, waves in

@@ -26,7 +26,7 @@
 // partial per slot, a second launch adds the partials in a fixed order onto
 // sums_out (no floating-point atomics): equal inputs give equal bits.
 #include "exclusion.h"
-#include "hybrid_common.h"
+#include "wave.h"  // wave_lds_fence, wave_xor_sum
 
 #pragma clang fp contract(off)
 
@@ -60,13 +60,6 @@ struct LqParams {
   int32_t* row_n;
   double* partials;
 };
-
-template <typename T>
-__device__ __forceinline__ T lq_wave_sum(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
 
 // The wave's 64 columns c (one per lane, -1: not an entry), in lane order:
 // acc[j] += x_(l + 64 j) of each, q += the lane's x * x [LIST]. An item with
@@ -149,10 +142,10 @@ __device__ __forceinline__ void lq_row(const LqParams& P, int64_t row, int lane,
   double ss = 0.0, sh = 0.0;
 #pragma unroll
   for (int j = 0; j < NJ; ++j) ss += S[j] * S[j], sh += S[j] * H[j];
-  ss = lq_wave_sum(ss), q = lq_wave_sum(q), sh = lq_wave_sum(sh);
-  m = lq_wave_sum(m), g = lq_wave_sum(g);
+  ss = wave_xor_sum(ss), q = wave_xor_sum(q), sh = wave_xor_sum(sh);
+  m = wave_xor_sum(m), g = wave_xor_sum(g);
 #pragma unroll
-  for (int t = 0; t < kLqMaxTab; ++t) ts[t] = lq_wave_sum(ts[t]), tc[t] = lq_wave_sum(tc[t]);
+  for (int t = 0; t < kLqMaxTab; ++t) ts[t] = wave_xor_sum(ts[t]), tc[t] = wave_xor_sum(tc[t]);
   if (lane != 0) return;
   const double nan = __builtin_nan("");
   double* pr = P.per_row + row * ncol;
@@ -181,7 +174,7 @@ __global__ __launch_bounds__(256) void lq_kernel(const LqParams P) {
   const int64_t row = (int64_t)blockIdx.x * 4 + w;
   const int nslots = 2 * (2 + P.n_tab);
   for (int i = lane; i < kLqMaxSlots; i += kWave) red[w][i] = 0.0;
-  hl_wave_sync();
+  wave_lds_fence();
   if (row < P.n_rows) lq_row<NJ>(P, row, lane, red[w]);  // wave-uniform
   __syncthreads();
   if ((int)threadIdx.x < nslots) {
@@ -197,7 +190,7 @@ __global__ __launch_bounds__(64) void lq_reduce_kernel(const double* __restrict_
   const int lane = threadIdx.x, i = blockIdx.x;
   double v = 0.0;
   for (int64_t b = lane; b < n_blocks; b += 64) v += partials[b * nslots + i];
-  v = lq_wave_sum(v);
+  v = wave_xor_sum(v);
   if (lane == 0) sums[i] = sums[i] + v;
 }
 
@@ -213,7 +206,7 @@ __global__ __launch_bounds__(256) void lq_inv_norm_kernel(const float* __restric
     const double x = (double)vectors[j * ld + c];
     s += x * x;
   }
-  s = lq_wave_sum(s);
+  s = wave_xor_sum(s);
   if (lane == 0) out[j] = (s > 0.0 && s - s == 0.0) ? 1.0 / sqrt(s) : 0.0;
 }
 

@@ -21,7 +21,7 @@
 // d | 1 dwords so that the lanes of a wave hit distinct banks) when they fit
 // kMmrStageBytes; otherwise every step re-reads them from global memory (a
 // pool is at most 1 MiB: it stays in L2).
-#include "hybrid_common.h"
+#include "common.h"
 
 #pragma clang fp contract(off)
 

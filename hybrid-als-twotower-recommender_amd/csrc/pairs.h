@@ -1,21 +1,15 @@
 // What the pair kernels (csrc/als_pairs.hip, csrc/tt_pairs.hip) share: the
-// launch shape, the row-index check, the wave-level LDS ordering and the
-// fixed-order reduction of the metrics partials.
+// launch shape, the row-index check and the fixed-order reduction of the
+// metrics partials (the wave-level LDS ordering is wave_lds_fence of wave.h).
 #pragma once
 
-#include "common.h"
+#include "wave.h"
 
 namespace hrec {
 
 constexpr int kPairBlock = 256;        // 4 waves, one tile of 64 pairs each per step
 constexpr int kPairMaxBlocks = 2048;   // grid cap: the tiles beyond are taken in grid strides
 constexpr int kPairBatch = 8;          // row fetches per side in flight per lane (at most)
-
-__device__ __forceinline__ void pair_wave_sync() {  // a wave's LDS operations complete in issue order
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Blocks of a launch over n pairs: a function of n alone, so the partial sums
 // of the metrics mode have one layout (and one summation order) per n.
@@ -38,8 +32,7 @@ static __global__ __launch_bounds__(64 * HREC_PAIR_SUMS) void pairs_reduce_kerne
   const int lane = threadIdx.x & 63, i = threadIdx.x >> 6;
   double v = 0.0;
   for (int64_t b = lane; b < n_blocks; b += 64) v += partials[b * HREC_PAIR_SUMS + i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+  v = wave_xor_sum(v);
   if (lane == 0) sums[i] = v;
 }
 

@@ -1,6 +1,6 @@
 // The position of every held-out item among all candidates
 // (hrec_rank_positions): for each label entry of a row, how many live columns
-// stand before it in the list order better() (csrc/hybrid_common.h) — the
+// stand before it in the list order better() (csrc/order.h) — the
 // 0-based position the item would have in a top-n list of length n — and from
 // those positions the row's AUC, reciprocal rank and percentile-rank sums.
 // include/hrec.h has the contract.
@@ -83,17 +83,11 @@ __device__ __forceinline__ bool rp_before(uint64_t ka, int32_t ca, uint64_t kb, 
   return ka > kb || (ka == kb && ca < cb);
 }
 
-// order_key for an f32 value, in 32 bits.
-__device__ __forceinline__ uint32_t rp_order_key32(float v) {
-  if (v != v) return 0;
-  const uint32_t b = __float_as_uint(v + 0.0f);  // -0 -> +0
-  return (b >> 31) ? ~b : (b | 0x80000000u);
-}
 // The packed key of the f32 source: the value's 32-bit key above the
 // complemented column, so one unsigned compare is the list order (a larger
 // key stands first) and equal keys are equal columns; above 0, the sentinel's.
 __device__ __forceinline__ uint64_t rp_packed_key(float v, int64_t c) {
-  return ((uint64_t)rp_order_key32(v) << 32) | (uint32_t)(0xffffffffu - (uint32_t)c);
+  return ((uint64_t)order_key32(v) << 32) | (uint32_t)(0xffffffffu - (uint32_t)c);
 }
 
 // The number of sorted entries e (of P, a power of two >= 2) with
@@ -115,29 +109,10 @@ __device__ __forceinline__ int rp_search(const RpLds& L, int P, uint64_t k, int3
   return pos + (pred(pos) ? 1 : 0);
 }
 
-__device__ __forceinline__ int64_t rp_wave_sum(int64_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-__device__ __forceinline__ double rp_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-__device__ __forceinline__ int64_t rp_wave_min(int64_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const int64_t o = __shfl_xor(v, off, kWave);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-
 // The block's sum of v in every thread (waves added in wave order).
 __device__ __forceinline__ int64_t rp_block_sum(RpLds& L, int64_t v) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  v = rp_wave_sum(v);
+  v = wave_xor_sum(v);
   __syncthreads();
   if (lane == 0) L.red_i[w][0] = v;
   __syncthreads();
@@ -354,9 +329,9 @@ __global__ __launch_bounds__(kRpBlock) void rp_kernel(const RpParams P) {
   }
 
   // the row's values: integers exactly, the doubles in a fixed tree
-  sum_rank = rp_wave_sum(sum_rank), h = rp_wave_sum(h), ranked = rp_wave_sum(ranked);
-  min_rank = rp_wave_min(min_rank);
-  sw = rp_wave_sum(sw), swpr = rp_wave_sum(swpr);
+  sum_rank = wave_xor_sum(sum_rank), h = wave_xor_sum(h), ranked = wave_xor_sum(ranked);
+  min_rank = wave_xor_min(min_rank);
+  sw = wave_xor_sum(sw), swpr = wave_xor_sum(swpr);
   __syncthreads();
   if (lane == 0) {
     L.red_i[w][0] = sum_rank, L.red_i[w][1] = h, L.red_i[w][2] = ranked, L.red_i[w][3] = min_rank;
@@ -411,7 +386,7 @@ __global__ __launch_bounds__(kRpBlock) void rp_partial_kernel(const double* __re
 #pragma unroll
   for (int s = 0; s < kRpSums; ++s) {
     double v = row < n_rows ? rp_slot(out_row + 4 * row, out_row_n + 3 * row, s) : 0.0;
-    v = rp_wave_sum(v);
+    v = wave_xor_sum(v);
     if (lane == 0) red[w][s] = v;
   }
   __syncthreads();
@@ -428,7 +403,7 @@ __global__ __launch_bounds__(64) void rp_reduce_kernel(const double* __restrict_
   const int lane = threadIdx.x, s = blockIdx.x;
   double v = 0.0;
   for (int64_t b = lane; b < n_blocks; b += 64) v += partials[b * kRpSums + s];
-  v = rp_wave_sum(v);
+  v = wave_xor_sum(v);
   if (lane == 0) sums[s] = v;
 }
 

@@ -3,8 +3,8 @@
 // steps both share csrc/cascade.hip, the generic stable top-k csrc/topk.hip,
 // the hybrid fusion (K9) csrc/fuse.hip.
 #include "cascade.h"
-#include "hybrid_common.h"
 #include "score.h"
+#include "wave.h"  // lanes_below
 
 namespace hrec {
 

@@ -21,10 +21,13 @@
 
 namespace hrec {
 
+// The same mapping as ~order_key((double)x) of csrc/order.h (which folds -0
+// by v + 0.0 where this compares with 0.0); written that way the sort's
+// generated code changes, so it stays in place.
 template <typename T>
 __device__ __forceinline__ uint64_t desc_key(T x) {
   const double v = (double)x;  // f32 -> f64 is exact and order-preserving
-  if (v != v) return ~0ull;    // NaN last (better() in hybrid_common.h)
+  if (v != v) return ~0ull;    // NaN last (better() in order.h)
   const uint64_t bits = (v == 0.0) ? 0ull : (uint64_t)__double_as_longlong(v);
   const uint64_t asc = (bits >> 63) ? ~bits : (bits | 0x8000000000000000ull);  // ascending-order key
   return ~asc;  // descending; never ~0 (asc == 0 would be a NaN pattern)

@@ -1,7 +1,7 @@
 // K10: synthetic interaction matrix (CSR / CSC shards) and ALS initial
 // factors, generated on the device from counter-based hashes so that any
 // shard layout (and the CPU oracle) sees bit-identical data.
-#include "common.h"
+#include "wave.h"  // lanes_below, wave_lds_fence, wave_xor_sum
 
 namespace hrec {
 
@@ -20,8 +20,7 @@ __global__ __launch_bounds__(256) void synth_count_kernel(uint64_t seed, uint64_
     const uint64_t h = transposed ? pair_hash(seed, (uint64_t)c, g) : pair_hash(seed, g, (uint64_t)c);
     cnt += (h < thr) ? 1u : 0u;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, kWave);
+  cnt = wave_xor_sum(cnt);
   if (lane == 0) counts[r] = (int64_t)cnt;
 }
 
@@ -79,8 +78,7 @@ __global__ __launch_bounds__(256) void init_factors_kernel(uint64_t seed, int64_
     }
     z_sh[w][c] = z[q];
   }
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  wave_lds_fence();
   double s = 0.0;
   for (int c = 0; c < k; ++c) {
     const double zc = (double)z_sh[w][c];

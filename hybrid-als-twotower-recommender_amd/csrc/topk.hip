@@ -1,8 +1,8 @@
 // Generic stable top-k (the reference's sorted(..., reverse=True)[:k]): kk
 // rounds of arg-best over segments held in registers, or one wave per row
-// with per-lane sorted lists; the order is better() of hybrid_common.h.
+// with per-lane sorted lists; the order is better() of order.h.
 // Larger top_k than kTopkSelectMax: the sort path (csrc/sort_topk.hip).
-#include "hybrid_common.h"
+#include "order.h"  // better, KV, wave_best
 
 namespace hrec {
 

@@ -9,7 +9,7 @@
 // last axis, y = xhat*gamma + beta). Loss MSE, optimiser Adam (:84-88) with
 // TF 2.8's dense ResourceApplyAdam and sparse (IndexedSlices) update rules.
 // f32 throughout (the reference's Keras dtype).
-#include "tt_ln.h"  // wave_sum, ln_row, adam_elem (shared with csrc/tt_fold_in.hip)
+#include "tt_ln.h"  // ln_row, adam_elem (shared with csrc/tt_fold_in.hip); brings wave.h's wave_xor_sum
 
 namespace hrec {
 
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(kBlock) void tt_backward_kernel(
     const int64_t g = r0 + r;
     float s = 0.f;
     for (int c = lane; c < d; c += kWave) s = fmaf(uvec[g * d + c], ivec[g * d + c], s);
-    const float yhat = wave_sum(s);
+    const float yhat = wave_xor_sum(s);
     const float e = yhat - y[g];
     const float dy = 2.0f * e / (float)B;
     if (lane == 0) {
@@ -356,8 +356,8 @@ __global__ __launch_bounds__(kBlock) void tt_backward_kernel(
       m1 += dxh;
       m2 += dxh * ixhat[g * d + c];
     }
-    m1 = wave_sum(m1) / (float)d;
-    m2 = wave_sum(m2) / (float)d;
+    m1 = wave_xor_sum(m1) / (float)d;
+    m2 = wave_xor_sum(m2) / (float)d;
     for (int c = lane; c < d; c += kWave) {
       const float xh = ixhat[g * d + c];
       const float dxh = dy * uvec[g * d + c] * P.gi[c];
@@ -369,8 +369,8 @@ __global__ __launch_bounds__(kBlock) void tt_backward_kernel(
       u1 += dxh;
       u2 += dxh * uxhat[g * d + c];
     }
-    u1 = wave_sum(u1) / (float)d;
-    u2 = wave_sum(u2) / (float)d;
+    u1 = wave_xor_sum(u1) / (float)d;
+    u2 = wave_xor_sum(u2) / (float)d;
     for (int c = lane; c < d; c += kWave) {
       const float xh = uxhat[g * d + c];
       const float dxh = dy * ivec[g * d + c] * P.gu[c];

@@ -18,7 +18,7 @@
 // turned into an address - and the marked ones are taken four at a time in
 // CSR order, their four rows loaded before the first dot so the loads overlap.
 // Every sum has a fixed order (columns ascending inside a lane, then the xor
-// butterfly of wave_sum; entries in CSR order), so equal inputs give equal
+// butterfly of wave_xor_sum; entries in CSR order), so equal inputs give equal
 // bits. The item vectors of a user are re-read from the caches at every step
 // (a short history is a few KiB); staging them in LDS was not tried. Not tuned.
 #include "tt_ln.h"
@@ -27,10 +27,6 @@ namespace hrec {
 
 constexpr int kFoldWaves = 4;  // users per block
 constexpr int kFoldGroup = 4;  // history entries whose rows are in flight together
-
-__device__ __forceinline__ float lane_value(float x, int lane) {  // lane: wave-uniform
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), lane));
-}
 
 template <int NE>
 __global__ __launch_bounds__(kFoldWaves* kWave) void tt_fold_in_kernel(
@@ -83,7 +79,6 @@ __global__ __launch_bounds__(kFoldWaves* kWave) void tt_fold_in_kernel(
         rt = ratings[q];
       }
       uint64_t todo = __ballot((uint64_t)ir < (uint64_t)n_items);
-      const int ir_lo = (int)(uint32_t)ir, ir_hi = (int)(ir >> 32);
       while (todo) {  // wave-uniform
         int src[kFoldGroup], cnt = 0;
 #pragma unroll
@@ -99,10 +94,9 @@ __global__ __launch_bounds__(kFoldWaves* kWave) void tt_fold_in_kernel(
         float vr[kFoldGroup][NE], dot[kFoldGroup], rr[kFoldGroup];
 #pragma unroll
         for (int g = 0; g < kFoldGroup; ++g) {
-          const int64_t r = ((int64_t)__builtin_amdgcn_readlane(ir_hi, src[g]) << 32) |
-                            (int64_t)(uint32_t)__builtin_amdgcn_readlane(ir_lo, src[g]);
+          const int64_t r = lane_read(ir, src[g]);
           const float* __restrict__ vp = item_vec + r * d;
-          rr[g] = lane_value(rt, src[g]);
+          rr[g] = lane_read(rt, src[g]);
 #pragma unroll
           for (int i = 0; i < NE; ++i) vr[g][i] = on[i] ? vp[lane + kWave * i] : 0.f;
         }
@@ -114,7 +108,7 @@ __global__ __launch_bounds__(kFoldWaves* kWave) void tt_fold_in_kernel(
           dot[g] = s;
         }
 #pragma unroll
-        for (int g = 0; g < kFoldGroup; ++g) dot[g] = wave_sum(dot[g]);
+        for (int g = 0; g < kFoldGroup; ++g) dot[g] = wave_xor_sum(dot[g]);
 #pragma unroll
         for (int g = 0; g < kFoldGroup; ++g) {
           if (g < cnt) {
@@ -142,8 +136,8 @@ __global__ __launch_bounds__(kFoldWaves* kWave) void tt_fold_in_kernel(
         m2 += dxh[i] * xh[i];
       }
     }
-    m1 = wave_sum(m1) / (float)d;
-    m2 = wave_sum(m2) / (float)d;
+    m1 = wave_xor_sum(m1) / (float)d;
+    m2 = wave_xor_sum(m2) / (float)d;
     const float lr = step_lr[t];
 #pragma unroll
     for (int i = 0; i < NE; ++i) {

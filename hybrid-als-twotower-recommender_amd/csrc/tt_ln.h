@@ -4,17 +4,11 @@
 // Keras' sparse Adam step.
 #pragma once
 
-#include "common.h"
+#include "wave.h"  // wave_xor_sum
 
 namespace hrec {
 
 constexpr float kLnEps = 1e-3f;
-
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, kWave);
-  return x;
-}
 
 // LayerNorm of one row held in LDS (length d), one wave. Writes y (and the
 // normalised row + 1/std when save != nullptr).
@@ -23,13 +17,13 @@ __device__ __forceinline__ void ln_row(const float* __restrict__ x, int d, const
                                        float* __restrict__ xhat_out, float* __restrict__ rstd_out, int lane) {
   float s = 0.f;
   for (int c = lane; c < d; c += kWave) s += x[c];
-  const float mean = wave_sum(s) / (float)d;
+  const float mean = wave_xor_sum(s) / (float)d;
   float q = 0.f;
   for (int c = lane; c < d; c += kWave) {
     const float t = x[c] - mean;
     q += t * t;
   }
-  const float var = wave_sum(q) / (float)d;
+  const float var = wave_xor_sum(q) / (float)d;
   const float rstd = 1.0f / sqrtf(var + kLnEps);
   for (int c = lane; c < d; c += kWave) {
     const float xh = (x[c] - mean) * rstd;
@@ -50,7 +44,7 @@ __device__ __forceinline__ float ln_regs(const float (&x)[NE], const bool (&on)[
 #pragma unroll
   for (int i = 0; i < NE; ++i)
     if (on[i]) s += x[i];
-  const float mean = wave_sum(s) / (float)d;
+  const float mean = wave_xor_sum(s) / (float)d;
   float q = 0.f;
 #pragma unroll
   for (int i = 0; i < NE; ++i)
@@ -58,7 +52,7 @@ __device__ __forceinline__ float ln_regs(const float (&x)[NE], const bool (&on)[
       const float t = x[i] - mean;
       q += t * t;
     }
-  const float var = wave_sum(q) / (float)d;
+  const float var = wave_xor_sum(q) / (float)d;
   const float rstd = 1.0f / sqrtf(var + kLnEps);
 #pragma unroll
   for (int i = 0; i < NE; ++i) {

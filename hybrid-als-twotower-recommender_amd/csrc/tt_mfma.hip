@@ -26,7 +26,7 @@
 // output row (4d).
 #include <type_traits>
 
-#include "common.h"
+#include "wave.h"  // wave_xor_sum
 
 namespace hrec {
 
@@ -337,16 +337,14 @@ __global__ __launch_bounds__(256) void tt_ln_rows_kernel(float* __restrict__ x, 
   float* xr = x + r * d;
   float s = 0.f;
   for (int c = lane; c < d; c += kWave) s += xr[c];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, kWave);
+  s = wave_xor_sum(s);
   const float mean = s / (float)d;
   float qv = 0.f;
   for (int c = lane; c < d; c += kWave) {
     const float t = xr[c] - mean;
     qv += t * t;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) qv += __shfl_xor(qv, off, kWave);
+  qv = wave_xor_sum(qv);
   const float rstd = 1.0f / sqrtf(qv / (float)d + kLnEpsM);
   for (int c = lane; c < d; c += kWave) {
     const float xh = (xr[c] - mean) * rstd;
@@ -440,8 +438,7 @@ __global__ __launch_bounds__(256) void tt_bwd_rows_kernel(TTBwd P, const float* 
   const float* v = ivec + g * d;
   float s = 0.f;
   for (int c = lane; c < d; c += kWave) s = fmaf(u[c], v[c], s);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, kWave);
+  s = wave_xor_sum(s);
   const float e = s - y[g];
   const float dy = 2.0f * e / (float)B;
   // item LN backward: dxh = dy·u·gamma ; dx = rstd·(dxh - mean(dxh) - xh·mean(dxh·xh))

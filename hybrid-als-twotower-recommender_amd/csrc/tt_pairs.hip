@@ -111,7 +111,7 @@ __global__ __launch_bounds__(kPairBlock) void tt_pairs_kernel(
     srow[w][0][lane] = mu;
     srow[w][1][lane] = mv;
     fetch_ids(t + t_step, ur, ir, y);
-    pair_wave_sync();
+    wave_lds_fence();
     float acc = 0.f;
     for (int c0 = 0; c0 < d; c0 += CW) {
       const int col = c0 + VW * q;  // this lane's first column; VW divides d, so col < d covers the vector
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(kPairBlock) void tt_pairs_kernel(
           }
         }
       }
-      pair_wave_sync();
+      wave_lds_fence();
       const float* __restrict__ xu = tu + lane * STR;
       const float* __restrict__ xv = tv + lane * STR;
       if (permuted) {  // d is a multiple of CW: two whole steps of 16 per chunk
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(kPairBlock) void tt_pairs_kernel(
         }
         for (; c < kc; ++c) acc = fmaf(xu[c], xv[c], acc);
       }
-      pair_wave_sync();  // the next chunk / tile overwrites the pieces
+      wave_lds_fence();  // the next chunk / tile overwrites the pieces
     }
     const float pred = known ? acc : __builtin_nanf("");
     if (p < n) {
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(kPairBlock) void tt_pairs_kernel(
   // lanes (xor tree), then the four waves in wave order: a fixed order
 #pragma unroll
   for (int i = 0; i < HREC_PAIR_SUMS; ++i) {
-#pragma unroll
+#pragma unroll  // written out: wave_xor_sum here changes the generated code
     for (int off = 32; off > 0; off >>= 1) s[i] += __shfl_xor(s[i], off, kWave);
     if (lane == 0) red[w][i] = s[i];
   }

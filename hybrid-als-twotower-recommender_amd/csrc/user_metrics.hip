@@ -113,29 +113,6 @@ __device__ double um_sum(const double* __restrict__ a, int64_t n, double* vs, in
   return vs[0];
 }
 
-template <typename T>
-__device__ __forceinline__ T um_wave_sum(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-__device__ __forceinline__ double um_min(double a, double b) { return fmin(a, b); }
-__device__ __forceinline__ float um_min(float a, float b) { return fminf(a, b); }
-__device__ __forceinline__ double um_max(double a, double b) { return fmax(a, b); }
-__device__ __forceinline__ float um_max(float a, float b) { return fmaxf(a, b); }
-template <typename T>
-__device__ __forceinline__ T um_wave_min(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = um_min(v, __shfl_xor(v, off, kWave));
-  return v;
-}
-template <typename T>
-__device__ __forceinline__ T um_wave_max(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = um_max(v, __shfl_xor(v, off, kWave));
-  return v;
-}
-
 // np.digitize(x, [0.33, 0.66]): NaN sorts past both edges.
 __device__ __forceinline__ int um_grade(double x) { return x != x ? 2 : (x >= 0.33 ? 1 : 0) + (x >= 0.66 ? 1 : 0); }
 
@@ -176,13 +153,13 @@ __device__ __forceinline__ void um_row(const UmParams& P, int64_t row, int lane,
       ++m;
       const S s = um_score<SRC>(P, row, c, f);
       tmin = fmin(tmin, r), tmax = fmax(tmax, r);
-      pmin = um_min(pmin, s), pmax = um_max(pmax, s);
+      pmin = lane_min(pmin, s), pmax = lane_max(pmax, s);
       inf |= (s - s != (S)0 && s == s) ? 1 : 0;
     }
   }
-  n_rel = um_wave_sum(n_rel), m = um_wave_sum(m), inf = um_wave_sum(inf);
-  tmin = um_wave_min(tmin), tmax = um_wave_max(tmax);
-  pmin = um_wave_min(pmin), pmax = um_wave_max(pmax);
+  n_rel = wave_xor_sum(n_rel), m = wave_xor_sum(m), inf = wave_xor_sum(inf);
+  tmin = wave_xor_min(tmin), tmax = wave_xor_max(tmax);
+  pmin = wave_xor_min(pmin), pmax = wave_xor_max(pmax);
   // 3. hits below each k
   int len = P.list_len ? P.list_len[row] : P.list_n;
   len = len < 0 ? 0 : (len > P.list_n ? P.list_n : len);
@@ -201,7 +178,7 @@ __device__ __forceinline__ void um_row(const UmParams& P, int64_t row, int lane,
     for (int i = 0; i < kUmMaxK; ++i) hk[i] += (i < nk && pos < P.k[i]) ? 1 : 0;
   }
 #pragma unroll
-  for (int i = 0; i < kUmMaxK; ++i) hk[i] = um_wave_sum(hk[i]);
+  for (int i = 0; i < kUmMaxK; ++i) hk[i] = wave_xor_sum(hk[i]);
   // 4. grades and errors over the common items
   int c2 = 0, c1 = 0, c0 = 0, s2 = 0, s1 = 0, s0 = 0, t2 = 0, t1 = 0, bad = 0;
   double sabs = 0.0, ssq = 0.0;
@@ -236,10 +213,10 @@ __device__ __forceinline__ void um_row(const UmParams& P, int64_t row, int lane,
       sabs += fabs(d);
       ssq += d * d;
     }
-    c2 = um_wave_sum(c2), c1 = um_wave_sum(c1), c0 = um_wave_sum(c0);
-    s2 = um_wave_sum(s2), s1 = um_wave_sum(s1), s0 = um_wave_sum(s0);
-    t2 = um_wave_sum(t2), t1 = um_wave_sum(t1), bad = um_wave_sum(bad);
-    sabs = um_wave_sum(sabs), ssq = um_wave_sum(ssq);
+    c2 = wave_xor_sum(c2), c1 = wave_xor_sum(c1), c0 = wave_xor_sum(c0);
+    s2 = wave_xor_sum(s2), s1 = wave_xor_sum(s1), s0 = wave_xor_sum(s0);
+    t2 = wave_xor_sum(t2), t1 = wave_xor_sum(t1), bad = wave_xor_sum(bad);
+    sabs = wave_xor_sum(sabs), ssq = wave_xor_sum(ssq);
   }
   if (lane != 0) return;
   // 5. the row's values
@@ -301,7 +278,7 @@ __global__ __launch_bounds__(256) void um_kernel(const UmParams P) {
   const int64_t row = (int64_t)blockIdx.x * 4 + w;
   const int nslots = 2 * (2 * P.n_k + 3) + HREC_UM_STATUS_BITS;
   for (int i = lane; i < kUmMaxSlots; i += kWave) red[w][i] = 0.0;
-  hl_wave_sync();
+  wave_lds_fence();
   if (row < P.n_rows) um_row<SRC>(P, row, lane, red[w], vs[w], wo[w], wn[w]);  // wave-uniform
   __syncthreads();
   if ((int)threadIdx.x < nslots) {
@@ -317,7 +294,7 @@ __global__ __launch_bounds__(64) void um_reduce_kernel(const double* __restrict_
   const int lane = threadIdx.x, i = blockIdx.x;
   double v = 0.0;
   for (int64_t b = lane; b < n_blocks; b += 64) v += partials[b * nslots + i];
-  v = um_wave_sum(v);
+  v = wave_xor_sum(v);
   if (lane == 0) sums[i] = v;
 }
 
