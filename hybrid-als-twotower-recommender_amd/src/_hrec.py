@@ -111,6 +111,12 @@ _SIGNATURES = {
                                  _c_dbl, _c_i32, _vp, _vp, _vp, _vp]),
     "hrec_als_explain": (_c_i32, [_vp, _c_i64, _c_i32, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i32, _c_i32,
                                   _c_dbl, _c_i32, _c_dbl, _vp, _c_i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hrec_cosine_items_bytes": (_c_sz, [_c_i64, _c_i32]),
+    "hrec_cosine_items": (_c_i32, [_vp, _c_i64, _c_i32, _c_i64, _vp, _vp, _vp]),
+    "hrec_cosine_topk_workspace_bytes": (_c_sz, [_c_i32, _c_i64, _c_i32, _c_i32, _c_i32]),
+    "hrec_cosine_topk": (_c_i32, [_vp, _c_i64, _c_i32, _c_i64, _vp, _vp, _c_i32, _c_i32, _c_i32, _c_dbl, _c_i32, _vp, _vp,
+                                  _vp, _vp, _vp, _vp, _c_sz, _vp]),
+    "hrec_cosine_topk_counts": (_c_i32, [_vp, _c_i32, _c_i64, _c_i32, _c_i32, _vp, _vp]),
     "hrec_fuse_workspace_bytes": (_c_sz, [_c_i64, _c_i32]),
     "hrec_fuse_topk": (_c_i32, [_vp, _vp, _c_i32, _c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp,
                                 _c_sz, _vp]),
@@ -2085,6 +2091,90 @@ def mmr_rerank(pool, scores, vectors, inv_norm, lambda_, top_n, pool_len=None, d
         _dev(out_pos, torch.int32, "out_pos"), _dev(out_len, torch.int32, "out_len"),
         _dev(out_value, torch.float64, "out_value"), _stream()))
     return out_pos, out_len, out_value
+
+
+# ------------------------------------------------- cosine neighbours
+COSINE_TOP_MAX = 1024  # largest top_k of cosine_topk
+COSINE_MODES = {"auto": 0, "exhaustive": 1, "pruned": 2}
+COSINE_AUTO_CUT = 3072  # kCosAutoCut of csrc/cosine_topk.hip: auto ranks smaller matrices exhaustively
+COSINE_CAP = 4096  # kCosCap: rows the pruned arm's filter may keep per query
+
+
+def cosine_items(vectors, inv_norm, d=None):
+    """hrec_cosine_items: the bf16 unit-row operand of cosine_topk's pruned
+    arm (uint8 device buffer), prepared once per matrix and reused by every
+    batch. vectors f32 [n, >= d] with inv_norm = row_inv_norms(vectors, d)."""
+    name = "cosine_items"
+    v_ptr, n, d, ld = _vector_rows(name, vectors, d)
+    if inv_norm.numel() != n:
+        raise HrecError(f"{name}: inv_norm must hold one value per vector")
+    out = torch.empty(int(lib().hrec_cosine_items_bytes(n, d)), dtype=torch.uint8, device=vectors.device)
+    _check("hrec_cosine_items", lib().hrec_cosine_items(v_ptr, n, d, ld, _dev(inv_norm, torch.float64, "inv_norm"),
+                                                        _dev(out, torch.uint8, "out"), _stream()))
+    return out
+
+
+def cosine_topk_workspace_bytes(n_q, n, top_k, d, mode=0):
+    return int(lib().hrec_cosine_topk_workspace_bytes(int(n_q), int(n), int(top_k), int(d), int(mode)))
+
+
+def cosine_topk_counts(ws, n_q, n, top_k, d):
+    """int32 device [n_q]: the rows the pruned arm's filter kept per query in
+    the last mode-2 cosine_topk call on the workspace `ws` (same shape)."""
+    out = torch.empty(n_q, dtype=torch.int32, device=ws.device)
+    _check("hrec_cosine_topk_counts", lib().hrec_cosine_topk_counts(
+        _dev(ws, torch.uint8, "ws"), int(n_q), int(n), int(top_k), int(d), _dev(out, torch.int32, "out"), _stream()))
+    return out
+
+
+def cosine_topk(vectors, inv_norm, query_rows, top_k, skip_self=True, min_sim=float("-inf"), mode=0, items=None,
+                d=None, ws=None, want_overflow=False, redo=True):
+    """hrec_cosine_topk: per query row (int64 device rows of `vectors`; a row
+    outside [0, n) is an unknown query) the stable top-k of the cosines to
+    every row: larger first, equal cosines -> the smaller column, the query's
+    own column left out when skip_self, cut to the prefix with cosine >
+    min_sim. vectors f32 [n, >= d] with inv_norm = row_inv_norms(vectors, d);
+    mode 0 auto / 1 exhaustive / 2 pruned (or the names of COSINE_MODES);
+    items = cosine_items(vectors, inv_norm, d) for the pruned arm. Returns
+    device (out_idx int64 [n_q, top_k], -1 past out_len; out_val f64, NaN past
+    out_len; out_len int32 [n_q]). A call whose pruned arm raised its overflow
+    flag is redone in the exhaustive arm (want_overflow: the flag of the first
+    attempt is returned as a fourth value; redo=False leaves the incomplete
+    result and the workspace as the pruned arm left them, for
+    cosine_topk_counts). The same bits on every call and in every mode."""
+    name = "cosine_topk"
+    v_ptr, n, d, ld = _vector_rows(name, vectors, d)
+    dev = vectors.device
+    mode = COSINE_MODES.get(mode, mode)
+    if inv_norm.numel() != n:
+        raise HrecError(f"{name}: inv_norm must hold one value per vector")
+    if not isinstance(query_rows, torch.Tensor) or query_rows.dim() != 1:
+        raise HrecError(f"{name}: query_rows must be a 1-D device tensor")
+    n_q, top_k = int(query_rows.numel()), int(top_k)
+    out_idx = torch.empty((n_q, max(top_k, 0)), dtype=torch.int64, device=dev)
+    out_val = torch.empty((n_q, max(top_k, 0)), dtype=torch.float64, device=dev)
+    out_len = torch.empty(n_q, dtype=torch.int32, device=dev)
+    overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+    raised = False
+
+    def run(m):
+        nonlocal ws
+        need = cosine_topk_workspace_bytes(n_q, n, top_k, d, m)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _check("hrec_cosine_topk", lib().hrec_cosine_topk(
+            v_ptr, n, d, ld, _dev(inv_norm, torch.float64, "inv_norm"), _dev(query_rows, torch.int64, "query_rows"),
+            n_q, top_k, int(bool(skip_self)), float(min_sim), int(m), _dev(items, torch.uint8, "items"),
+            _dev(out_idx, torch.int64, "out_idx"), _dev(out_val, torch.float64, "out_val"),
+            _dev(out_len, torch.int32, "out_len"), _dev(overflow, torch.int32, "overflow"),
+            _dev(ws, torch.uint8, "ws"), ws.numel(), _stream()))
+
+    run(mode)
+    if n_q and mode != 1 and int(overflow.item()):
+        raised = True
+        if redo:
+            run(1)
+    return (out_idx, out_val, out_len, raised) if want_overflow else (out_idx, out_val, out_len)
 
 
 # ------------------------------------------------- ALS explanations

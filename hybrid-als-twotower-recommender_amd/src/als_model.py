@@ -1202,6 +1202,37 @@ class ALSModel:
         anything but None raises ValueError."""
         return self._recommend_frame("item", items, num_users, exclude, diversify)
 
+    # ------------------------------------------------ cosine neighbours
+    # implicit's similar_items / similar_users ("more like this"): the rows
+    # of one factor matrix ranked by cosine (hrec_cosine_topk, DESIGN §31).
+    def _similar_frame(self, side, subset, num, min_similarity):
+        model = self._trained()
+        col, ids, F = ("userId", model.user_ids, model.U) if side == "user" else ("itemId", model.item_ids, model.V)
+        # the ids ascend: "the earlier row first" is "the smaller id first"
+        return ranked_lists.similar_rows_frame(col, ids, F, model.k, subset, num, min_similarity,
+                                               ids_dev=model._ids_device(side))
+
+    def similar_items(self, items=None, num=10, min_similarity=None):
+        """implicit's similar_items: a DataFrame with one row per item
+        (`itemId` ascending; None: every item of the model; a DataFrame with
+        an itemId column or an array-like of ids otherwise: its distinct ids,
+        unknown ones left out) and `recommendations`: the item's `num` (1 ..
+        1024) nearest other items by the cosine between item factors, as
+        (itemId: int, similarity: float) tuples, best first. Equal
+        similarities keep the smaller itemId first; the item itself never
+        appears; min_similarity (None: no cut) keeps the similarities above
+        it (the reference's _find_similar_items: num=3, min_similarity=0.5).
+        A similarity is the f64 cosine of hrec_cosine_topk: the same bits on
+        every call. An item with a zero factor row has similarity 0.0 to
+        everything. Ranked on the device; on every rank of a multi-GPU world
+        the whole answer."""
+        return self._similar_frame("item", items, num, min_similarity)
+
+    def similar_users(self, users=None, num=10, min_similarity=None):
+        """implicit's similar_users: similar_items over the user factors
+        (`userId`, (userId, similarity) tuples)."""
+        return self._similar_frame("user", users, num, min_similarity)
+
     # ----------------------------------------- RankingEvaluator / RankingMetrics
     RANKING_METRIC_NAMES = ("meanAveragePrecision", "meanAveragePrecisionAtK", "precisionAtK", "recallAtK",
                             "ndcgAtK")

@@ -305,6 +305,29 @@ class RecommenderEvaluator:
         return pd.DataFrame({key: lists[key].to_numpy(), "recommendations": picked})
 
     @staticmethod
+    def similar_rows(vectors, ids, queries=None, num=10, min_similarity=None):
+        """Cosine neighbours among the rows of any matrix (not in the
+        reference; user-tower outputs for instance): `vectors` [len(ids), d <=
+        256] (f32; array or device tensor) holds the vector of ids[j] (int,
+        distinct). Returns a lists frame with `id` (queries None: every id, in
+        row order; an array-like otherwise: its distinct ids ascending, those
+        outside `ids` left out) and `recommendations`: the `num` (1 .. 1024)
+        nearest other rows as (id, similarity: float) tuples, best first;
+        equal similarities keep the earlier row first; min_similarity (None:
+        no cut) keeps the similarities above it. hrec_cosine_topk: the same
+        bits on every call. evaluate_lists and diversify_lists take the frame
+        as it is."""
+        _hrec.require_device()
+        iid = ranked_lists.int_ids(np.asarray(ids).reshape(-1), "ids")
+        if np.unique(iid).size != iid.size:
+            raise ValueError("similar_rows: ids must not repeat an id")
+        v = vectors if isinstance(vectors, torch.Tensor) else torch.as_tensor(np.asarray(vectors, np.float32))
+        if v.dim() != 2 or v.shape[0] != iid.size or not 1 <= v.shape[1] <= _hrec.LQ_MAX_D:
+            raise ValueError(f"similar_rows: vectors must be [len(ids), 1 .. {_hrec.LQ_MAX_D}]")
+        v = v.to(torch.float32).cuda().contiguous()
+        return ranked_lists.similar_rows_frame("id", iid, v, int(v.shape[1]), queries, num, min_similarity)
+
+    @staticmethod
     def summarize(frame):
         """Per metric column of an evaluate_scores / evaluate_users frame: its
         mean over the users where it is defined (not NaN) and their count, as

@@ -593,6 +593,20 @@ class HybridRecommendationSystem:
         vec = m.V[rows.clamp(min=0)] * (rows >= 0).unsqueeze(1)  # an item the ALS model does not know: the zero vector
         return vec.contiguous(), m.k
 
+    def similar_items(self, item_features, items=None, num=10, min_similarity=None, similarity="twotower"):
+        """TwoTowerModel.similar_items over the candidates of `item_features`
+        with the cosines of list_quality_metrics' `similarity`: "twotower":
+        between the candidates' item-tower vectors; "als": between the ALS
+        item factors gathered into candidate order, where an item the ALS
+        model does not know is the zero vector: similarity 0.0 to everything.
+        Equal similarities keep frame order. No counterpart in the reference:
+        failures raise."""
+        self._require_models()
+        cand = self.twotower_model.candidates(item_features)
+        vectors, d = self._similarity_vectors(cand, similarity)
+        return ranked_lists.similar_rows_frame("itemId", cand.item_ids, vectors, d, items, num, min_similarity,
+                                               ids_dev=cand.ids_dev)
+
     def list_quality_metrics(self, item_features, k=10, users=None, exclude=None, history=None, actual=None, f1_k=10,
                              similarity="twotower", diversify=None):
         """ALSModel.list_quality_metrics for the fused top-k lists over the

@@ -534,6 +534,101 @@ def lists_frame(key_col, keys, ids, val, lens=None):
     return pd.DataFrame({key_col: keys, "recommendations": recs})
 
 
+# -------------------------------------------------------- cosine neighbours
+# "More like this" (hrec_cosine_topk): the rows of one matrix
+# ranked by their cosine to a query row of the same matrix.
+SIMILAR_BATCH = 4096  # queries of one hrec_cosine_topk call
+SIMILAR_WS_BYTES = 1 << 30  # a call's workspace stays below this (while a batch of one query allows)
+SIMILAR_MAX = _hrec.COSINE_TOP_MAX
+
+
+def similar(vectors, d, query_rows, num, min_similarity=None, skip_self=True, mode=0, stats=None):
+    """The `num` nearest rows of `vectors` (f32 device [n, >= d], the first d
+    columns) by cosine for every query row (int64, numpy or device: rows of
+    the same matrix; outside [0, n): no list): device (columns int64 [n_q,
+    num] best first, -1 past a list's length; sims f64, NaN there; lens int32
+    [n_q]). Equal cosines keep the smaller column, the query itself is left
+    out (skip_self), min_similarity (None: no cut) keeps cosines above it.
+    hrec_row_inv_norms and the pruned arm's operand once, then sub-batches of
+    SIMILAR_BATCH queries (fewer where the workspace would pass
+    SIMILAR_WS_BYTES); a batch whose pruned arm raised its flag is redone in
+    the exhaustive arm, in the same workspace, and under mode 0 (auto) every
+    batch after it takes the exhaustive arm directly: at most one pruned pass
+    is wasted on vectors the margin cannot prune. mode: 0 / "auto", 1 /
+    "exhaustive", 2 / "pruned". stats (a dict, optional) counts batches and
+    flagged."""
+    num = check_num(num, SIMILAR_MAX)
+    dev = vectors.device
+    q = torch.as_tensor(query_rows, dtype=torch.int64, device=dev).reshape(-1).contiguous()
+    n, n_q = int(vectors.shape[0]), int(q.numel())
+    cols = torch.full((n_q, num), -1, dtype=torch.int64, device=dev)
+    sims = torch.full((n_q, num), float("nan"), dtype=torch.float64, device=dev)
+    lens = torch.zeros(n_q, dtype=torch.int32, device=dev)
+    if n == 0 or n_q == 0:
+        return cols, sims, lens
+    mode = _hrec.COSINE_MODES.get(mode, mode)
+    min_sim = float("-inf") if min_similarity is None else float(min_similarity)
+    inv = _hrec.row_inv_norms(vectors, d)
+    items = _hrec.cosine_items(vectors, inv, d) if mode != 1 else None
+    def need(b):  # one workspace serves the arm asked for and the exhaustive redo of a flagged batch
+        return max(_hrec.cosine_topk_workspace_bytes(b, n, num, d, mode),
+                   _hrec.cosine_topk_workspace_bytes(b, n, num, d, 1))
+
+    batch = min(SIMILAR_BATCH, n_q)
+    while batch > 1 and need(batch) > SIMILAR_WS_BYTES:
+        batch = (batch + 1) // 2
+    ws = torch.empty(need(batch), dtype=torch.uint8, device=dev)
+    for lo in range(0, n_q, batch):
+        hi = min(lo + batch, n_q)
+        i, v, m, raised = _hrec.cosine_topk(vectors, inv, q[lo:hi], num, skip_self=skip_self, min_sim=min_sim,
+                                            mode=mode, items=items, d=d, ws=ws, want_overflow=True)
+        cols[lo:hi], sims[lo:hi], lens[lo:hi] = i, v, m
+        if stats is not None:
+            stats["batches"] = stats.get("batches", 0) + 1
+            stats["flagged"] = stats.get("flagged", 0) + int(raised)
+        if raised and mode == 0:
+            # vectors too concentrated for the margin to prune: the bound would cost every later batch a wasted
+            # pass too, so the rest goes through the exhaustive arm (the same bits); an explicit mode 2 is kept
+            mode = 1
+    return cols, sims, lens
+
+
+def similar_frame(key_col, keys, id_table, vectors, d, query_rows, num, min_similarity=None, mode=0):
+    """similar() as a lists frame: per key its [(id, similarity: float)], best
+    first, the ids gathered from id_table (int64 device, one per row of
+    vectors) on the device."""
+    cols, sims, lens = similar(vectors, d, query_rows, num, min_similarity, mode=mode)
+    n = int(vectors.shape[0])
+    if cols.numel() == 0 or n == 0:
+        return lists_frame(key_col, keys, cols, sims, lens)
+    ids, sims = pad_lists(id_table, cols, sims, lens, n)
+    return lists_frame(key_col, keys, ids, sims, lens)
+
+
+def similar_rows_frame(key_col, ids, vectors, d, queries, num, min_similarity=None, ids_dev=None):
+    """similar_frame over the rows of `vectors` named by `ids` (int64,
+    distinct, one per row, in any order). queries None: every row, in row
+    order; a DataFrame with a key_col column or an array-like of ids: its
+    distinct ids ascending, those outside `ids` left out. Equal similarities
+    keep the earlier ROW first (the smaller id where ids ascend)."""
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    if int(vectors.shape[0]) != ids.size:
+        raise ValueError(f"ids must name every row of vectors ({ids.size} ids, {int(vectors.shape[0])} rows)")
+    num = check_num(num, SIMILAR_MAX)
+    if queries is None:
+        rows = np.arange(ids.size, dtype=np.int64)
+    else:
+        if hasattr(queries, "columns"):
+            queries = queries[key_col]
+        keys = np.unique(int_ids(np.asarray(queries).reshape(-1), key_col))
+        order = np.argsort(ids, kind="stable")
+        pos = np.minimum(np.searchsorted(ids[order], keys), max(ids.size - 1, 0))
+        rows = order[pos][ids[order][pos] == keys] if ids.size else np.zeros(0, np.int64)
+    if ids_dev is None:
+        ids_dev = torch.as_tensor(ids, device=vectors.device)
+    return similar_frame(key_col, ids[rows], ids_dev, vectors, d, rows, num, min_similarity)
+
+
 # ------------------------------------------------------- ALS explanations
 # Why an ALS prediction is what it is (hrec_als_explain, DESIGN §30): a user
 # row solves its normal equations, so a prediction is a sum of one term per

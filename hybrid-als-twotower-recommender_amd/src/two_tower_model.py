@@ -512,6 +512,22 @@ class TwoTowerModel:
         return self.recommend_for_users(np.arange(int(self.num_users), dtype=np.int64), item_features, num_items,
                                         exclude, diversify)
 
+    def similar_items(self, item_features, items=None, num=10, min_similarity=None):
+        """implicit's similar_items over a candidate frame (or candidates()'s
+        object): a DataFrame with `itemId` (None: every candidate, in frame
+        order; a DataFrame with an itemId column or an array-like otherwise:
+        its distinct ids ascending, those outside the frame left out) and
+        `recommendations`: the `num` (1 .. 1024) nearest other candidates by
+        the cosine between item-tower vectors, as (itemId, similarity: float)
+        tuples, best first. Equal similarities keep frame order; the item
+        itself never appears; min_similarity (None: no cut) keeps the
+        similarities above it. Any embedding_size up to 256 (the default 50
+        included) goes through hrec_cosine_topk; the same bits on every call."""
+        cand = self.candidates(item_features)
+        d = int(cand.vectors.shape[1]) if len(cand) else 1
+        return ranked_lists.similar_rows_frame("itemId", cand.item_ids, cand.vectors, d, items, num, min_similarity,
+                                               ids_dev=cand.ids_dev)
+
     def ranking_metrics(self, data, item_features, k=10, label_col=None, min_rating=None, exclude=None,
                         diversify=None):
         """Spark's RankingMetrics (binary relevance) of the model's top-k

@@ -38,6 +38,9 @@
  *          (no reference line)                        -> hrec_mmr_rerank
  *   ALS predictions explained by the user's history
  *          (no reference line)                        -> hrec_als_explain
+ *   Cosine neighbours of rows of one matrix
+ *          src/als_model.py:93-104 (factors, towers)  -> hrec_cosine_items,
+ *                                                          hrec_cosine_topk
  *   Keras  two-tower graph   src/two_tower_model.py:38-89 -> hrec_tt_*
  *   Keras  fit of one user-embedding row, everything else
  *          frozen, for new users (no reference line)  -> hrec_tt_fold_in_users
@@ -950,6 +953,67 @@ int hrec_als_explain(const int64_t* lists, int64_t lists_ld, int list_n, const i
                      int64_t n_items, int k, int kp, double reg_param, int implicit, double alpha,
                      const double* yty, int top_m, double* out_total, int32_t* out_pos,
                      double* out_val, int32_t* out_len, float* out_row, void* stream);
+
+/* Cosine neighbours of rows of one matrix (additive to ABI 7): "more like
+ * this" for item factors, user factors or tower vectors (the reference's
+ * ALSModel._find_similar_items, src/als_model.py:93-104, keeps the top 3 with
+ * sim > 0.5 and skips the item itself).
+ *
+ * hrec_cosine_topk: vectors f32 [n][ld], the first d columns (1 <= d <= 256,
+ * ld >= d, 1 <= n < 2^31; the columns past d are never read); inv_norm f64 [n]
+ * = hrec_row_inv_norms of them; query_rows int64 [n_q] names rows of the same
+ * matrix (a row outside [0, n), -1 included, is an unknown query; repeats are
+ * allowed; 0 <= n_q < 65536). 1 <= top_k <= 1024; skip_self 0 or 1; min_sim
+ * f64 (-inf: no cut; NaN is an error); mode 0 auto, 1 exhaustive, 2 pruned.
+ * The similarity, all f64 and unfused:
+ *   dot(q, j) = the chain acc = acc + (double)v_q[c] * (double)v_j[c] for
+ *     c = 0 .. d - 1 ascending, from 0.0 (the product of two f32 values is
+ *     exact in f64, so a fused multiply-add gives the same bits);
+ *   sim(q, j) = (dot * inv_norm[q]) * inv_norm[j]; +0.0 where inv_norm[q] == 0
+ *     or inv_norm[j] == 0 (hrec_list_quality's zero-vector rule: a row with a
+ *     zero or non-finite squared norm). Every sim is finite.
+ * Per query b: the stable ranking of all columns j in [0, n) by sim, larger
+ * first, equal sims -> the smaller j; with skip_self without column
+ * query_rows[b]; cut to kk = min(top_k, n - skip_self) entries, then to the
+ * prefix with sim > min_sim (strict).
+ * Outputs: out_idx int64 / out_val f64 [n_q][top_k], out_len int32 [n_q]; past
+ * out_len the entries are -1 and NaN; an unknown query has out_len 0.
+ * Mode 1 writes the f64 sims of a sub-batch of queries to the workspace (the
+ * query's own column as NaN) and ranks them with the f64 stable top-k. Mode 2
+ * bounds every sim on the bf16 matrix cores from the prepared operand `items`
+ * (hrec_cosine_items; may be NULL in mode 1, and in mode 0, which then takes
+ * mode 1), runs the exact chain only for the rows a proven margin cannot rule
+ * out and ranks those (csrc/cosine_topk.hip derives the margin). When a
+ * query's kept list overflows, *overflow (device int, written by every call)
+ * is set and the results of the call are incomplete: rerun it in mode 1.
+ * Mode 0 takes mode 1 below a catalogue size fixed in the library (3072 rows,
+ * from measurement) and where top_k * n is too large for the sample bound to
+ * keep the lists within their capacity; like mode 2 it may set *overflow, and
+ * one rerun in mode 1 always completes the call. Equal inputs give equal bits
+ * on every call and in every mode (no floating-point atomics, fixed orders).
+ * n_q == 0 returns HREC_OK and touches nothing.
+ * Workspace: hrec_cosine_topk_workspace_bytes(n_q, n, top_k, d, mode).
+ *
+ * hrec_cosine_items: the operand of mode 2, once per matrix and reused by
+ * every batch: bf16 rows [n][dk] of (float)((double)v_jc * inv_norm[j]), dk =
+ * 32, 64, 128 or 256 columns (zero past d), a zero row where inv_norm is 0.
+ * out: hrec_cosine_items_bytes(n, d) bytes, 256-B aligned.
+ *
+ * hrec_cosine_topk_counts (diagnostics, as hrec_als_score_topk_pruned_counts):
+ * after a mode-2 call, out int32 [n_q] = the rows the filter kept per query,
+ * read from that call's workspace (the same n_q, n, top_k and d); a count
+ * above 4096 is a list that overflowed. */
+size_t hrec_cosine_items_bytes(int64_t n, int d);
+int hrec_cosine_items(const float* vectors, int64_t n, int d, int64_t ld, const double* inv_norm,
+                      void* out, void* stream);
+size_t hrec_cosine_topk_workspace_bytes(int n_q, int64_t n, int top_k, int d, int mode);
+int hrec_cosine_topk(const float* vectors, int64_t n, int d, int64_t ld, const double* inv_norm,
+                     const int64_t* query_rows, int n_q, int top_k, int skip_self, double min_sim,
+                     int mode, const void* items, int64_t* out_idx, double* out_val,
+                     int32_t* out_len, int* overflow, void* workspace, size_t workspace_bytes,
+                     void* stream);
+int hrec_cosine_topk_counts(const void* workspace, int n_q, int64_t n, int top_k, int d,
+                            int32_t* out, void* stream);
 
 /* ------------------------------------------------------ cold-start sim --
  * ALSModel._find_similar_items (src/als_model.py:93-104): out[q*n_items+j] =
